@@ -6,7 +6,12 @@ torch.distributed.run with one rank per GPU.  One bench "step" = one pass of the
 `--mcmc-steps` stretch-move steps of the whole ensemble (W * mcmc_steps walker updates), every state stored
 to the chain in HBM.  W untimed warm-up steps (this is where the hipGraph is captured), then exactly K steps
 bracketed by barrier + torch.cuda.synchronize() on both sides; the time is the MAX over ranks; rank 0 prints
-ONE JSON line.
+ONE JSON line.  `--dump-outputs DIR` writes what the last timed step returned (chain, log-probabilities, final
+walkers) as .npy files; the inputs are seeded, so two builds can be compared output for output.
+
+A plain run measures the headline only.  `--full` adds the side measurements: CPU baselines, predict / Cholesky
+figures, the other configurations, the end-to-end calls and the parity gate against the oracle
+(`--no-cpu-baseline` / `--no-extras` leave parts of them out).
 
 Multi-GPU: `--mode replicas` (default) = one independent 256-walker ensemble per GPU, different seeds, no
 data-path collective (weak scaling).  `--mode shard` = ONE ensemble of 256*N walkers, active half partitioned
@@ -25,6 +30,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 FP64_PEAK_TFLOPS = 78.6   # MI355X fp64 vector = fp64 matrix peak (spec); MI355X_MICROARCH.md lists no fp64 row
+DUMP_LIMIT_BYTES = 64_000_000   # --dump-outputs: all files together
 
 
 _CPU = {}   # worker-side state of the CPU baseline (inherited by fork: no pickling of the GP)
@@ -408,6 +414,31 @@ def config_extras():
     return res
 
 
+def dump_outputs(outdir, chain, chain_lp, coords, logp, acceptance):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the stored chain [steps, walkers, d],
+    its log-probabilities [steps, walkers] (None: not returned by this path), the final walkers and their log-probabilities,
+    the acceptance fractions -- as float64 .npy files.  A chain over the size budget is cut to a fixed, seeded sample of its
+    steps, whose indices go to chain_steps.npy."""
+    os.makedirs(outdir, exist_ok=True)
+    out = {"coords": coords, "log_prob": logp, "acceptance_fraction": acceptance}
+    out = {k: np.asarray(v.cpu().numpy() if hasattr(v, "cpu") else v, dtype=np.float64) for k, v in out.items()}
+    n = int(chain.shape[0])
+    per_step = chain[0].numel() * 8 + (chain_lp[0].numel() * 8 if chain_lp is not None else 0)
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in out.values()) - 4096
+    if n * per_step > room:
+        import torch
+        keep = np.sort(np.random.RandomState(0).choice(n, max(1, room // (per_step + 8)), replace=False))
+        idx = torch.as_tensor(keep, device=chain.device)
+        chain = chain[idx]
+        chain_lp = chain_lp[idx] if chain_lp is not None else None
+        out["chain_steps"] = keep.astype(np.float64)
+    out["chain"] = chain.cpu().numpy().astype(np.float64, copy=False)
+    if chain_lp is not None:
+        out["chain_log_prob"] = chain_lp.cpu().numpy().astype(np.float64, copy=False)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -421,12 +452,20 @@ def main():
     ap.add_argument("--ensembles", type=int, default=1,
                     help="independent ensembles of --walkers walkers sharing every launch on each GPU (default 1 = the "
                          "headline configuration: ONE 256-walker ensemble per GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the predict / Cholesky side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (CPU baselines, predict / Cholesky, other configurations, end-to-end "
+                         "calls, parity gate); a plain run times the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the parity gate")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the predict / Cholesky side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the chain, log-probabilities and final walkers of the last timed step "
+                         "(rank 0) to DIR/<name>.npy (float64, at most 64 MB)")
     ap.add_argument("--shard-extra", action="store_true",
                     help="N > 1: also time ONE ensemble of 256*N walkers sharded over the ranks (all-gather per half step); "
                          "opt-in so that an untested collective path can never cost the headline line")
     args = ap.parse_args()
+    run_cpu = args.full and not args.no_cpu_baseline
+    run_extras = args.full and not args.no_extras
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks here, BEFORE anything in this process touches the GPU (no
@@ -455,7 +494,7 @@ def main():
     # CPU baselines first: the multi-core one forks a pool, which must happen before the GPU is initialised
     cpu_base = cpu_base_all = cpu_base_vec = cpu_pred = cpu_e2e = None
     cpu_chain = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and run_cpu:
         cfg0 = make_config(args.config, N=args.ntrain, W=args.walkers)
         cpu_base = cpu_baseline(cfg0, budget_s=10.0, cores=1)
         cpu_chain = []
@@ -518,9 +557,10 @@ def main():
         state = {"coords": torch.as_tensor(p0, device="cuda"), "step": 0}
 
         def one_step():
-            _, c, _, _ = ens.run(state["coords"], args.mcmc_steps, step0=state["step"], store=True)
+            ch, c, lp, nacc = ens.run(state["coords"], args.mcmc_steps, step0=state["step"], store=True)
             state["coords"] = c
             state["step"] += args.mcmc_steps
+            state["last"] = (ch, getattr(ens, "last_chain_logp", None), c, lp, nacc)
         samples_per_step = Wtot * args.mcmc_steps
         launches_per_step = 2 * args.mcmc_steps
     else:
@@ -531,8 +571,9 @@ def main():
         sampler.run_mcmc(p0, 1, store=False)
 
         def one_step():
-            sampler.run_mcmc(None, args.mcmc_steps, store=True)
+            # the previous step's chain is dropped before the run, so that the last one stays readable (--dump-outputs)
             sampler._chains.clear(); sampler._chain_lps.clear(); sampler._thins.clear()
+            sampler.run_mcmc(None, args.mcmc_steps, store=True)
         samples_per_step = W * E * args.mcmc_steps * world
         launches_per_step = 2 * args.mcmc_steps
 
@@ -560,6 +601,13 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     value = samples_per_step * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        if shard:
+            ch, ch_lp, c, lp, nacc = state["last"]
+            dump_outputs(args.dump_outputs, ch, ch_lp, c, lp, nacc.double() / args.mcmc_steps)
+        else:
+            dump_outputs(args.dump_outputs, sampler._chains[-1], sampler._chain_lps[-1], sampler._coords, sampler._logp,
+                         sampler.acceptance_fraction)
 
     # Secondary measurement on N > 1 GPUs (every rank takes part): ONE ensemble of 256*N walkers sharded over the ranks
     # with an RCCL all-gather of the updated half after every half step (alabi_amd/dist.py).  Reported next to the
@@ -650,7 +698,7 @@ def main():
         if path == "stream":
             out["roofline"]["counters"] = pmc_summary("ens_stream_kernel<")
         out["acceptance_fraction"] = float(sampler.acceptance_fraction.mean()) if not shard else None
-        if not args.no_extras:
+        if run_extras:
             extras = {"first_fit_incl_init_s": first_fit_s}
             for rep in range(2):
                 torch.cuda.synchronize(); t1 = time.perf_counter()
@@ -703,7 +751,7 @@ def main():
                     if cpu_e2e is not None:
                         extras["end_to_end"]["cpu_baseline"] = cpu_e2e
             out["extras"] = extras
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and run_cpu:
             out["parity_gate"] = parity_gate(cfg, gp, y_dev, cpu_chain, args)
         if shard_info is not None:
             out["sharded_ensemble"] = shard_info
