@@ -7,6 +7,7 @@ The numerical work lives in ``csrc/libalabi_hip.so`` (hand-written HIP for gfx95
 from . import benchmarks, gp_utils, mcmc_utils, utility  # noqa: F401
 from .core import CachedSurrogateLikelihood, SurrogateModel  # noqa: F401
 from .gp import HipGP  # noqa: F401
+from .nested import NestedResults, NestedSampler, resample_equal  # noqa: F401
 from .sampler import EnsembleSampler  # noqa: F401
 from .utility import *  # noqa: F401,F403
 

@@ -88,6 +88,14 @@ SIGNATURES = {
     "alabi_ens_step_lists": (_i, [_vp, _i, _vp, _pi, _vp]),
     "alabi_ens_step_with_randoms": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _d, _vp, _vp]),
     "alabi_ens_export_draws": (_i, [_vp, _ll, _d, _vp, _pi, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "alabi_ns_create": (_i, [_vp, _i, _pd, _ull, C.POINTER(_vp)]),
+    "alabi_ns_destroy": (_i, [_vp]),
+    "alabi_ns_set_logp": (_i, [_vp, _d, _d, _i]),
+    "alabi_ns_prior_draw": (_i, [_vp, _ll, _i, _i, _vp, _vp, _vp]),
+    "alabi_ns_walk": (_i, [_vp, _ll, _i, _vp, _vp, _i, _d, _vp, _d, _i, _vp, _vp, _vp, _vp]),
+    "alabi_ns_propose": (_i, [_vp, _ll, _i, _vp, _i, _i, _vp, _d, _vp, _vp]),
+    "alabi_ns_accept": (_i, [_vp, _i, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
+    "alabi_ns_last_path": (_i, [_vp, _pi]),
 }
 
 _lib = None

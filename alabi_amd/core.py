@@ -6,10 +6,11 @@ Keeps the public surface of ``alabi.core.SurrogateModel`` that BASELINE.json's n
 ``y()``, ``training_results`` keys, result attributes) -- reference: alabi/core.py:248-251
 (ctor), :542 (init_samples), :736-764 (init_gp), :1097 (_fit_gp), :1163 (_opt_gp), :1446
 (surrogate_log_likelihood), :1535, :1587 (find_next_point), :1670 (active_train), :2073
-(lnprob), :2108 (run_emcee) -- and swaps the two third-party engines behind it:
-george.GP -> ``HipGP`` and emcee.EnsembleSampler -> ``alabi_amd.sampler.EnsembleSampler``.
+(lnprob), :2108 (run_emcee), :2417 (run_dynesty) -- and swaps the third-party engines behind it:
+george.GP -> ``HipGP``, emcee.EnsembleSampler -> ``alabi_amd.sampler.EnsembleSampler`` and
+dynesty's nested samplers -> ``alabi_amd.nested.NestedSampler``.
 
-Out of scope here: nested samplers, plotting, MPI / process pools, the
+Out of scope here: pymultinest / ultranest, plotting, MPI / process pools, the
 parallel-chain trainer.  Deliberate differences are listed in DESIGN.md ("Differences").
 """
 from __future__ import annotations
@@ -64,6 +65,16 @@ def _affine_map(fn, box):
         return mult, add
     except Exception:  # noqa: BLE001
         return None
+
+
+def _uniform_prior_box(prior_transform, ndim):
+    """The box [ndim, 2] of ``partial(ut.prior_transform_uniform, bounds=B)`` (the tutorials' prior transform, which the
+    fused nested-sampling path samples directly), else None (any other callable runs on the host)."""
+    f = getattr(prior_transform, "func", None)
+    kwp = dict(getattr(prior_transform, "keywords", None) or {})
+    if f is ut.prior_transform_uniform and "bounds" in kwp and not getattr(prior_transform, "args", ()):
+        return np.asarray(kwp["bounds"], dtype=np.float64).reshape(ndim, 2)
+    return None
 
 
 class CachedSurrogateLikelihood:
@@ -1153,3 +1164,182 @@ class SurrogateModel(object):
         np.savez(fname, samples=self.emcee_samples)
 
     run_mcmc = run_emcee  # BASELINE.json's name for the same entry point
+
+    # ------------------------------------------------------------------------ nested sampling
+    def run_dynesty(self, like_fn=None, prior_transform=None, mode="dynamic", sampler_kwargs={}, run_kwargs={},
+                    multi_proc=False, save_iter=None, prior_transform_comment=None, samples_file=None, min_ess=int(1e4)):
+        """Nested sampling of the posterior and its evidence log Z on the GPU (core.py:2417-2787); the sampler is
+        alabi_amd.nested.NestedSampler (its docstring states the algorithm) in place of dynesty's.
+
+        * Fused path: the surrogate likelihood (like_fn None / "surrogate" / "gp"), prior_transform None or
+          ``partial(ut.prior_transform_uniform, bounds=...)``, affine theta scaler, affine / nlog / log y scaler: every walk
+          step evaluates the GP mean inside ``ns_walk_kernel``.
+        * Otherwise (like_fn "true" or a callable, any other prior_transform, scalers the kernel cannot fold) the device proposes
+          and accepts, and the host evaluates ``like_fn(prior_transform(u))`` row by row with 1-D arrays of shape (d,), as
+          dynesty calls them (the surrogate under exotic scalers takes the whole batch in one call).
+        sampler_kwargs: ``nlive`` (50 ndim), ``sample`` ("auto" / "rwalk"), ``walks`` (25), ``batch`` (ceil(nlive / 4)),
+        ``seed``; ``bound``, ``pool``, ``queue_size`` and ``multi_proc`` have no effect.  run_kwargs: ``dlogz`` (0.5),
+        ``maxiter`` (5e4), ``maxcall``, and for mode="dynamic" ``dlogz_init`` (0.5), ``nlive_init``, ``nlive_batch``,
+        ``maxbatch`` (10), ``n_effective`` (1e4), ``wt_kwargs`` / ``stop_kwargs`` (pfrac = 1.0 only).  Under
+        ``torch.distributed`` every rank runs its own sampler (seed + rank) and rank 0 writes the files."""
+        from . import dist as adist
+        from .nested import GPUWalkBackend, NestedSampler, PickleCheckpoint
+        rank, world = adist.world_info()
+        # ---- likelihood (core.py:2533-2573)
+        if like_fn is None or (isinstance(like_fn, str) and like_fn.lower() in ("surrogate", "gp", "surrogate_log_likelihood")) \
+                or (callable(like_fn) and like_fn == self.surrogate_log_likelihood):
+            self.like_fn_name, self.like_fn = "surrogate", self.surrogate_log_likelihood
+        elif (isinstance(like_fn, str) and like_fn.lower() in ("true", "true_log_likelihood")) or \
+                (callable(like_fn) and like_fn == self.true_log_likelihood):
+            self.like_fn_name, self.like_fn = "true", self.true_log_likelihood
+        elif callable(like_fn):
+            self.like_fn_name, self.like_fn = "custom", like_fn
+        elif isinstance(like_fn, str):
+            raise ValueError(f"Unknown string identifier for like_fn: '{like_fn}'. "
+                             "Valid options: 'surrogate', 'true', 'gp', 'surrogate_log_likelihood', 'true_log_likelihood'")
+        else:
+            raise TypeError(f"like_fn must be None, a string, or a callable function. Received type: {type(like_fn)}")
+        if self.like_fn_name == "surrogate" and not hasattr(self, "gp"):
+            raise NameError("GP has not been trained")
+        # ---- prior transform (core.py:2575-2598)
+        box = None                                   # the uniform box the fused path can use, in theta
+        if prior_transform is None:
+            self.prior_transform = partial(ut.prior_transform_uniform, bounds=self.bounds)
+            self.prior_transform_comment = ("Default uniform prior transform. \nPrior function: ut.prior_transform_uniform\n"
+                                            f"\twith bounds {self.bounds}")
+            box = np.asarray(self.bounds, dtype=np.float64).reshape(self.ndim, 2)
+        else:
+            self.prior_transform = prior_transform
+            if prior_transform_comment is None:
+                self.prior_transform_comment = "User defined prior transform."
+                try:
+                    self.prior_transform_comment += f"Prior function: {self.prior_transform.__name__}"
+                except Exception:  # noqa: BLE001
+                    self.prior_transform_comment += "Prior function: unrecorded"
+            else:
+                self.prior_transform_comment = prior_transform_comment
+            box = _uniform_prior_box(prior_transform, self.ndim)
+        dynesty_t0 = time.time()
+        # ---- sampler / run settings (core.py:2603-2649)
+        skw = dict(sampler_kwargs)
+        nlive = int(skw.pop("nlive", 50 * self.ndim))
+        sample = skw.pop("sample", "auto")
+        if sample not in ("auto", "rwalk"):
+            raise NotImplementedError(f"sample={sample!r}: only the random walk ('auto' / 'rwalk') is built")
+        walks = int(skw.pop("walks", 25))
+        batch = skw.pop("batch", None)
+        seed = skw.pop("seed", None)
+        for k in ("bound", "pool", "queue_size", "first_update", "update_interval", "bootstrap", "enlarge"):
+            skw.pop(k, None)                         # bounding / process-pool settings: no effect here
+        if skw:
+            raise TypeError(f"run_dynesty: unsupported sampler_kwargs {sorted(skw)}")
+        if mode not in ("dynamic", "static"):
+            raise ValueError(f"mode {mode} is not a valid option. Choose 'dynamic' or 'static'.")
+        rkw = {"wt_kwargs": {"pfrac": 1.0}, "stop_kwargs": {"pfrac": 1.0}, "maxiter": int(5e4), "dlogz_init": 0.5}
+        rkw.update(run_kwargs)
+        rkw.pop("print_progress", None)
+        if mode == "static":                         # dynamic-only settings (the reference hands them to dynesty in both modes)
+            for k in ("wt_kwargs", "stop_kwargs", "dlogz_init", "nlive_init", "nlive_batch", "maxbatch", "n_effective"):
+                rkw.pop(k, None)
+        allowed = {"dlogz", "maxiter", "maxcall", "dlogz_init", "nlive_init", "nlive_batch", "maxbatch", "n_effective",
+                   "wt_kwargs", "stop_kwargs"}
+        if set(rkw) - allowed:
+            raise TypeError(f"run_dynesty: unsupported run_kwargs {sorted(set(rkw) - allowed)}")
+        # ---- which path
+        t_aff = _affine_map(self.theta_scaler.transform, self.bounds) if hasattr(self, "theta_scaler") else \
+            (np.ones(self.ndim), np.zeros(self.ndim))
+        y_kind = self._y_unscale_kind() if hasattr(self, "gp") else None
+        fused = self.like_fn_name == "surrogate" and box is not None and t_aff is not None and y_kind is not None
+        if hasattr(self, "gp") and len(self.training_results["iteration"]) > 0:
+            self.eval_gp_at_iteration(-1)            # makes self.gp carry the latest hyper-parameters / data
+        if hasattr(self, "gp"):
+            gp_obj, y_obj = self.gp, self._y
+        else:                                        # like_fn="true" before any GP exists: the handle needs an owner only
+            gp_obj, y_obj = HipGP(self.ndim), np.zeros(1)
+        pt = self.prior_transform
+        if fused:
+            lo_t, hi_t = box[:, 0], box[:, 1]
+            t_mult, t_add = t_aff
+            bounds_s = np.stack([lo_t * t_mult + t_add, hi_t * t_mult + t_add], axis=1)
+            logp_affine = (y_kind[1], y_kind[2]) if y_kind[0] == "affine" else (1.0, 0.0)
+            logp_map = None if y_kind[0] == "affine" else y_kind[0]
+            host_loglike = None
+            to_theta = lambda u: lo_t + u * (hi_t - lo_t)                     # noqa: E731  (prior_transform_uniform)
+        else:
+            bounds_s = np.tile([0.0, 1.0], (self.ndim, 1))
+            logp_affine, logp_map = (1.0, 0.0), None
+            like = self.like_fn
+
+            def to_theta(u):
+                return np.array([np.asarray(pt(row), dtype=np.float64).reshape(-1) for row in np.atleast_2d(u)])
+
+            if self.like_fn_name == "surrogate":                                # one batched GPU predict
+                def host_loglike(u):
+                    return np.asarray(like(to_theta(u)), dtype=np.float64).reshape(-1)
+            else:
+                def host_loglike(u):
+                    return np.array([float(np.asarray(like(th)).reshape(-1)[0]) for th in to_theta(u)], dtype=np.float64)
+        if self.verbose:
+            print(f"Running nested sampling ({mode}, {'fused GPU walks' if fused else 'host likelihood'}) with {nlive} live "
+                  "points...")
+        all_samples, all_logz, run_number, accumulated = [], [], 1, 0
+        run_seed = self._seed() if seed is None else int(seed)
+        while True:
+            s = run_seed + rank
+            backend = GPUWalkBackend(gp_obj, y_obj, bounds_s, seed=s, to_theta=to_theta, logp_affine=logp_affine,
+                                     logp_map=logp_map, host_loglike=host_loglike)
+            dsampler = NestedSampler(backend, nlive, dynamic=(mode == "dynamic"), walks=walks, batch=batch, seed=s)
+            checkpoint = None
+            if save_iter is not None and rank == 0:
+                pkl = os.path.join(self.savedir, f"dynesty_sampler_{self.like_fn_name}_run{run_number}.pkl")
+                checkpoint = PickleCheckpoint(dsampler, pkl, save_iter)
+            res = dsampler.run_nested(checkpoint=checkpoint, **rkw)
+            if checkpoint is not None:
+                checkpoint.write(res)
+            backend.close()
+            cur = res.samples_equal(np.random.default_rng(s))
+            all_samples.append(cur)
+            all_logz.append(float(res.logz[-1]))
+            accumulated += cur.shape[0]
+            if self.verbose and min_ess > 0:
+                print(f"Run {run_number} complete: {cur.shape[0]} samples, logZ = {res.logz[-1]:.3f}")
+            if accumulated >= min_ess:
+                break
+            run_number += 1
+            if run_number > 10:
+                print(f"WARNING: Reached maximum of 10 runs, stopping with {accumulated} samples")
+                break
+            run_seed = self._seed() if seed is None else int(seed) + 1000003 * (run_number - 1)
+        if len(all_samples) > 1:
+            self.dynesty_samples = np.vstack(all_samples)
+            self.dynesty_logz = max(all_logz)        # the reference keeps the largest log evidence of the runs
+        else:
+            self.dynesty_samples, self.dynesty_logz = all_samples[0], all_logz[0]
+        self.dynesty_sampler = dsampler
+        self.dynesty_results = res
+        self.dynesty_logz_err = float(res.logzerr[-1])
+        self.dynesty_path = backend.path
+        if self.like_fn_name == "true":
+            self.dynesty_samples_true = self.dynesty_samples
+        elif self.like_fn_name == "surrogate":
+            self.dynesty_samples_surrogate = self.dynesty_samples
+        self.dynesty_run = True
+        self.dynesty_runtime = time.time() - dynesty_t0
+        if rank != 0:
+            return                                   # files are rank 0's
+        if self.cache:
+            try:
+                self.save()
+            except Exception:  # noqa: BLE001
+                pass
+        if samples_file is not None:
+            fname = f"{self.savedir}/{samples_file}"
+        elif self.like_fn_name == "true":
+            fname = f"{self.savedir}/dynesty_samples_final_{self.like_fn_name}.npz"
+        else:
+            res_t = getattr(self, "training_results", {"iteration": []})
+            it = res_t["iteration"][-1] if len(res_t["iteration"]) else 0
+            fname = f"{self.savedir}/dynesty_samples_final_{self.like_fn_name}_iter_{it}.npz"
+        if self.verbose:
+            print(f"Saved dynesty samples to {fname}")
+        np.savez(fname, samples=self.dynesty_samples)

@@ -39,6 +39,7 @@ extern "C" {
 
 typedef struct alabi_gp alabi_gp;
 typedef struct alabi_ens alabi_ens;
+typedef struct alabi_ns alabi_ns;
 
 /* Library / device --------------------------------------------------------------------- */
 int alabi_abi_version(void);
@@ -309,6 +310,38 @@ int alabi_ens_step_with_randoms(alabi_ens* ens, double* coords, double* logp,
 int alabi_ens_export_draws(alabi_ens* ens, long long step, double a, int* order, int* n0,
                            double* u_z, int* partner, double* u_acc, int* cw, double* zz,
                            void* stream);
+
+/* Nested sampling (dynesty's NestedSampler / DynamicNestedSampler with sample="rwalk" as driven by
+ * SurrogateModel.run_dynesty, alabi/core.py:2417-2787, likelihood = surrogate_log_likelihood core.py:1446-1508, prior =
+ * ut.prior_transform_uniform core.py:2578-2585).  The host keeps the nested-sampling loop (alabi_amd/nested.py); the
+ * library runs the constrained random walks.  Points live in the unit cube; bounds is a host array [d,2] in the GP's
+ * scaled coordinates, x = lo + u (hi - lo) (hi < lo is allowed: a decreasing affine theta scaler).
+ * logL(u) = map(scale * GP mean(x) + shift) as alabi_ens_set_logp_affine / _map (default 1, 0, identity).
+ * Draws are keyed by (seed, call, global walk id = walk_id0 + b, step) (Philox4x32-10, layout in nested.hip), so a call
+ * split into several launches by walk_id0 gives the same bits.  call, walk_id0 + K < 2^32. */
+int alabi_ns_create(alabi_gp* gp, int d, const double* bounds /* host [d,2], scaled */, unsigned long long seed,
+                    alabi_ns** out);
+int alabi_ns_destroy(alabi_ns* ns);
+int alabi_ns_set_logp(alabi_ns* ns, double scale, double shift, int map_kind /* 0 identity, 1 nlog, 2 log */);
+/* n uniform points u_out [n,d] (dynesty's initial live points) and, if logl_out is not NULL, their logL [n]. */
+int alabi_ns_prior_draw(alabi_ns* ns, long long call, int walk_id0, int n, double* u_out, double* logl_out, void* stream);
+/* K independent walks of `walks` Metropolis steps from u0 [K,d] (logL logl0 [K]; NULL: evaluated first):
+ * u' = u + scale * chol z, z ~ N(0, I_d), chol [d,d] row-major lower triangle; accept iff 0 < u' < 1 and logL(u') > logl_star.
+ * Writes u_out [K,d] (may alias u0), logl_out [K] and, if n_accept is not NULL, int32 [2K]: accepted steps per walk, then
+ * likelihood evaluations (in-cube proposals) per walk.  A walk that accepts nothing returns its start bit for bit. */
+int alabi_ns_walk(alabi_ns* ns, long long call, int walk_id0, const double* u0, const double* logl0, int K, double logl_star,
+                  const double* chol, double scale, int walks, double* u_out, double* logl_out, int* n_accept, void* stream);
+/* The same walk split around a host likelihood (like_fn callables, custom prior_transform, core.py:2533-2601):
+ * alabi_ns_propose writes step `step` of every walk, u_prop [K,d], with the draws and arithmetic of alabi_ns_walk;
+ * the caller evaluates logl_prop [K] (-inf outside the cube); alabi_ns_accept applies the accept test and updates
+ * u_cur / logl_cur in place, ADDING to n_accept [2K] as alabi_ns_walk counts. */
+int alabi_ns_propose(alabi_ns* ns, long long call, int walk_id0, const double* u_cur, int K, int step, const double* chol,
+                     double scale, double* u_prop, void* stream);
+int alabi_ns_accept(alabi_ns* ns, int K, const double* u_prop, const double* logl_prop, double logl_star, double* u_cur,
+                    double* logl_cur, int* n_accept, void* stream);
+/* Path of the last alabi_ns_walk: 1 training set resident in registers, 2 tiled (point pairs beyond the block re-read
+ * from L2 every step). */
+int alabi_ns_last_path(alabi_ns* ns, int* path /* host */);
 
 #ifdef __cplusplus
 }

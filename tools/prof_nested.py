@@ -1,0 +1,131 @@
+"""Nested sampling measurements (DESIGN.md "Nested sampling"): ns_walk_kernel per step at N=2000, d=10 for K = 64 / 256 / 1024
+walks against the ensemble's per-step time, and run_dynesty end to end at the tutorial's settings and at C3 size, with a
+reference-shaped CPU leg (one oracle predict per likelihood call, as dynesty calls the reference's surrogate).
+
+    python tools/prof_nested.py            # everything, one JSON line per measurement
+    python tools/prof_nested.py walk       # only the walk kernel (the part to run under rocprofv3 --kernel-trace --stats)
+"""
+import json
+import math
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from conftest import make_problem  # noqa: E402
+
+
+def emit(**kw):
+    print(json.dumps(kw), flush=True)
+
+
+def walk_kernel():
+    from alabi_amd import EnsembleSampler, HipGP
+    from alabi_amd.nested import GPUWalkBackend
+    N, d, walks = 2000, 10, 25
+    X, y, h = make_problem(N, d, 0)
+    g = HipGP(d, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"])
+    g.compute(X)
+    box = np.array([[-3.0, 3.0]] * d)
+    be = GPUWalkBackend(g, y, box, seed=1, to_theta=lambda u: u)
+    u, l = be.prior(0, 4096)
+    lstar = float(np.quantile(l, 0.5))
+    keep = np.flatnonzero(l > lstar)
+    chol = np.linalg.cholesky(np.cov(u.T))
+    flop_eval = N * (2 * d + 33)          # per GP mean: d fma + ~33 fp64 ops of exp / sign per training point (se_pair_terms)
+    for K in (64, 256, 1024):
+        idx = keep[np.arange(K) % len(keep)]
+        u0 = torch.as_tensor(u[idx], device="cuda")
+        l0 = torch.as_tensor(l[idx], device="cuda")
+        ch = torch.as_tensor(chol, device="cuda")
+        uo, lo = torch.empty_like(u0), torch.empty_like(l0)
+        nacc = torch.zeros(2 * K, dtype=torch.int32, device="cuda")
+        from alabi_amd import _lib
+        lib, ns, st = _lib.lib(), be._ensure(), _lib.current_stream()
+
+        def once(call):
+            _lib.check(lib.alabi_ns_walk(ns, call, 0, _lib.ptr(u0), _lib.ptr(l0), K, lstar, _lib.ptr(ch), 0.5, walks,
+                                         _lib.ptr(uo), _lib.ptr(lo), _lib.ptr(nacc), st), "alabi_ns_walk")
+        for i in range(3):
+            once(i)
+        torch.cuda.synchronize()
+        reps = 20
+        t0 = time.perf_counter()
+        for i in range(reps):
+            once(100 + i)
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / reps
+        evals = float(nacc[K:].sum().item())
+        emit(what="ns_walk", N=N, d=d, K=K, walks=walks, path=be.last_path(), us_per_launch=dt * 1e6,
+             us_per_step=dt * 1e6 / walks, walk_steps_per_s=K * walks / dt, evals_last_launch=evals,
+             gflops_wall=evals * flop_eval / dt / 1e9)
+    # the ensemble at the same GP: time per step and per proposal
+    W, steps = 256, 400
+    s = EnsembleSampler(W, d, g, y, box, seed=3)
+    p0 = np.random.RandomState(0).uniform(-1, 1, (W, d))
+    s.run_mcmc(p0, 50)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    s.run_mcmc(s.get_last_sample().coords, steps)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    emit(what="ensemble_reference_point", N=N, d=d, W=W, us_per_step=dt / steps * 1e6, us_per_half_step=dt / steps / 2 * 1e6,
+         proposals_per_s=W * steps / dt)
+    be.close()
+
+
+def _gauss(d, seed):
+    rng = np.random.RandomState(seed)
+    A = rng.randn(d, d)
+    prec = A @ A.T / d + 0.5 * np.eye(d)
+
+    def like(theta):
+        t = np.atleast_2d(theta)
+        out = -0.5 * np.einsum("ni,ij,nj->n", t, prec, t)
+        return out if np.ndim(theta) == 2 else float(out[0])
+    return like
+
+
+def end_to_end(name, d, ntrain, nlive, mode, bounds):
+    import tempfile
+
+    from alabi_amd import SurrogateModel
+    from oracle.gp_oracle import OracleGP
+    sm = SurrogateModel(lnlike_fn=_gauss(d, 0), bounds=[bounds] * d, savedir=tempfile.mkdtemp(), verbose=False,
+                        random_state=0, cache=False)
+    sm.init_samples(ntrain=ntrain)
+    sm.init_gp(hyperopt_method="ml", gp_nopt=1)
+    sm.run_dynesty(mode=mode, sampler_kwargs={"nlive": nlive, "seed": 1}, min_ess=0)     # warm-up (library load, first calls)
+    t0 = time.perf_counter()
+    sm.run_dynesty(mode=mode, sampler_kwargs={"nlive": nlive, "seed": 2}, min_ess=0)
+    wall = time.perf_counter() - t0
+    r = sm.dynesty_results
+    emit(what="run_dynesty", config=name, d=d, N=ntrain, nlive=nlive, mode=mode, wall_s=wall, niter=int(r.niter),
+         nsamples=int(len(r.logl)), ncall=int(r.ncall), evals_per_s=r.ncall / wall, iters_per_s=r.niter / wall,
+         logz=float(r.logz[-1]), logzerr=float(r.logzerr[-1]), status=r.status, n_stuck=int(r.n_stuck))
+    # reference-shaped CPU leg: dynesty hands the reference's surrogate_log_likelihood ONE point per call
+    hp = sm.gp.get_parameter_vector(include_frozen=True)
+    o = OracleGP(d, hp[0], hp[1], hp[2], hp[3:]).compute(sm._theta)
+    pts = np.random.RandomState(1).uniform(bounds[0], bounds[1], (400, d))
+    t0 = time.perf_counter()
+    for p in pts:
+        o.predict(sm._y, p.reshape(1, -1))
+    per = (time.perf_counter() - t0) / len(pts)
+    emit(what="cpu_reference_shaped", config=name, N=ntrain, d=d, s_per_eval=per, evals_per_s=1.0 / per,
+         est_wall_s_for_same_ncall=per * r.ncall)
+
+
+if __name__ == "__main__":
+    what = sys.argv[1] if len(sys.argv) > 1 else "all"
+    torch.cuda.set_device(0)
+    if what in ("all", "walk"):
+        walk_kernel()
+    if what in ("all", "e2e"):
+        end_to_end("tutorial", 2, 200, 100, "dynamic", (-4.0, 4.0))
+        end_to_end("C3", 10, 2000, 500, "static", (-2.0, 2.0))
