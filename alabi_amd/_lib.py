@@ -96,6 +96,12 @@ SIGNATURES = {
     "alabi_ns_propose": (_i, [_vp, _ll, _i, _vp, _i, _i, _vp, _d, _vp, _vp]),
     "alabi_ns_accept": (_i, [_vp, _i, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
     "alabi_ns_last_path": (_i, [_vp, _pi]),
+    "alabi_kde_create": (_i, [_i, C.POINTER(_vp)]),
+    "alabi_kde_destroy": (_i, [_vp]),
+    "alabi_kde_set_data": (_i, [_vp, _vp, _vp, _ll, _pd, _vp]),
+    "alabi_kde_logpdf": (_i, [_vp, _vp, _ll, _vp, _vp]),
+    "alabi_kde_pdf": (_i, [_vp, _vp, _ll, _vp, _vp]),
+    "alabi_kde_plan": (_i, [_vp, _ll, _pi, _pi]),
 }
 
 _lib = None

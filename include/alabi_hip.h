@@ -40,6 +40,7 @@ extern "C" {
 typedef struct alabi_gp alabi_gp;
 typedef struct alabi_ens alabi_ens;
 typedef struct alabi_ns alabi_ns;
+typedef struct alabi_kde alabi_kde;
 
 /* Library / device --------------------------------------------------------------------- */
 int alabi_abi_version(void);
@@ -342,6 +343,25 @@ int alabi_ns_accept(alabi_ns* ns, int K, const double* u_prop, const double* log
 /* Path of the last alabi_ns_walk: 1 training set resident in registers, 2 tiled (point pairs beyond the block re-read
  * from L2 every step). */
 int alabi_ns_last_path(alabi_ns* ns, int* path /* host */);
+
+/* Gaussian kernel density estimate: scipy.stats.gaussian_kde(dataset, bw_method, weights) as built and evaluated by the
+ * reference's metrics, kl_divergence_kde (alabi/metrics.py:210-336: gaussian_kde(...) at :292-296, kde.pdf at :314-315).
+ * The host computes the bandwidth (scipy's _compute_covariance; alabi_amd/kde.py); the library holds the whitened samples.
+ * p(q) = det(2 pi S)^(-1/2) sum_i w_i exp(-|L^-1 (q - x_i)|^2 / 2), S = L L^T.  Results do not depend on the device:
+ * the split of the sample axis is a function of (N, M, d) only, and repeated calls are bit-identical. */
+int alabi_kde_create(int d, alabi_kde** out);
+int alabi_kde_destroy(alabi_kde* kde);
+/* Prepares the samples X [N,d] (row-major) once: centring, whitening by L, augmented rows.  logw [N] holds log w_i of
+ * weights normalised to sum 1 (-inf for a zero weight); NULL = uniform 1/N.  cho_cov: host [d,d] row-major, lower
+ * triangle read (scipy's kde.cho_cov).  Synchronises `stream`. */
+int alabi_kde_set_data(alabi_kde* kde, const double* X, const double* logw, long long N, const double* cho_cov,
+                       void* stream);
+/* kde.logpdf(Q.T) -- scipy.stats.gaussian_kde.logpdf: out [M] = log p(Q [M,d]); finite where p underflows. */
+int alabi_kde_logpdf(alabi_kde* kde, const double* Q, long long M, double* out, void* stream);
+/* kde.pdf(Q.T) / kde.evaluate -- alabi/metrics.py:314-315: out [M] = p(Q [M,d]) (0 where it underflows, as scipy's). */
+int alabi_kde_pdf(alabi_kde* kde, const double* Q, long long M, double* out, void* stream);
+/* The split of the sample axis a call with M queries uses: `parts` ranges of `pts` samples (host ints). */
+int alabi_kde_plan(alabi_kde* kde, long long M, int* parts, int* pts);
 
 #ifdef __cplusplus
 }
