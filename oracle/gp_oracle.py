@@ -20,17 +20,16 @@ from __future__ import annotations
 import numpy as np
 from scipy.linalg import cho_solve, cholesky, solve_triangular
 
-__all__ = ["sqexp_kernel", "stationary_kernel", "OracleGP", "NotPositiveDefinite"]
+__all__ = ["sqexp_kernel", "stationary_kernel", "scaled_sq_dist", "radial_and_derivatives", "OracleGP",
+           "NotPositiveDefinite"]
 
 
 class NotPositiveDefinite(np.linalg.LinAlgError):
     pass
 
 
-def stationary_kernel(x1, x2, log_amp, log_M, kernel="ExpSquaredKernel", log_alpha=1.0):
-    """amp * f(r2) for the four kernels init_gp offers (alabi/core.py:1000-1014), george definitions:
-    ExpSquared exp(-r2/2); Matern32 (1+s)exp(-s), s=sqrt(3 r2); Matern52 (1+s+s^2/3)exp(-s), s=sqrt(5 r2);
-    RationalQuadratic (1 + r2/(2 alpha))^-alpha."""
+def scaled_sq_dist(x1, x2, log_M):
+    """r2[i, j] = sum_k (x1_ik - x2_jk)^2 / exp(log_M_k)."""
     x1 = np.atleast_2d(np.asarray(x1, dtype=np.float64))
     x2 = np.atleast_2d(np.asarray(x2, dtype=np.float64))
     inv_m = np.exp(-np.asarray(log_M, dtype=np.float64))
@@ -38,16 +37,38 @@ def stationary_kernel(x1, x2, log_amp, log_M, kernel="ExpSquaredKernel", log_alp
     for k in range(x1.shape[1]):
         diff = x1[:, k][:, None] - x2[:, k][None, :]
         r2 += diff * diff * inv_m[k]
+    return r2
+
+
+def radial_and_derivatives(r2, kernel="ExpSquaredKernel", log_alpha=1.0):
+    """(f, df/d r2, df/d log_alpha) of the radial profile k = amp f(r2) of the four kernels init_gp offers
+    (alabi/core.py:1000-1014), george definitions:
+      ExpSquared         f = exp(-r2/2)                            f' = -f/2
+      Matern32           f = (1+s) exp(-s),       s = sqrt(3 r2)   f' = -(3/2) exp(-s)
+      Matern52           f = (1+s+s^2/3) exp(-s), s = sqrt(5 r2)   f' = -(5/6) (1+s) exp(-s)
+      RationalQuadratic  f = (1+u)^-alpha,        u = r2/(2 alpha) f' = -f / (2 (1+u)),
+                         df/d log_alpha = alpha f (u/(1+u) - log1p(u))
+    The last entry is None for the three families without alpha.  The Matern slopes are finite at r2 = 0."""
+    r2 = np.asarray(r2, dtype=np.float64)
     if kernel == "ExpSquaredKernel":
         f = np.exp(-0.5 * r2)
-    elif kernel == "Matern32Kernel":
-        s = np.sqrt(3.0 * r2); f = (1.0 + s) * np.exp(-s)
-    elif kernel == "Matern52Kernel":
-        s = np.sqrt(5.0 * r2); f = (1.0 + s + s * s / 3.0) * np.exp(-s)
-    elif kernel == "RationalQuadraticKernel":
-        a = np.exp(log_alpha); f = (1.0 + 0.5 * r2 / a) ** (-a)
-    else:
-        raise ValueError(kernel)
+        return f, -0.5 * f, None
+    if kernel == "Matern32Kernel":
+        s = np.sqrt(3.0 * r2); e = np.exp(-s)
+        return (1.0 + s) * e, -1.5 * e, None
+    if kernel == "Matern52Kernel":
+        s = np.sqrt(5.0 * r2); e = np.exp(-s)
+        return (1.0 + s + s * s / 3.0) * e, -(5.0 / 6.0) * (1.0 + s) * e, None
+    if kernel == "RationalQuadraticKernel":
+        a = np.exp(log_alpha); u = 0.5 * r2 / a
+        f = (1.0 + u) ** (-a)
+        return f, -0.5 * f / (1.0 + u), a * f * (u / (1.0 + u) - np.log1p(u))
+    raise ValueError(kernel)
+
+
+def stationary_kernel(x1, x2, log_amp, log_M, kernel="ExpSquaredKernel", log_alpha=1.0):
+    """amp * f(r2) for the four kernels init_gp offers (f: radial_and_derivatives)."""
+    f, _, _ = radial_and_derivatives(scaled_sq_dist(x1, x2, log_M), kernel, log_alpha)
     return np.exp(log_amp) * f
 
 
@@ -57,14 +78,7 @@ def sqexp_kernel(x1, x2, log_amp, log_M):
     Restates ``ConstantKernel * ExpSquaredKernel(metric=diag)`` as built by the
     reference at alabi/core.py:1000 and alabi/gp_utils.py:230-231 (``kernel *= var(y)``).
     """
-    x1 = np.atleast_2d(np.asarray(x1, dtype=np.float64))
-    x2 = np.atleast_2d(np.asarray(x2, dtype=np.float64))
-    inv_m = np.exp(-np.asarray(log_M, dtype=np.float64))
-    r2 = np.zeros((x1.shape[0], x2.shape[0]))
-    for k in range(x1.shape[1]):
-        diff = x1[:, k][:, None] - x2[:, k][None, :]
-        r2 += diff * diff * inv_m[k]
-    return np.exp(log_amp) * np.exp(-0.5 * r2)
+    return stationary_kernel(x1, x2, log_amp, log_M)
 
 
 class OracleGP:
@@ -202,26 +216,33 @@ class OracleGP:
         return ll if np.isfinite(ll) else -np.inf
 
     def grad_log_likelihood(self, y, quiet=True):
-        """d logL / d p over the unfrozen vector (core.py:1261, gp_utils.py:165).
+        """d logL / d p over the unfrozen vector, in get_parameter_names() order (core.py:1261, gp_utils.py:165).
 
-        A = alpha alpha^T - K^-1 ; dL/dp = 0.5 tr(A dK/dp) ; dL/dmean = sum(alpha).
+        A = alpha alpha^T - K^-1 ; dL/dp = 0.5 tr(A dK/dp) ; dL/dmean = sum(alpha), with K = amp f(r2) + wn I and
+        f, f' = df/dr2 from radial_and_derivatives:
+          dK/d log_wn = wn I ;  dK/d log_amp = amp f ;  dK/d log_M_k = amp f' (-D_k^2 / M_k) ;
+          dK/d log_alpha = amp df/d log_alpha  (rational quadratic only).
         """
         y = np.asarray(y, dtype=np.float64).ravel()
         alpha = self._compute_alpha(y)
         n = len(y)
         Kinv = cho_solve((self._L, True), np.eye(n), check_finite=False)
         A = np.outer(alpha, alpha) - Kinv
-        Kk = sqexp_kernel(self._x, self._x, self.log_amp, self.log_M)
+        amp = np.exp(self.log_amp)
+        f, fp, fa = radial_and_derivatives(scaled_sq_dist(self._x, self._x, self.log_M), self.kernel_name, self.log_alpha)
         g = []
         if self.fit_mean:
             g.append(float(np.sum(alpha)))
         if self.fit_white_noise:
             g.append(0.5 * float(np.trace(A)) * np.exp(self.log_white_noise))
-        g.append(0.5 * float(np.sum(A * Kk)))
+        g.append(0.5 * float(np.sum(A * (amp * f))))
+        if self.kernel_name == "RationalQuadraticKernel":
+            g.append(0.5 * float(np.sum(A * (amp * fa))))
+        slope = -(amp * fp)                     # squared exponential: K / 2
         inv_m = np.exp(-self.log_M)
         for k in range(self.ndim):
             diff = self._x[:, k][:, None] - self._x[:, k][None, :]
-            g.append(0.5 * float(np.sum(A * Kk * (0.5 * diff * diff * inv_m[k]))))
+            g.append(0.5 * float(np.sum(A * slope * (diff * diff * inv_m[k]))))
         return np.array(g)
 
     def get_inverse(self):

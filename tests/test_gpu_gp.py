@@ -247,8 +247,8 @@ def test_full_size_configs_properties(torch_gpu):
 
 
 def test_grad_log_likelihood_analytic():
-    """alabi_gp_grad_log_likelihood vs the oracle's analytic gradient (sq-exp) and vs central differences of the device
-    likelihood (all four kernels); N not a multiple of 64 so the padded rows are exercised."""
+    """alabi_gp_grad_log_likelihood vs the oracle's closed-form gradient (all four kernels) and vs central differences of the
+    device likelihood; N not a multiple of 64 so the padded rows are exercised."""
     from alabi_amd import HipGP
     from oracle.gp_oracle import OracleGP
     X, y, h = make_problem(333, 5, 21, log_wn=-6.0)
@@ -263,10 +263,100 @@ def test_grad_log_likelihood_analytic():
         an, fd = gk.grad_log_likelihood(y), gk.grad_log_likelihood_fd(y, h=1e-5)
         assert an.shape == fd.shape
         np.testing.assert_allclose(an, fd, rtol=2e-5, atol=2e-5 * np.max(np.abs(fd)))
+        ko = OracleGP(5, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"], kernel=kernel, log_alpha=0.3).compute(X)
+        gko = ko.grad_log_likelihood(y)
+        assert an.shape == gko.shape
+        np.testing.assert_allclose(an, gko, rtol=1e-8, atol=1e-8 * np.max(np.abs(gko)))
     # frozen parameters drop out of the vector (george protocol)
     gf = HipGP(5, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"], fit_mean=False, fit_white_noise=False)
     gf.compute(X)
     np.testing.assert_allclose(gf.grad_log_likelihood(y), ga[2:], rtol=1e-12)
+
+
+# the four kernel families init_gp offers; the rational quadratic at three shape parameters log alpha
+GRAD_FAMILIES = [("ExpSquaredKernel", 1.0), ("Matern32Kernel", 1.0), ("Matern52Kernel", 1.0),
+                 ("RationalQuadraticKernel", -1.2), ("RationalQuadraticKernel", 0.4), ("RationalQuadraticKernel", 2.5)]
+
+
+def _grad_pair(X, h, kernel, log_alpha, **kw):
+    from alabi_amd import HipGP
+    from oracle.gp_oracle import OracleGP
+    d = X.shape[1]
+    g = HipGP(d, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"], kernel=kernel, log_alpha=log_alpha, **kw)
+    g.compute(X)
+    o = OracleGP(d, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"], kernel=kernel, log_alpha=log_alpha).compute(X)
+    return g, o
+
+
+def _assert_grad_matches(ga, go):
+    assert ga.shape == go.shape
+    np.testing.assert_allclose(ga, go, rtol=1e-8, atol=1e-8 * np.max(np.abs(go)))
+
+
+@pytest.mark.parametrize("N,d", [(2, 1), (63, 7), (65, 17), (129, 33), (700, 10), (200, 64)])
+@pytest.mark.parametrize("kernel,log_alpha", GRAD_FAMILIES)
+def test_grad_log_likelihood_closed_form_all_families(torch_gpu, kernel, log_alpha, N, d):
+    """grad_contract_kernel + grad_final_kernel against the oracle's closed form for every kernel family: N on both sides of
+    the 64-row tiles, d on full dimension buckets (1, 10, 64) and padded ones (7 -> 8, 17 -> 20, 33 -> 48)."""
+    X, y, h = make_problem(N, d, 7 + N + d, log_wn=-6.0, ell2=4.0 * d)
+    g, o = _grad_pair(X, h, kernel, log_alpha)
+    assert g.get_parameter_names() == o.get_parameter_names()
+    _assert_grad_matches(g.grad_log_likelihood(y), o.grad_log_likelihood(y))
+    assert abs(g.log_likelihood(y) - o.log_likelihood(y)) <= 1e-9 * abs(o.log_likelihood(y))
+
+
+@pytest.mark.parametrize("kernel,log_alpha", [("Matern52Kernel", 1.0), ("RationalQuadraticKernel", 0.4)])
+def test_grad_log_likelihood_state_on_one_handle(torch_gpu, kernel, log_alpha):
+    """The gradient follows the state of its handle, each time against the oracle at the same state: new hyper-parameters
+    (the cached L^-1 is keyed on the factor), a training set grown one row at a time through compute_from (the handle moves
+    from object to object, appends stop at multiples of 64), repeated calls and a prior variance prediction (same bits), and
+    frozen mean / white noise / amplitude (each drops exactly its own entry; the rational quadratic's log_alpha keeps its slot)."""
+    from alabi_amd import HipGP
+    from oracle.gp_oracle import OracleGP
+    d, n0 = 5, 150
+    X, y, h = make_problem(200, d, 77, log_wn=-6.0, ell2=4.0 * d)
+    g, o = _grad_pair(X[:n0], h, kernel, log_alpha)
+    g1 = g.grad_log_likelihood(y[:n0])
+    _assert_grad_matches(g1, o.grad_log_likelihood(y[:n0]))
+    assert np.array_equal(g.grad_log_likelihood(y[:n0]), g1)
+    p = g.get_parameter_vector()
+    p[2:] += 0.2 * np.random.RandomState(3).uniform(-1.0, 1.0, p.size - 2)          # amplitude, (log alpha), length scales
+    g.set_parameter_vector(p); g.recompute()
+    o.set_parameter_vector(p); o.recompute()
+    g2 = g.grad_log_likelihood(y[:n0])
+    _assert_grad_matches(g2, o.grad_log_likelihood(y[:n0]))
+    assert np.max(np.abs(g2 - g1)) > 1e-3 * np.max(np.abs(g1))
+    # a fresh handle at the same state, with the L^-1 cache built first by a variance prediction: the same bits
+    gb = HipGP(d, kernel=kernel, log_alpha=log_alpha); gb.set_parameter_vector(p); gb.compute(X[:n0])
+    Xs = np.random.RandomState(4).uniform(-3, 3, (7, d))
+    gb.predict(y[:n0], Xs, return_var=True); gb.predict_grad_device(y[:n0], Xs)
+    assert np.array_equal(gb.grad_log_likelihood(y[:n0]), g2)
+    # growth one row at a time: appends up to 128 and 192 rows, refits at 129 and 193
+    kw = dict(kernel=kernel, log_alpha=log_alpha)
+    prev = HipGP(d, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"], **kw); prev.compute(X[:120])
+    appended = 0
+    for n in range(121, 200):
+        cur = HipGP(d, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"], **kw)
+        cur.compute_from(prev, X[:n])
+        appended = max(appended, getattr(cur, "appended", 0))
+        prev = cur
+        if n in (127, 128, 129, 150, 191, 192, 193):
+            on = OracleGP(d, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"], **kw).compute(X[:n])
+            _assert_grad_matches(cur.grad_log_likelihood(y[:n]), on.grad_log_likelihood(y[:n]))
+    assert appended >= 60
+    # frozen entries: the oracle's full vector without that entry (fit_amp=False fixes log_constant at 0)
+    for frozen, name in (("fit_mean", "mean:value"), ("fit_white_noise", "white_noise:value"), ("fit_amp", "kernel:k1:log_constant")):
+        hf = dict(h, log_amp=0.0) if frozen == "fit_amp" else h
+        gf, of = _grad_pair(X[:n0], hf, kernel, log_alpha, **{frozen: False})
+        names = list(of.get_parameter_names())
+        keep = [i for i, nm in enumerate(names) if nm != name]
+        full = of.grad_log_likelihood(y[:n0])
+        gg = gf.grad_log_likelihood(y[:n0])
+        assert len(gg) == len(gf.get_parameter_vector()) == len(names) - 1
+        _assert_grad_matches(gg, full[keep])
+        if kernel == "RationalQuadraticKernel":
+            slot = [i for i, nm in enumerate(gf.get_parameter_names()) if nm.endswith("log_alpha")]
+            assert slot == [keep.index(names.index("kernel:k2:log_alpha"))]
 
 
 @pytest.mark.parametrize("w_path", ["1", "0"])
@@ -408,17 +498,26 @@ def test_append_point_matches_full_factorisation():
     assert np.all(np.isfinite(mu))
 
 
+# (N, d, M) at which every kernel family runs: d on full and padded dimension buckets up to 64, M across the 16-query groups
+PGRAD_SHAPES = [(40, 1, 17), (63, 7, 16), (129, 17, 33), (300, 33, 5), (130, 64, 3), (2000, 10, 20)]
+
+
 @pytest.mark.parametrize("N,d,M,kernel", [(40, 3, 24, "ExpSquaredKernel"), (500, 5, 7, "ExpSquaredKernel"),
                                           (2000, 10, 33, "ExpSquaredKernel"), (300, 4, 16, "Matern52Kernel"),
-                                          (300, 4, 5, "RationalQuadraticKernel"), (130, 20, 3, "ExpSquaredKernel")])
+                                          (300, 4, 5, "RationalQuadraticKernel"), (130, 20, 3, "ExpSquaredKernel")]
+                         + [(N, d, M, k) for N, d, M in PGRAD_SHAPES for k in ("ExpSquaredKernel", "Matern32Kernel",
+                                                                            "Matern52Kernel", "RationalQuadraticKernel")])
 def test_predict_grad_against_oracle(torch_gpu, N, d, M, kernel):
     """alabi_gp_predict_grad (closed-form d mu/dx, d var/dx through the cached L^-1) against the oracle: the closed form
-    for the squared exponential (1e-9 of the gradient scale) and the reference-shaped finite differences
-    (utility.py:511-623, step 1e-6) for every kernel family (1e-5)."""
+    for every kernel family (1e-9 of the gradient scale) and the reference-shaped finite differences (utility.py:511-623,
+    step 1e-6; 1e-5).  Besides the M random queries, a second batch sits exactly on training points (r2 = 0) and 30 to 60
+    length scales away from the data.  The PGRAD_SHAPES cases use squared length scales that grow with d (the default ones
+    leave r2 ~ 3 d between random points, where the kernel vanishes in 33 or 64 dimensions) and a nugget that keeps cond(K)
+    below ~1e6."""
     from alabi_amd import HipGP
     from oracle.gp_oracle import OracleGP
     from oracle import utility_oracle as uo
-    X, y, h = make_problem(N, d, 11 + d)
+    X, y, h = make_problem(N, d, 11 + d, **(dict(log_wn=-6.0, ell2=4.0 * d) if (N, d, M) in PGRAD_SHAPES else {}))
     g = HipGP(d, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"], kernel=kernel)
     g.compute(X)
     o = OracleGP(d, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"], kernel=kernel).compute(X)
@@ -436,10 +535,19 @@ def test_predict_grad_against_oracle(torch_gpu, N, d, M, kernel):
     fd_var = np.array([uo.grad_gp_var_prediction(t, o) for t in Xs[:nq]])
     assert np.max(np.abs(dmu[:nq] - fd_mu)) <= 1e-5 * np.max(np.abs(fd_mu))
     assert np.max(np.abs(dvar[:nq] - fd_var)) <= 1e-5 * np.max(np.abs(fd_var)) + 1e-7 * amp
-    if kernel == "ExpSquaredKernel":
-        _, _, dmu_o, dvar_o = uo.analytic_predict_grad(o, y, Xs)
-        assert np.max(np.abs(dmu - dmu_o)) <= 1e-9 * np.max(np.abs(dmu_o))
-        assert np.max(np.abs(dvar - dvar_o)) <= 1e-9 * np.max(np.abs(dvar_o)) + 1e-9 * amp
+    far = X[:3].copy()
+    for j in range(3):
+        c = j % d
+        far[j, c] = X[:, c].max() + (30.0 + 15.0 * j) * np.exp(0.5 * h["log_M"][c])
+    Xe = np.vstack([X[[0, N // 2, N - 1]], far])
+    mu_e, var_e, dmu_e, dvar_e = [t.cpu().numpy() for t in g.predict_grad_device(y, Xe)]
+    mu_eo, var_eo = o.predict(y, Xe, return_var=True)
+    assert np.max(np.abs(mu_e - mu_eo) / (np.abs(mu_eo) + 1)) <= 1e-8
+    assert np.max(np.abs(var_e - var_eo)) <= 1e-6 * amp
+    _, _, dmu_o, dvar_o = uo.analytic_predict_grad(o, y, np.vstack([Xs, Xe]))
+    dmu, dvar = np.vstack([dmu, dmu_e]), np.vstack([dvar, dvar_e])
+    assert np.max(np.abs(dmu - dmu_o)) <= 1e-9 * np.max(np.abs(dmu_o))
+    assert np.max(np.abs(dvar - dvar_o)) <= 1e-9 * np.max(np.abs(dvar_o)) + 1e-9 * amp
 
 
 def test_grad_utilities_against_reference_vectors(torch_gpu, golden_grad):
@@ -626,13 +734,14 @@ def test_predict_mean_matrix_core_path(torch_gpu, monkeypatch, d, N, kernel, M):
 
 def test_predict_grad_point_host_buffers(torch_gpu):
     """alabi_gp_predict_grad_point (one point, host buffers on both sides: what the polish step of find_next_point calls per
-    evaluation, alabi/utility.py:1030-1163) returns exactly what the batched device entry returns for that point; several points
-    take the device route."""
+    evaluation, alabi/utility.py:1030-1163) returns exactly what the batched device entry returns for that point, for every
+    kernel family; several points take the device route."""
     import torch
     from alabi_amd import HipGP
-    for N, d in ((90, 2), (700, 5), (2000, 10)):
+    for (N, d), kernel in [(nd, k) for nd in ((90, 2), (700, 5), (2000, 10))
+                           for k in ("ExpSquaredKernel", "Matern32Kernel", "Matern52Kernel", "RationalQuadraticKernel")]:
         X, y, h = make_problem(N, d, 300 + N)
-        g = HipGP(d, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"]); g.compute(X)
+        g = HipGP(d, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"], kernel=kernel, log_alpha=0.4); g.compute(X)
         rng = np.random.RandomState(N)
         pts = rng.uniform(-1.0, 1.0, (5, d))
         ref = [t.cpu().numpy() for t in g.predict_grad_device(y, pts)]

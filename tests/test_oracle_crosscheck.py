@@ -7,8 +7,13 @@ from scipy.linalg import cho_factor, cho_solve
 
 from oracle.gp_oracle import NotPositiveDefinite, OracleGP, sqexp_kernel
 from oracle import stretch_oracle as so
+from oracle import utility_oracle as uo
 from oracle.autocorr_oracle import integrated_time as oracle_tau
 from conftest import make_problem
+
+# the four kernel families init_gp offers; the rational quadratic at three shape parameters log alpha
+FAMILIES = [("ExpSquaredKernel", 1.0), ("Matern32Kernel", 1.0), ("Matern52Kernel", 1.0),
+            ("RationalQuadraticKernel", -1.2), ("RationalQuadraticKernel", 0.4), ("RationalQuadraticKernel", 2.5)]
 
 
 def _gp(X, y, h):
@@ -32,6 +37,49 @@ def test_gp_against_sklearn():
     np.testing.assert_allclose(var, sd_sk ** 2 - np.exp(h["log_white_noise"]), rtol=1e-6, atol=1e-8)
     # marginal likelihood
     assert abs(gp.log_likelihood(y) - sk.log_marginal_likelihood_value_) < 1e-7 * abs(gp.log_likelihood(y))
+
+
+@pytest.mark.parametrize("kernel,log_alpha", FAMILIES)
+def test_gp_gradient_against_sklearn(kernel, log_alpha):
+    """The oracle's closed-form d logL / dp against scikit-learn's log_marginal_likelihood(theta, eval_gradient=True) on
+    ConstantKernel * K + WhiteKernel (K = RBF, Matern nu = 3/2 and 5/2 with anisotropic length_scale = sqrt(M), or the
+    isotropic RationalQuadratic).  sklearn's theta is log(constant, length_scale, alpha, noise_level): log_amp, log_M / 2,
+    log_alpha, log_wn.  Both sides evaluate the same fp64 algebra; the hyper-parameters sit inside sklearn's default bounds."""
+    from sklearn.gaussian_process import GaussianProcessRegressor
+    from sklearn.gaussian_process.kernels import RBF, ConstantKernel, Matern, RationalQuadratic, WhiteKernel
+    d = 3
+    X, y, h = make_problem(100, d, 4, log_wn=-6.0)
+    rq = kernel == "RationalQuadraticKernel"
+    log_M = np.full(d, np.mean(h["log_M"])) if rq else h["log_M"]
+    ell = np.sqrt(np.exp(log_M))
+    if kernel == "ExpSquaredKernel":
+        k = RBF(length_scale=ell)
+    elif rq:
+        k = RationalQuadratic(length_scale=float(ell[0]), alpha=float(np.exp(log_alpha)))
+    else:
+        k = Matern(length_scale=ell, nu=1.5 if kernel == "Matern32Kernel" else 2.5)
+    k = ConstantKernel(np.exp(h["log_amp"])) * k + WhiteKernel(np.exp(h["log_white_noise"]))
+    sk = GaussianProcessRegressor(kernel=k, optimizer=None, alpha=0.0).fit(X, y - h["mean"])
+    ll_sk, g_sk = sk.log_marginal_likelihood(sk.kernel_.theta, eval_gradient=True)
+    at, i = {}, 0
+    for hp in sk.kernel_.hyperparameters:
+        at[hp.name] = g_sk[i:i + hp.n_elements]; i += hp.n_elements
+    o = OracleGP(d, h["mean"], h["log_white_noise"], h["log_amp"], log_M, kernel=kernel, log_alpha=log_alpha).compute(X)
+    g = o.grad_log_likelihood(y)
+    names = o.get_parameter_names()
+    assert g.shape == (len(names),) == o.get_parameter_vector().shape
+    ex = {"mean:value": np.sum(sk.alpha_), "white_noise:value": at["k2__noise_level"][0],
+          "kernel:k1:log_constant": at["k1__k1__constant_value"][0]}
+    lm = [names.index(f"kernel:k2:metric:log_M_{c}_{c}") for c in range(d)]
+    if rq:
+        ex["kernel:k2:log_alpha"] = at["k1__k2__alpha"][0]
+        mine = np.array([g[names.index(n)] for n in ex] + [np.sum(g[lm])])       # one isotropic length scale
+        ref = np.array(list(ex.values()) + [0.5 * at["k1__k2__length_scale"][0]])
+    else:
+        mine = np.array([g[names.index(n)] for n in ex] + list(g[lm]))
+        ref = np.array(list(ex.values()) + list(0.5 * at["k1__k2__length_scale"]))
+    assert np.max(np.abs(mine - ref)) <= 1e-9 * np.max(np.abs(ref)), (mine, ref)
+    assert abs(o.log_likelihood(y) - ll_sk) <= 1e-9 * abs(ll_sk)
 
 
 def test_gp_against_scipy_and_known_answers():
@@ -72,16 +120,41 @@ def test_gp_closed_form_two_points():
     assert abs(mu[0] - mu_ref) < 1e-13 and abs(var[0] - var_ref) < 1e-13
 
 
-def test_gp_gradient_matches_finite_differences():
+@pytest.mark.parametrize("fit_mean,fit_white_noise", [(True, True), (False, True), (True, False), (False, False)])
+@pytest.mark.parametrize("kernel,log_alpha", FAMILIES)
+def test_gp_gradient_matches_finite_differences(kernel, log_alpha, fit_mean, fit_white_noise):
     X, y, h = make_problem(60, 2, 5, log_wn=-6.0)
-    gp = _gp(X, y, h)
+    gp = OracleGP(2, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"], fit_mean=fit_mean,
+                  fit_white_noise=fit_white_noise, kernel=kernel, log_alpha=log_alpha).compute(X)
     p0 = gp.get_parameter_vector()
     g = gp.grad_log_likelihood(y)
+    assert g.shape == p0.shape == (len(gp.get_parameter_names()),)
     for i in range(len(p0)):
         e = np.zeros_like(p0); e[i] = 1e-6
         gp.set_parameter_vector(p0 + e); gp.recompute(); fp = gp.log_likelihood(y)
         gp.set_parameter_vector(p0 - e); gp.recompute(); fm = gp.log_likelihood(y)
         assert abs((fp - fm) / 2e-6 - g[i]) < 1e-4 * max(1.0, abs(g[i]))
+
+
+@pytest.mark.parametrize("kernel,log_alpha", FAMILIES)
+def test_analytic_predict_grad_matches_reference_finite_differences(kernel, log_alpha):
+    """analytic_predict_grad (closed-form d mu/dx, d var/dx: what the HIP path evaluates) against the reference's finite
+    differences (utility.py:511-623, step 1e-6), to the accuracy of the differencing as in test_oracle_golden.py: random
+    queries, queries exactly on training points (r2 = 0, where the Matern kernels have the kink of sqrt) and queries 30
+    length scales away from the data."""
+    d = 3
+    X, y, h = make_problem(80, d, 7, log_wn=-8.0)
+    o = OracleGP(d, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"], kernel=kernel, log_alpha=log_alpha).compute(X)
+    far = X[:d].copy()
+    for c in range(d):
+        far[c, c] = X[:, c].max() + 30.0 * np.exp(0.5 * h["log_M"][c])
+    Xs = np.vstack([np.random.RandomState(2).uniform(-3, 3, (6, d)), X[[0, 17, 41]], far])
+    _, _, dmu, dvar = uo.analytic_predict_grad(o, y, Xs)
+    fd_mu = np.array([uo.grad_gp_mean_prediction(t, o) for t in Xs])
+    fd_var = np.array([uo.grad_gp_var_prediction(t, o) for t in Xs])
+    assert dmu.shape == dvar.shape == Xs.shape
+    assert np.max(np.abs(dmu - fd_mu)) <= 1e-6 * np.max(np.abs(fd_mu))
+    assert np.max(np.abs(dvar - fd_var)) <= 1e-6 * np.max(np.abs(fd_var))
 
 
 def test_not_positive_definite_is_reported():
