@@ -146,6 +146,19 @@ def check(status, where):
         raise AlabiHipError(status, where)
 
 
+def destroy(handle, call, sync=False):
+    """Destroy a library handle (None or NULL: nothing to do) through its destroy ``call``, after a device synchronise if the
+    kernels that use it may still be running.  Errors are swallowed: at interpreter shutdown the library may be gone already."""
+    if handle is not None and handle.value:
+        try:
+            if sync:
+                import torch
+                torch.cuda.synchronize()
+            getattr(lib(), call)(handle)
+        except Exception:  # noqa: BLE001
+            pass
+
+
 def ptr(t):
     """Device pointer of a torch tensor (None -> NULL)."""
     return None if t is None else C.c_void_p(t.data_ptr())

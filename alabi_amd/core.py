@@ -27,6 +27,7 @@ import scipy.optimize as op
 import torch
 
 from . import gp_utils, mcmc_utils
+from . import posterior as post
 from . import utility as ut
 from .gp import HipGP, _dev
 from .sampler import EnsembleSampler
@@ -34,47 +35,6 @@ from .sampler import EnsembleSampler
 __all__ = ["SurrogateModel", "CachedSurrogateLikelihood"]
 
 _KERNELS = ("ExpSquaredKernel", "RationalQuadraticKernel", "Matern32Kernel", "Matern52Kernel")
-
-
-def _is_identity(scaler, probe):
-    try:
-        return bool(np.array_equal(np.asarray(scaler.transform(probe)), np.asarray(probe)))
-    except Exception:  # noqa: BLE001
-        return False
-
-
-def _affine_map(fn, box):
-    """(mult, add) with fn(x) == mult * x + add per column on `box` ([d, 2] lower / upper), or None if fn is not an
-    increasing-or-decreasing affine map per dimension there (checked at three interior points)."""
-    try:
-        box = np.asarray(box, dtype=np.float64).reshape(-1, 2)
-        lo, hi = box[:, 0], box[:, 1]
-        f_lo = np.asarray(fn(lo.reshape(1, -1)), dtype=np.float64).reshape(-1)
-        f_hi = np.asarray(fn(hi.reshape(1, -1)), dtype=np.float64).reshape(-1)
-        if f_lo.shape != lo.shape or np.any(hi == lo):
-            return None
-        mult = (f_hi - f_lo) / (hi - lo)
-        add = f_lo - mult * lo
-        if not (np.all(np.isfinite(mult)) and np.all(np.isfinite(add)) and np.all(mult != 0)):
-            return None
-        for frac in (0.25, 0.5, 0.8):
-            x = lo + frac * (hi - lo)
-            fx = np.asarray(fn(x.reshape(1, -1)), dtype=np.float64).reshape(-1)
-            if not np.allclose(fx, mult * x + add, rtol=1e-11, atol=1e-11 * (np.abs(f_hi) + np.abs(f_lo) + 1e-300)):
-                return None
-        return mult, add
-    except Exception:  # noqa: BLE001
-        return None
-
-
-def _uniform_prior_box(prior_transform, ndim):
-    """The box [ndim, 2] of ``partial(ut.prior_transform_uniform, bounds=B)`` (the tutorials' prior transform, which the
-    fused nested-sampling path samples directly), else None (any other callable runs on the host)."""
-    f = getattr(prior_transform, "func", None)
-    kwp = dict(getattr(prior_transform, "keywords", None) or {})
-    if f is ut.prior_transform_uniform and "bounds" in kwp and not getattr(prior_transform, "args", ()):
-        return np.asarray(kwp["bounds"], dtype=np.float64).reshape(ndim, 2)
-    return None
 
 
 class CachedSurrogateLikelihood:
@@ -915,12 +875,10 @@ class SurrogateModel(object):
             return v if np.isfinite(v) else -np.inf
 
         cand = ut.prior_sampler(bounds=self.bounds, nsample=4096, sampler="uniform", random_state=self._seed())
-        if like_fn == self.surrogate_log_likelihood:     # one batched GPU predict
-            like_c = np.asarray(like_fn(cand), dtype=np.float64).reshape(-1)
-        else:
+        if like_fn != self.surrogate_log_likelihood:     # row by row on the host; the surrogate: one batched GPU predict
             cand = cand[:256]
-            like_c = np.array([float(np.asarray(like_fn(c.reshape(1, -1))).reshape(-1)[0]) for c in cand])
-        post_c = like_c + np.array([float(np.asarray(prior_fn(c.reshape(1, -1))).reshape(-1)[0]) for c in cand])
+        like_c = post.host_likelihood(like_fn, self.surrogate_log_likelihood, (1, -1))(cand)
+        post_c = like_c + post.host_rows(prior_fn, (1, -1))(cand)
         post_c = np.where(np.isfinite(post_c), post_c, -np.inf)
         starts = [cand[i] for i in np.argsort(-post_c)[:max(int(nRestarts), 1)]]
         if theta0 is not None:
@@ -942,24 +900,34 @@ class SurrogateModel(object):
         ball = best_x + 1e-3 * (hi - lo) * self._rng.standard_normal((nw, self.ndim))
         return np.minimum(np.maximum(ball, lo + 1e-9 * (hi - lo)), hi - 1e-9 * (hi - lo))
 
-    def _y_unscale_kind(self):
-        """How y_scaler.inverse_transform acts on a GP mean: ("affine", slope, offset), ("nlog",) / ("log",) for the two
-        non-affine scalers the reference ships (alabi/utility.py:62-71), or None (anything else)."""
-        y_lo, y_hi = float(np.min(self._y)), float(np.max(self._y))
-        aff = _affine_map(self.y_scaler.inverse_transform, np.array([[y_lo - 1.0, y_hi + 1.0]]))
-        if aff is not None and aff[0][0] > 0:
-            return ("affine", float(aff[0][0]), float(aff[1][0]))
-        try:
-            probe = np.linspace(y_lo - 0.5, y_hi + 0.5, 7).reshape(-1, 1)
-            got = np.asarray(self.y_scaler.inverse_transform(probe), dtype=np.float64).reshape(-1)
-            p10 = 10.0 ** probe.reshape(-1)
-            if np.allclose(got, -p10, rtol=1e-12, atol=0.0):
-                return ("nlog",)
-            if np.allclose(got, p10, rtol=1e-12, atol=0.0):
-                return ("log",)
-        except Exception:  # noqa: BLE001
-            pass
-        return None
+    # ---- what run_emcee and run_dynesty share
+    def _handle_owner(self):
+        """(gp, y) a sampler is built on: ``self.gp`` carrying the latest hyper-parameters / data, or -- like_fn="true" before any GP
+        exists -- a bare HipGP, because the device handle needs an owner only."""
+        if not hasattr(self, "gp"):
+            return HipGP(self.ndim), np.zeros(1)
+        if len(self.training_results["iteration"]) > 0:
+            self.eval_gp_at_iteration(-1)
+        return self.gp, self._y
+
+    def _write_samples(self, sampler, samples, samples_file):
+        """After a sampler run (the caller lets rank 0 only through): the cached model, quietly, and the .npz of samples, whose
+        name is returned."""
+        if self.cache:
+            try:
+                self.save()
+            except Exception:  # noqa: BLE001
+                pass
+        if samples_file is not None:
+            fname = f"{self.savedir}/{samples_file}"
+        elif self.like_fn_name == "true":
+            fname = f"{self.savedir}/{sampler}_samples_final_{self.like_fn_name}.npz"
+        else:
+            res = getattr(self, "training_results", {"iteration": []})
+            it = res["iteration"][-1] if len(res["iteration"]) else 0
+            fname = f"{self.savedir}/{sampler}_samples_final_{self.like_fn_name}_iter_{it}.npz"
+        np.savez(fname, samples=samples)
+        return fname
 
     def run_emcee(self, like_fn=None, prior_fn=None, nwalkers=None, nsteps=int(5e4), sampler_kwargs={}, run_kwargs={},
                   opt_init=False, multi_proc=True, prior_fn_comment=None, burn=None, thin=None, samples_file=None,
@@ -989,147 +957,69 @@ class SurrogateModel(object):
         Files (the .npz of samples, the cached model) are written by rank 0 only."""
         from . import dist as adist
         rank, world = adist.world_info()
-        sampler_kwargs = dict(sampler_kwargs)
-        shard = bool(sampler_kwargs.pop("shard", False)) and bool(multi_proc) and world > 1
+        kw = dict(sampler_kwargs)
+        shard = bool(kw.pop("shard", False)) and bool(multi_proc) and world > 1
         replicas = bool(multi_proc) and world > 1 and not shard
         # ---- likelihood
-        like_host = None                          # host callable on theta [n,d] -> [n], or None for the device surrogate
         if like_fn is None or (isinstance(like_fn, str) and like_fn.lower() in ("surrogate", "gp")):
-            self.like_fn_name = "surrogate"
-            self.like_fn = self.surrogate_log_likelihood
+            self.like_fn_name, self.like_fn = "surrogate", self.surrogate_log_likelihood
             if not hasattr(self, "gp"):
                 raise NameError("GP has not been trained")
         elif isinstance(like_fn, str) and like_fn.lower() == "true":
-            self.like_fn_name = "true"
-            self.like_fn = self.true_log_likelihood
-            like_host = self.like_fn
+            self.like_fn_name, self.like_fn = "true", self.true_log_likelihood
         elif callable(like_fn):
-            self.like_fn_name = "likelihood"
-            self.like_fn = like_fn
-            like_host = like_fn
+            self.like_fn_name, self.like_fn = "likelihood", like_fn
         else:
             raise ValueError("like_fn must be None, 'surrogate', 'gp', 'true' or a callable")
-        # ---- prior: None (uniform box) or one of the two shipped priors fuse into the kernel; anything else is a host call
-        prior_bounds, prior_data, prior_host = None, None, None
-        if prior_fn is not None:
-            f = getattr(prior_fn, "func", None)
-            kwp = dict(getattr(prior_fn, "keywords", None) or {})
-            argp = tuple(getattr(prior_fn, "args", ()) or ())
-            name = getattr(f, "__name__", "")
-            if name == "lnprior_uniform" and f is ut.lnprior_uniform and ("bounds" in kwp or len(argp) >= 1):
-                prior_bounds = kwp.get("bounds", argp[0] if argp else None)
-            elif name == "lnprior_normal" and f is ut.lnprior_normal and (("bounds" in kwp and "data" in kwp) or len(argp) >= 2):
-                prior_bounds = kwp.get("bounds", argp[0] if argp else None)
-                prior_data = kwp.get("data", argp[1] if len(argp) > 1 else None)
-            else:
-                prior_host = prior_fn
-        # ---- scalers
-        t_aff = _affine_map(self.theta_scaler.transform, self.bounds) if hasattr(self, "theta_scaler") else \
-            (np.ones(self.ndim), np.zeros(self.ndim))
-        y_kind = self._y_unscale_kind() if (like_host is None) else ("affine", 1.0, 0.0)
-        if like_host is None and (t_aff is None or y_kind is None):
-            # exotic scalers: the surrogate is evaluated through surrogate_log_likelihood (batched GPU predict) on the host side
-            like_host = self.surrogate_log_likelihood
-        if like_host is not None:
-            t_aff = (np.ones(self.ndim), np.zeros(self.ndim))     # walkers move in theta itself
-            y_kind = ("affine", 1.0, 0.0)
-        t_mult, t_add = t_aff                      # scaled = t_mult * theta + t_add, per dimension
-        logp_affine = (y_kind[1], y_kind[2]) if y_kind[0] == "affine" else (1.0, 0.0)
-        logp_map = None if y_kind[0] == "affine" else y_kind[0]
-        box = self.bounds if prior_bounds is None else np.asarray(prior_bounds, dtype=np.float64).reshape(self.ndim, 2)
-        _box = np.sort(box * t_mult[:, None] + t_add[:, None], axis=1)          # the prior box in scaled coordinates
-        normal_prior = None
-        if prior_data is not None:
-            pm = np.array([np.nan if dd[0] is None else float(dd[0]) for dd in prior_data])
-            ps = np.array([np.nan if dd[0] is None else float(dd[1]) for dd in prior_data])
-            # N(m, s) on theta_k is N(mult m + add, |mult| s) on the scaled coordinate; the density stays the theta-space one,
-            # so log|mult| per normal coordinate goes back into the log-probability through the constant shift
-            normal_prior = (pm * t_mult + t_add, ps * np.abs(t_mult))
-            if logp_map is None:
-                logp_affine = (logp_affine[0], logp_affine[1] + float(np.sum(np.log(np.abs(t_mult[np.isfinite(pm)])))))
-            elif np.any(t_mult[np.isfinite(pm)] != 1.0):
-                prior_host, normal_prior = prior_fn, None        # cannot fold the Jacobian behind a non-affine map: host prior
-        to_theta = lambda c: (np.asarray(c) - t_add) / t_mult  # noqa: E731
-
-        if like_host is not None and prior_fn is not None and prior_data is not None:
-            prior_host, normal_prior = prior_fn, None            # the fused normal prior lives in the device likelihood path
-
-        def _rows(fn):
-            """Host callable on sampler coordinates [n,d] -> [n]: one call per point with a (1, d) argument, exactly what
-            lnprob hands to like_fn / prior_fn (core.py:2097-2098)."""
-            def call(q):
-                th = to_theta(q)
-                return np.array([float(np.asarray(fn(row.reshape(1, -1))).reshape(-1)[0]) for row in th], dtype=np.float64)
-            return call
-
-        def _batched(fn):                                        # the surrogate takes the whole batch in one GPU predict
-            return lambda q: np.asarray(fn(to_theta(q)), dtype=np.float64).reshape(-1)
-        sampler_extra = {}
-        if prior_host is not None or like_host is not None:
-            like_call = None
-            if like_host is not None:
-                like_call = _batched(like_host) if like_host == self.surrogate_log_likelihood else _rows(like_host)
-            sampler_extra = dict(prior_fn=_rows(prior_host) if prior_host is not None else None, like_fn=like_call,
-                                 gate_box=prior_host is None)
+        like_host = None if self.like_fn_name == "surrogate" else self.like_fn     # on theta; None: the device surrogate
+        # ---- plan: None (uniform box) or one of the two shipped priors fuse into the kernel; anything else is a host call
+        plan = post.plan_ensemble(like_host, self.surrogate_log_likelihood, prior_fn, self.bounds,
+                                  getattr(self, "theta_scaler", None), getattr(self, "y_scaler", None), getattr(self, "_y", None))
+        sampler_extra = {} if plan.fused else dict(prior_fn=plan.host_prior, like_fn=plan.host_like,
+                                                   gate_box=plan.host_prior is None)
         self.prior_fn = partial(ut.lnprior_uniform, bounds=self.bounds) if prior_fn is None else prior_fn
         self.prior_fn_comment = ("Default uniform prior. \nPrior function: ut.prior_fn_uniform\n"
                                  f"\twith bounds {self.bounds}") if prior_fn_comment is None else prior_fn_comment
         self.nwalkers = int(10 * self.ndim) if nwalkers is None else int(nwalkers)
         self.nsteps = int(nsteps)
-        if hasattr(self, "gp") and len(self.training_results["iteration"]) > 0:
-            self.eval_gp_at_iteration(-1)   # makes self.gp carry the latest hyper-parameters / data
-        if shard and (prior_host is not None or like_host is not None):
+        gp_obj, y_obj = self._handle_owner()
+        if shard and not plan.fused:
             raise ValueError('sampler_kwargs={"shard": True} needs the fused log-probability (surrogate likelihood, shipped priors '
                              'and scalers); host callables run as replicas')
         if opt_init:
             p0 = self.find_map(prior_fn=self.prior_fn)           # core.py:2290-2292
         else:
             p0_seed = self._seed()                               # (drawn on every rank alike: the model's stream stays in step)
-            p0 = ut.prior_sampler(nsample=self.nwalkers, bounds=box, sampler="uniform",
+            p0 = ut.prior_sampler(nsample=self.nwalkers, bounds=plan.theta_box, sampler="uniform",
                                   random_state=p0_seed + (1000003 * rank if replicas else 0))
-        p0 = p0 * t_mult + t_add                   # walkers live in scaled coordinates
-        if hasattr(self, "gp"):
-            gp_obj, y_obj = self.gp, self._y
-        else:                                      # like_fn="true" before any GP exists: the handle needs an owner only
-            gp_obj, y_obj = HipGP(self.ndim), np.zeros(1)
+        p0 = p0 * plan.t_mult + plan.t_add         # walkers live in scaled coordinates
         if self.verbose:
             print(f"Running emcee-style ensemble on the GPU with {self.nwalkers} walkers for {self.nsteps} steps...")
-        all_chains, all_times, accumulated, run_number = [], [], 0, 1
-        kw = dict(sampler_kwargs)
+        self.emcee_runtime = 0.0
         kw.setdefault("seed", self._seed())
         if replicas:
             kw["seed"] = int(kw["seed"]) + rank
         if shard:
             kw["shard"] = True
-        while True:
+
+        def run(run_number):
+            start = p0
+            if run_number > 1:
+                start = self.emcee_sampler.get_last_sample().coords
+                kw["seed"] = self._seed() + (rank if replicas else 0)
             t0 = time.time()
-            self.emcee_sampler = EnsembleSampler(self.nwalkers, self.ndim, gp_obj, y_obj, _box, logp_affine=logp_affine,
-                                                 normal_prior=normal_prior, logp_map=logp_map, **sampler_extra, **kw)
-            self.emcee_sampler.run_mcmc(p0, self.nsteps, **run_kwargs)
-            all_times.append(time.time() - t0)
-            cur_iburn, cur_ithin = mcmc_utils.estimate_burnin(self.emcee_sampler, verbose=self.verbose)
-            cur_burn = burn if burn is not None else cur_iburn
-            cur_thin = thin if thin is not None else cur_ithin
-            cur = to_theta(self.emcee_sampler.get_chain(discard=cur_burn, thin=cur_thin, flat=True))
-            if replicas:
-                cur = adist.gather_replicas(cur)                 # every rank's kept samples, in rank order, on every rank
-            all_chains.append(cur)
-            accumulated += cur.shape[0]
-            if self.verbose and min_ess > 0:
-                print(f"Run {run_number} complete: {cur.shape[0]} samples (total {accumulated})")
-            if accumulated >= min_ess:
-                break
-            run_number += 1
-            if run_number > 10:
-                print(f"WARNING: Reached maximum of 10 runs, stopping with {accumulated} samples")
-                break
-            p0 = self.emcee_sampler.get_last_sample().coords
-            kw["seed"] = self._seed() + (rank if replicas else 0)
-        self.emcee_samples = np.vstack(all_chains) if len(all_chains) > 1 else all_chains[0]
-        self._emcee_full, self._emcee_full_src = None, (self.emcee_sampler, t_add, t_mult)     # emcee_samples_full: on first access
-        self.iburn, self.ithin = cur_iburn, cur_ithin
-        self.burn, self.thin = cur_burn, cur_thin
-        self.emcee_runtime = sum(all_times)
+            self.emcee_sampler = EnsembleSampler(self.nwalkers, self.ndim, gp_obj, y_obj, plan.box, logp_affine=plan.logp_affine,
+                                                 normal_prior=plan.normal_prior, logp_map=plan.logp_map, **sampler_extra, **kw)
+            self.emcee_sampler.run_mcmc(start, self.nsteps, **run_kwargs)
+            self.emcee_runtime += time.time() - t0
+            self.iburn, self.ithin = mcmc_utils.estimate_burnin(self.emcee_sampler, verbose=self.verbose)
+            self.burn = burn if burn is not None else self.iburn
+            self.thin = thin if thin is not None else self.ithin
+            cur = plan.to_theta(self.emcee_sampler.get_chain(discard=self.burn, thin=self.thin, flat=True))
+            return adist.gather_replicas(cur) if replicas else cur   # every rank's kept samples, in rank order, on every rank
+
+        self.emcee_samples = post.run_until_min_ess(run, min_ess, (lambda total: f" (total {total})") if self.verbose else None)
+        self._emcee_full, self._emcee_full_src = None, (self.emcee_sampler, plan.t_add, plan.t_mult)   # emcee_samples_full: lazily
         if self.like_fn_name == "true":
             self.emcee_samples_true = self.emcee_samples
         elif self.like_fn_name == "surrogate":
@@ -1148,20 +1038,7 @@ class SurrogateModel(object):
         self.emcee_run = True
         if (replicas or shard) and rank != 0:
             return                                               # files are rank 0's
-        if self.cache:
-            try:
-                self.save()
-            except Exception:  # noqa: BLE001
-                pass
-        if samples_file is not None:
-            fname = f"{self.savedir}/{samples_file}"
-        elif self.like_fn_name == "true":
-            fname = f"{self.savedir}/emcee_samples_final_{self.like_fn_name}.npz"
-        else:
-            res = getattr(self, "training_results", {"iteration": []})
-            it = res["iteration"][-1] if len(res["iteration"]) else 0
-            fname = f"{self.savedir}/emcee_samples_final_{self.like_fn_name}_iter_{it}.npz"
-        np.savez(fname, samples=self.emcee_samples)
+        self._write_samples("emcee", self.emcee_samples, samples_file)
 
     run_mcmc = run_emcee  # BASELINE.json's name for the same entry point
 
@@ -1202,23 +1079,16 @@ class SurrogateModel(object):
         if self.like_fn_name == "surrogate" and not hasattr(self, "gp"):
             raise NameError("GP has not been trained")
         # ---- prior transform (core.py:2575-2598)
-        box = None                                   # the uniform box the fused path can use, in theta
         if prior_transform is None:
             self.prior_transform = partial(ut.prior_transform_uniform, bounds=self.bounds)
             self.prior_transform_comment = ("Default uniform prior transform. \nPrior function: ut.prior_transform_uniform\n"
                                             f"\twith bounds {self.bounds}")
-            box = np.asarray(self.bounds, dtype=np.float64).reshape(self.ndim, 2)
         else:
             self.prior_transform = prior_transform
+            self.prior_transform_comment = prior_transform_comment
             if prior_transform_comment is None:
-                self.prior_transform_comment = "User defined prior transform."
-                try:
-                    self.prior_transform_comment += f"Prior function: {self.prior_transform.__name__}"
-                except Exception:  # noqa: BLE001
-                    self.prior_transform_comment += "Prior function: unrecorded"
-            else:
-                self.prior_transform_comment = prior_transform_comment
-            box = _uniform_prior_box(prior_transform, self.ndim)
+                self.prior_transform_comment = ("User defined prior transform."
+                                                f"Prior function: {getattr(prior_transform, '__name__', 'unrecorded')}")
         dynesty_t0 = time.time()
         # ---- sampler / run settings (core.py:2603-2649)
         skw = dict(sampler_kwargs)
@@ -1245,80 +1115,35 @@ class SurrogateModel(object):
                    "wt_kwargs", "stop_kwargs"}
         if set(rkw) - allowed:
             raise TypeError(f"run_dynesty: unsupported run_kwargs {sorted(set(rkw) - allowed)}")
-        # ---- which path
-        t_aff = _affine_map(self.theta_scaler.transform, self.bounds) if hasattr(self, "theta_scaler") else \
-            (np.ones(self.ndim), np.zeros(self.ndim))
-        y_kind = self._y_unscale_kind() if hasattr(self, "gp") else None
-        fused = self.like_fn_name == "surrogate" and box is not None and t_aff is not None and y_kind is not None
-        if hasattr(self, "gp") and len(self.training_results["iteration"]) > 0:
-            self.eval_gp_at_iteration(-1)            # makes self.gp carry the latest hyper-parameters / data
-        if hasattr(self, "gp"):
-            gp_obj, y_obj = self.gp, self._y
-        else:                                        # like_fn="true" before any GP exists: the handle needs an owner only
-            gp_obj, y_obj = HipGP(self.ndim), np.zeros(1)
-        pt = self.prior_transform
-        if fused:
-            lo_t, hi_t = box[:, 0], box[:, 1]
-            t_mult, t_add = t_aff
-            bounds_s = np.stack([lo_t * t_mult + t_add, hi_t * t_mult + t_add], axis=1)
-            logp_affine = (y_kind[1], y_kind[2]) if y_kind[0] == "affine" else (1.0, 0.0)
-            logp_map = None if y_kind[0] == "affine" else y_kind[0]
-            host_loglike = None
-            to_theta = lambda u: lo_t + u * (hi_t - lo_t)                     # noqa: E731  (prior_transform_uniform)
-        else:
-            bounds_s = np.tile([0.0, 1.0], (self.ndim, 1))
-            logp_affine, logp_map = (1.0, 0.0), None
-            like = self.like_fn
-
-            def to_theta(u):
-                return np.array([np.asarray(pt(row), dtype=np.float64).reshape(-1) for row in np.atleast_2d(u)])
-
-            if self.like_fn_name == "surrogate":                                # one batched GPU predict
-                def host_loglike(u):
-                    return np.asarray(like(to_theta(u)), dtype=np.float64).reshape(-1)
-            else:
-                def host_loglike(u):
-                    return np.array([float(np.asarray(like(th)).reshape(-1)[0]) for th in to_theta(u)], dtype=np.float64)
+        # ---- plan: fused walks, or the host evaluates like_fn(prior_transform(u))
+        plan = post.plan_nested(self.like_fn, self.surrogate_log_likelihood, self.prior_transform, self.bounds,
+                                getattr(self, "theta_scaler", None), getattr(self, "y_scaler", None), getattr(self, "_y", None))
+        gp_obj, y_obj = self._handle_owner()
         if self.verbose:
-            print(f"Running nested sampling ({mode}, {'fused GPU walks' if fused else 'host likelihood'}) with {nlive} live "
+            print(f"Running nested sampling ({mode}, {'fused GPU walks' if plan.fused else 'host likelihood'}) with {nlive} live "
                   "points...")
-        all_samples, all_logz, run_number, accumulated = [], [], 1, 0
-        run_seed = self._seed() if seed is None else int(seed)
-        while True:
-            s = run_seed + rank
-            backend = GPUWalkBackend(gp_obj, y_obj, bounds_s, seed=s, to_theta=to_theta, logp_affine=logp_affine,
-                                     logp_map=logp_map, host_loglike=host_loglike)
-            dsampler = NestedSampler(backend, nlive, dynamic=(mode == "dynamic"), walks=walks, batch=batch, seed=s)
+        all_logz = []
+
+        def run(run_number):
+            s = (self._seed() if seed is None else int(seed) + 1000003 * (run_number - 1)) + rank
+            backend = GPUWalkBackend(gp_obj, y_obj, plan.box, seed=s, to_theta=plan.to_theta, logp_affine=plan.logp_affine,
+                                     logp_map=plan.logp_map, host_loglike=plan.host_like)
+            self.dynesty_sampler = NestedSampler(backend, nlive, dynamic=(mode == "dynamic"), walks=walks, batch=batch, seed=s)
             checkpoint = None
             if save_iter is not None and rank == 0:
                 pkl = os.path.join(self.savedir, f"dynesty_sampler_{self.like_fn_name}_run{run_number}.pkl")
-                checkpoint = PickleCheckpoint(dsampler, pkl, save_iter)
-            res = dsampler.run_nested(checkpoint=checkpoint, **rkw)
+                checkpoint = PickleCheckpoint(self.dynesty_sampler, pkl, save_iter)
+            res = self.dynesty_sampler.run_nested(checkpoint=checkpoint, **rkw)
             if checkpoint is not None:
                 checkpoint.write(res)
             backend.close()
-            cur = res.samples_equal(np.random.default_rng(s))
-            all_samples.append(cur)
+            self.dynesty_results, self.dynesty_logz_err, self.dynesty_path = res, float(res.logzerr[-1]), backend.path
             all_logz.append(float(res.logz[-1]))
-            accumulated += cur.shape[0]
-            if self.verbose and min_ess > 0:
-                print(f"Run {run_number} complete: {cur.shape[0]} samples, logZ = {res.logz[-1]:.3f}")
-            if accumulated >= min_ess:
-                break
-            run_number += 1
-            if run_number > 10:
-                print(f"WARNING: Reached maximum of 10 runs, stopping with {accumulated} samples")
-                break
-            run_seed = self._seed() if seed is None else int(seed) + 1000003 * (run_number - 1)
-        if len(all_samples) > 1:
-            self.dynesty_samples = np.vstack(all_samples)
-            self.dynesty_logz = max(all_logz)        # the reference keeps the largest log evidence of the runs
-        else:
-            self.dynesty_samples, self.dynesty_logz = all_samples[0], all_logz[0]
-        self.dynesty_sampler = dsampler
-        self.dynesty_results = res
-        self.dynesty_logz_err = float(res.logzerr[-1])
-        self.dynesty_path = backend.path
+            return res.samples_equal(np.random.default_rng(s))
+
+        note = (lambda total: f", logZ = {all_logz[-1]:.3f}") if self.verbose else None
+        self.dynesty_samples = post.run_until_min_ess(run, min_ess, note)
+        self.dynesty_logz = max(all_logz)            # the reference keeps the largest log evidence of the runs
         if self.like_fn_name == "true":
             self.dynesty_samples_true = self.dynesty_samples
         elif self.like_fn_name == "surrogate":
@@ -1327,19 +1152,6 @@ class SurrogateModel(object):
         self.dynesty_runtime = time.time() - dynesty_t0
         if rank != 0:
             return                                   # files are rank 0's
-        if self.cache:
-            try:
-                self.save()
-            except Exception:  # noqa: BLE001
-                pass
-        if samples_file is not None:
-            fname = f"{self.savedir}/{samples_file}"
-        elif self.like_fn_name == "true":
-            fname = f"{self.savedir}/dynesty_samples_final_{self.like_fn_name}.npz"
-        else:
-            res_t = getattr(self, "training_results", {"iteration": []})
-            it = res_t["iteration"][-1] if len(res_t["iteration"]) else 0
-            fname = f"{self.savedir}/dynesty_samples_final_{self.like_fn_name}_iter_{it}.npz"
+        fname = self._write_samples("dynesty", self.dynesty_samples, samples_file)
         if self.verbose:
             print(f"Saved dynesty samples to {fname}")
-        np.savez(fname, samples=self.dynesty_samples)

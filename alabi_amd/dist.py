@@ -241,12 +241,7 @@ class ShardedRun:
         self._comm = comm
 
     def __del__(self):
-        try:
-            if getattr(self, "_comm", None) is not None:
-                torch.cuda.synchronize()
-                _lib.lib().alabi_dist_comm_destroy(self._comm)
-        except Exception:  # noqa: BLE001
-            pass
+        _lib.destroy(getattr(self, "_comm", None), "alabi_dist_comm_destroy", sync=True)
         self._comm = None
 
     def stats(self):

@@ -164,13 +164,19 @@ class HipGP:
         self._cap = cap
 
     def _release(self):
-        if getattr(self, "_handle", None) is not None:
-            try:
-                _lib.lib().alabi_gp_destroy(self._handle)
-            except Exception:
-                pass
+        _lib.destroy(getattr(self, "_handle", None), "alabi_gp_destroy")
         self._handle = None
         self._cap = 0
+
+    def sampler_handle(self, y, surrogate_on_device):
+        """The handle a sampler attaches to: with the surrogate evaluated on the device, the factorised GP with alpha ready for
+        ``y``; otherwise the GP only owns the handle, and a bare one will do."""
+        if surrogate_on_device:
+            self.predict_device(y, torch.zeros((1, self.ndim), dtype=torch.float64, device=_dev()))
+            return self.handle
+        if self._handle is None:
+            self._ensure_handle(64)
+        return self._handle
 
     def __del__(self):
         self._release()

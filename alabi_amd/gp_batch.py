@@ -31,11 +31,7 @@ class HipGPBatch:
         self.njobs = 0
 
     def close(self):
-        if getattr(self, "_handle", None) is not None:
-            try:
-                _lib.lib().alabi_gp_batch_destroy(self._handle)
-            except Exception:  # noqa: BLE001
-                pass
+        _lib.destroy(getattr(self, "_handle", None), "alabi_gp_batch_destroy")
         self._handle = None
 
     def __del__(self):

@@ -201,13 +201,7 @@ class DeviceKDE:
 
     # ------------------------------------------------------------------------ lifetime
     def _release(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            try:
-                torch.cuda.synchronize()
-                _lib.lib().alabi_kde_destroy(h)
-            except Exception:  # noqa: BLE001  (interpreter shutdown)
-                pass
+        _lib.destroy(getattr(self, "_handle", None), "alabi_kde_destroy", sync=True)
         self._handle = None
 
     def __del__(self):

@@ -382,13 +382,7 @@ class GPUWalkBackend:
     def _ensure(self):
         if self._ns is not None:
             return self._ns
-        if self.host_loglike is None:
-            self.gp.predict_device(self._y, torch.zeros((1, self.ndim), dtype=torch.float64, device=_dev()))   # alpha ready
-            h = self.gp.handle
-        else:                    # the surrogate is not evaluated on the device: the GP only owns the handle
-            if self.gp._handle is None:
-                self.gp._ensure_handle(64)
-            h = self.gp._handle
+        h = self.gp.sampler_handle(self._y, surrogate_on_device=self.host_loglike is None)
         ns = C.c_void_p()
         _lib.check(_lib.lib().alabi_ns_create(h, self.ndim, _lib.host_doubles(self.bounds.ravel()), C.c_ulonglong(self.seed),
                                               C.byref(ns)), "alabi_ns_create")
@@ -403,12 +397,7 @@ class GPUWalkBackend:
         return int(p.value)
 
     def close(self):
-        if getattr(self, "_ns", None) is not None:
-            try:
-                torch.cuda.synchronize()
-                _lib.lib().alabi_ns_destroy(self._ns)
-            except Exception:  # noqa: BLE001
-                pass
+        _lib.destroy(getattr(self, "_ns", None), "alabi_ns_destroy", sync=True)
         self._ns = None
 
     def __del__(self):

@@ -110,13 +110,7 @@ class EnsembleSampler:
 
     # ------------------------------------------------------------------ handle lifetime
     def _ensure_ens(self):
-        if self.like_fn_host is None:
-            self.gp.predict_device(self._y, torch.zeros((1, self.ndim), dtype=torch.float64, device=_dev()))  # alpha ready
-            h = self.gp.handle
-        else:                    # the surrogate is not evaluated on the device: the GP only owns the ensemble handle
-            if self.gp._handle is None:
-                self.gp._ensure_handle(64)
-            h = self.gp._handle
+        h = self.gp.sampler_handle(self._y, surrogate_on_device=self.like_fn_host is None)
         if self._ens is not None and self._ens_gp_handle is not None and self._ens_gp_handle.value == h.value:
             return
         self._release()
@@ -137,12 +131,7 @@ class EnsembleSampler:
         self._ens_gp_handle = C.c_void_p(h.value)
 
     def _release(self):
-        if getattr(self, "_ens", None) is not None:
-            try:
-                torch.cuda.synchronize()
-                _lib.lib().alabi_ens_destroy(self._ens)
-            except Exception:
-                pass
+        _lib.destroy(getattr(self, "_ens", None), "alabi_ens_destroy", sync=True)
         self._ens = None
         self._ens_gp_handle = None
 

@@ -210,7 +210,7 @@ def test_uniform_prior_transform_partial_selects_the_fused_box():
     """run_dynesty samples the box of the tutorial's partial(prior_transform_uniform, bounds=B) on the fused path; any other
     prior transform (including prior_transform_uniform itself with bounds passed positionally) goes to the host."""
     from alabi_amd import utility as ut
-    from alabi_amd.core import _uniform_prior_box
+    from alabi_amd.posterior import _uniform_prior_box
     B = np.array([[-2.0, 3.0], [0.5, 1.5]])
     box = _uniform_prior_box(partial(ut.prior_transform_uniform, bounds=B), 2)
     assert np.array_equal(box, B)
