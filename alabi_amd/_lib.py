@@ -95,6 +95,11 @@ SIGNATURES = {
     "alabi_ns_walk": (_i, [_vp, _ll, _i, _vp, _vp, _i, _d, _vp, _d, _i, _vp, _vp, _vp, _vp]),
     "alabi_ns_propose": (_i, [_vp, _ll, _i, _vp, _i, _i, _vp, _d, _vp, _vp]),
     "alabi_ns_accept": (_i, [_vp, _i, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
+    "alabi_ns_slice": (_i, [_vp, _ll, _i, _vp, _vp, _i, _d, _vp, _d, _i, _vp, _vp, _vp, _vp]),
+    "alabi_ns_slice_state_bytes": (_i, [_vp, _i, C.POINTER(_ll)]),
+    "alabi_ns_slice_begin": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "alabi_ns_slice_step": (_i, [_vp, _ll, _i, _i, _d, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    "alabi_ns_slice_end": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "alabi_ns_last_path": (_i, [_vp, _pi]),
     "alabi_kde_create": (_i, [_i, C.POINTER(_vp)]),
     "alabi_kde_destroy": (_i, [_vp]),

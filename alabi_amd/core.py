@@ -1054,8 +1054,11 @@ class SurrogateModel(object):
         * Otherwise (like_fn "true" or a callable, any other prior_transform, scalers the kernel cannot fold) the device proposes
           and accepts, and the host evaluates ``like_fn(prior_transform(u))`` row by row with 1-D arrays of shape (d,), as
           dynesty calls them (the surrogate under exotic scalers takes the whole batch in one call).
-        sampler_kwargs: ``nlive`` (50 ndim), ``sample`` ("auto" / "rwalk"), ``walks`` (25), ``batch`` (ceil(nlive / 4)),
-        ``seed``; ``bound``, ``pool``, ``queue_size`` and ``multi_proc`` have no effect.  run_kwargs: ``dlogz`` (0.5),
+        sampler_kwargs: ``nlive`` (50 ndim), ``sample`` ("auto" / "rwalk": ``walks`` (25) Metropolis steps per walk; "rslice":
+        ``slices`` (3 (3 + ndim)) random-direction slice updates per walk, 5-15 times the likelihood evaluations of the random
+        walk), ``batch`` (ceil(nlive / 4)), ``seed``.  Above ndim = 20 pass ``sample="rslice"``: 25 random-walk steps no longer
+        forget the start point there, and log Z comes out too high by several logzerr ("auto" stays the random walk at every
+        dimension).  ``bound``, ``pool``, ``queue_size`` and ``multi_proc`` have no effect.  run_kwargs: ``dlogz`` (0.5),
         ``maxiter`` (5e4), ``maxcall``, and for mode="dynamic" ``dlogz_init`` (0.5), ``nlive_init``, ``nlive_batch``,
         ``maxbatch`` (10), ``n_effective`` (1e4), ``wt_kwargs`` / ``stop_kwargs`` (pfrac = 1.0 only).  Under
         ``torch.distributed`` every rank runs its own sampler (seed + rank) and rank 0 writes the files."""
@@ -1094,9 +1097,12 @@ class SurrogateModel(object):
         skw = dict(sampler_kwargs)
         nlive = int(skw.pop("nlive", 50 * self.ndim))
         sample = skw.pop("sample", "auto")
-        if sample not in ("auto", "rwalk"):
-            raise NotImplementedError(f"sample={sample!r}: only the random walk ('auto' / 'rwalk') is built")
+        if sample not in ("auto", "rwalk", "rslice"):
+            raise NotImplementedError(f"sample={sample!r}: only the random walk ('auto' / 'rwalk') and random-direction slice "
+                                      "sampling ('rslice') are built")
         walks = int(skw.pop("walks", 25))
+        slices = skw.pop("slices", None)
+        move = {"sample": "rslice", "slices": slices} if sample == "rslice" else {}     # the random walk: the sampler's defaults
         batch = skw.pop("batch", None)
         seed = skw.pop("seed", None)
         for k in ("bound", "pool", "queue_size", "first_update", "update_interval", "bootstrap", "enlarge"):
@@ -1128,7 +1134,8 @@ class SurrogateModel(object):
             s = (self._seed() if seed is None else int(seed) + 1000003 * (run_number - 1)) + rank
             backend = GPUWalkBackend(gp_obj, y_obj, plan.box, seed=s, to_theta=plan.to_theta, logp_affine=plan.logp_affine,
                                      logp_map=plan.logp_map, host_loglike=plan.host_like)
-            self.dynesty_sampler = NestedSampler(backend, nlive, dynamic=(mode == "dynamic"), walks=walks, batch=batch, seed=s)
+            self.dynesty_sampler = NestedSampler(backend, nlive, dynamic=(mode == "dynamic"), walks=walks, batch=batch, seed=s,
+                                                 **move)
             checkpoint = None
             if save_iter is not None and rank == 0:
                 pkl = os.path.join(self.savedir, f"dynesty_sampler_{self.like_fn_name}_run{run_number}.pkl")

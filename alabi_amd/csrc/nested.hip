@@ -21,6 +21,12 @@
 //                               Cholesky factor C of the live points' covariance held in LDS, the cube gate 0 < u' < 1, the
 //                               GP mean at x(u'), accept iff logL(u') > L*.  A walk that accepts nothing returns its start
 //                               bit for bit.
+//   ns_slice_kernel<D, GENERIC, TMAX, TILED>  random-direction slice sampling (dynesty's "rslice"), one workgroup per walk, all slices
+//                               of the walk in one launch, the training-set share in VGPRs as above.  The slice is a state machine
+//                               (ns_slice_advance: direction, stepping out, shrinking; its scalars live in LDS) advanced by wave 0
+//                               from one in-cube query to the next; the loop around it holds the single ns_logl call site.
+//   ns_slice_step_kernel        the same state machine driven one query at a time around a host likelihood: per-walk state in
+//                               device memory, consumes the host's logL of the pending query, advances to the next one.
 //   ns_prior_kernel             uniform points in the cube.
 //   ns_propose_kernel           the proposal of one step of every walk (host-callable likelihoods): the same draws and the same
 //                               arithmetic as the fused walk (shared functions below), so both paths move identically.
@@ -31,6 +37,9 @@
 //   u1 = u53(r0, r1), u2 = u53(r2, r3), rad = sqrt(-2 log(1 - u1)), z_2j = rad cos(2 pi u2), z_2j+1 = rad sin(2 pi u2).
 // Prior draws use step = 0xFFFFFFFF: coordinate 2j = u53(r0, r1), 2j+1 = u53(r2, r3).  Splitting the walks of one call into
 // several launches (walk_id0 offsets) therefore gives bit-identical results.
+// Slice move (ns_slice_kernel / ns_slice_step_kernel): slice s of a walk takes its direction normals from step = s as above, and its
+// uniforms from counter (call, walk id, 0x80000000 | s, m), value u53(r0, r1): m = 0 the interval offset r, m >= 1 the m-th shrink
+// draw.  s < 2^31 - 1 keeps these apart from the prior draws.
 #include <cmath>
 #include <new>
 #include "ens_device.hpp"
@@ -165,6 +174,208 @@ __device__ inline double ns_logl(const NsArgs& p, const f64x2 (&xa)[D], f64x2 aa
         if (p.ymap) lp = apply_ymap(lp, p.ymap);
     }
     return lp;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- slice move
+#define ALABI_NS_SLICE_CAP 64            // contractions after which a slice ends where it started (termination guard)
+enum { NS_INIT = 0, NS_LEFT = 1, NS_RIGHT = 2, NS_SHRINK = 3, NS_DONE = 4 };
+
+// Scalars of one walk.  In the split path they are followed in device memory by u[d], a[d], q[d] (ns_slice_stride).
+struct NsSliceState {
+    double tl, tr, t, L;                 // interval ends and the coordinate of the pending query along the axis; logL of the walk
+    int phase, s, m, ncs;                // ncs: contractions of slice s so far
+    int nev, nexp, ncon, ncap;           // evaluations, expansions, contractions, capped slices of the walk
+    int pending, pad;                    // a query (point q, coordinate t) waits for its logL
+};
+
+__host__ __device__ inline size_t ns_slice_stride(int d) { return sizeof(NsSliceState) + (size_t)3 * d * sizeof(double); }
+
+__device__ inline double ns_slice_uniform(unsigned long long seed, long long call, uint32_t wid, int s, int m) {
+    uint32_t r[4];
+    philox4x32_10((uint32_t)call, wid, 0x80000000u | (uint32_t)s, (uint32_t)m, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    return u53(r[0], r[1]);
+}
+
+// Advances one walk from its state to its next query strictly inside the cube (returns 1; the point is in q_s, its logL is to be
+// handed in as `lp` by the next call) or to its end (returns 0).  Called by all 64 lanes of ONE wave with identical scalar
+// arguments: the scalars of the state are read into registers, carried wave-uniformly and written back by lane 0; lane k < d owns
+// coordinate k of the position u_s, the axis a_s and the query q_s, so no lane reads what another one wrote in this call.  No
+// barrier inside.  C: lower-triangular factor, row stride ldc, zero above the diagonal.
+__device__ __forceinline__ int ns_slice_advance(NsSliceState* st, double* u_s, double* a_s, double* q_s, const double* C, int ldc,
+                                       unsigned long long seed, long long call, uint32_t wid, int d, int slices, double scale,
+                                       double lstar, int lane, double lp) {
+    double tl = st->tl, tr = st->tr, t = st->t, L = st->L;
+    int phase = st->phase, s = st->s, m = st->m, ncs = st->ncs;
+    int nev = st->nev, nexp = st->nexp, ncon = st->ncon, ncap = st->ncap;
+    bool have = st->pending != 0;
+    const bool mine = lane < d;
+    double u = mine ? u_s[lane] : 0.5, a = mine ? a_s[lane] : 0.0, q = mine ? q_s[lane] : 0.5;
+    int query = 0;
+    while (phase != NS_DONE) {
+        bool contract = false;
+        if (have) {                                          // the logL of the point at t
+            have = false;
+            nev += 1;
+            const bool above = lp > lstar;                   // false for NaN
+            if (phase == NS_LEFT) {
+                if (above) { tl -= 1.0; nexp += 1; } else phase = NS_RIGHT;
+            } else if (phase == NS_RIGHT) {
+                if (above) { tr += 1.0; nexp += 1; } else phase = NS_SHRINK;
+            } else if (above) {
+                u = q; L = lp; s += 1; phase = NS_INIT;
+            } else {
+                contract = true;
+            }
+        }
+        if (contract) {
+            if (t < 0.0) tl = t; else tr = t;
+            ncon += 1; ncs += 1;
+        }
+        if (phase == NS_INIT) {
+            if (s >= slices) { phase = NS_DONE; break; }
+            // axis a = scale C z / |z|: pair j of the normals is drawn by lane j and read by every lane through the cross-lane network
+            double z0 = 0.0, z1 = 0.0;
+            if (2 * lane < d) ns_normal_pair(seed, call, wid, (uint32_t)s, (uint32_t)lane, z0, z1);
+            double acc = 0.0, n2 = 0.0;
+            for (int i = 0; i < d; ++i) {
+                const double zi = __shfl((i & 1) ? z1 : z0, i >> 1, 64);
+                n2 = fma(zi, zi, n2);
+                if (mine && i <= lane) acc = fma(C[(size_t)lane * ldc + i], zi, acc);
+            }
+            a = (scale * acc) / sqrt(n2);
+            const double r = ns_slice_uniform(seed, call, wid, s, 0);
+            tl = -r; tr = 1.0 - r; m = 1; ncs = 0; phase = NS_LEFT;
+        }
+        if (phase == NS_SHRINK) {
+            if (ncs >= ALABI_NS_SLICE_CAP) { ncap += 1; s += 1; phase = NS_INIT; continue; }
+            const double w = tr - tl;
+            t = tl + ns_slice_uniform(seed, call, wid, s, m) * w;
+            m += 1;
+        } else {
+            t = phase == NS_LEFT ? tl : tr;
+        }
+        q = u + t * a;
+        if (__all(!mine || (q > 0.0 && q < 1.0))) { query = 1; break; }
+        // outside the cube: the stepping on this side ends / one contraction, without an evaluation
+        if (phase == NS_LEFT) phase = NS_RIGHT;
+        else if (phase == NS_RIGHT) phase = NS_SHRINK;
+        else { if (t < 0.0) tl = t; else tr = t; ncon += 1; ncs += 1; }
+    }
+    if (mine) { u_s[lane] = u; a_s[lane] = a; q_s[lane] = q; }
+    if (lane == 0) {
+        st->tl = tl; st->tr = tr; st->t = t; st->L = L;
+        st->phase = phase; st->s = s; st->m = m; st->ncs = ncs;
+        st->nev = nev; st->nexp = nexp; st->ncon = ncon; st->ncap = ncap;
+        st->pending = query;
+    }
+    return query;
+}
+
+__device__ inline void ns_slice_reset(NsSliceState* st, double logl) {
+    st->tl = 0.0; st->tr = 0.0; st->t = 0.0; st->L = logl;
+    st->phase = NS_INIT; st->s = 0; st->m = 0; st->ncs = 0;
+    st->nev = 0; st->nexp = 0; st->ncon = 0; st->ncap = 0;
+    st->pending = 0; st->pad = 0;
+}
+
+// NsArgs as the walk kernel; p.walks = slices, p.n_acc = counts [4K]: evaluations, expansions, contractions, capped slices.
+template <int D, bool GENERIC, int TMAX, bool TILED>
+__global__ void __launch_bounds__(TMAX)
+ns_slice_kernel(NsArgs p) {
+    __shared__ double C_s[D * D];
+    __shared__ double u_s[D], a_s[D], q_s[D], qs_s[D];
+    __shared__ double scratch[16];
+    __shared__ NsSliceState st_s;
+    __shared__ int go_s;
+    const int tid = threadIdx.x, T = blockDim.x, b = blockIdx.x, d = p.d;
+    const uint32_t wid = (uint32_t)(p.walk_id0 + b);
+    const int half = p.Npad >> 1;
+    const bool vA = tid < half;
+    f64x2 xa[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k)
+        xa[k] = vA ? reinterpret_cast<const f64x2*>(p.Xsrc + (size_t)k * p.Npad)[tid] : f64x2{0.0, 0.0};
+    const f64x2 aa = vA ? reinterpret_cast<const f64x2*>(p.Asrc)[tid] : (GENERIC ? f64x2{0.0, 0.0} : f64x2{ALABI_SE_PAD, ALABI_SE_PAD});
+    for (int i = tid; i < D * D; i += T) {
+        const int r = i / D, c = i % D;
+        C_s[i] = (r < d && c <= r && p.walks > 0) ? p.chol[(size_t)r * d + c] : 0.0;
+    }
+    if (tid < D) {
+        u_s[tid] = tid < d ? p.u0[(size_t)b * d + tid] : 0.0;
+        a_s[tid] = 0.0; q_s[tid] = 0.0; qs_s[tid] = 0.0;
+    }
+    if (tid == 0) ns_slice_reset(&st_s, p.logl0[b]);
+    __syncthreads();
+    double lp = 0.0;
+    for (;;) {
+        if (tid < 64) {
+            const int query = ns_slice_advance(&st_s, u_s, a_s, q_s, C_s, D, p.seed, p.call, wid, d, p.walks, p.scale, p.logl_star,
+                                               tid, lp);
+            if (tid < d) qs_s[tid] = ns_gp_coord<GENERIC>(p, tid, q_s[tid]);
+            if (tid == 0) go_s = query;
+        }
+        __syncthreads();
+        if (!go_s) break;                                    // workgroup-uniform
+        // wave 0 writes go_s / qs_s / scratch again only after the barrier inside ns_logl, which every wave passes after reading them
+        lp = ns_logl<D, GENERIC, TILED>(p, xa, aa, qs_s, scratch);
+    }
+    if (tid < d) p.u_out[(size_t)b * d + tid] = u_s[tid];
+    if (tid == 0) {
+        p.logl_out[b] = st_s.L;
+        if (p.n_acc) {
+            p.n_acc[b] = st_s.nev; p.n_acc[p.K + b] = st_s.nexp; p.n_acc[2 * p.K + b] = st_s.ncon; p.n_acc[3 * p.K + b] = st_s.ncap;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256)
+ns_slice_begin_kernel(int K, int d, const double* __restrict__ u0, const double* __restrict__ logl0, char* __restrict__ state) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= K) return;
+    char* base = state + (size_t)b * ns_slice_stride(d);
+    ns_slice_reset(reinterpret_cast<NsSliceState*>(base), logl0[b]);
+    double* v = reinterpret_cast<double*>(base + sizeof(NsSliceState));
+    for (int k = 0; k < d; ++k) { v[k] = u0[(size_t)b * d + k]; v[d + k] = 0.0; v[2 * d + k] = 0.0; }
+}
+
+// One 64-lane workgroup (one wave) per walk: state in, ns_slice_advance, state out, the next query and whether there is one.
+__global__ void __launch_bounds__(64)
+ns_slice_step_kernel(unsigned long long seed, long long call, int walk_id0, int d, int slices, const double* __restrict__ chol,
+                     double scale, double logl_star, char* __restrict__ state, const double* __restrict__ logl_query,
+                     double* __restrict__ u_query, int* __restrict__ active) {
+    __shared__ double C_s[ALABI_MAX_DIM * ALABI_MAX_DIM];
+    __shared__ double u_s[ALABI_MAX_DIM], a_s[ALABI_MAX_DIM], q_s[ALABI_MAX_DIM];
+    __shared__ NsSliceState st_s;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    char* base = state + (size_t)b * ns_slice_stride(d);
+    NsSliceState* g = reinterpret_cast<NsSliceState*>(base);
+    double* v = reinterpret_cast<double*>(base + sizeof(NsSliceState));
+    for (int i = tid; i < d * d; i += 64) {
+        const int r = i / d, c = i % d;
+        C_s[r * ALABI_MAX_DIM + c] = c <= r ? chol[i] : 0.0;
+    }
+    if (tid < d) { u_s[tid] = v[tid]; a_s[tid] = v[d + tid]; q_s[tid] = v[2 * d + tid]; }
+    if (tid == 0) st_s = *g;
+    __syncthreads();
+    const double lp = st_s.pending ? logl_query[b] : 0.0;
+    const int query = ns_slice_advance(&st_s, u_s, a_s, q_s, C_s, ALABI_MAX_DIM, seed, call, (uint32_t)(walk_id0 + b), d, slices, scale,
+                                       logl_star, tid, lp);
+    __syncthreads();
+    if (tid < d) { v[tid] = u_s[tid]; v[d + tid] = a_s[tid]; v[2 * d + tid] = q_s[tid]; u_query[(size_t)b * d + tid] = q_s[tid]; }
+    if (tid == 0) { *g = st_s; active[b] = query; }
+}
+
+__global__ void __launch_bounds__(256)
+ns_slice_end_kernel(int K, int d, const char* __restrict__ state, double* __restrict__ u_out, double* __restrict__ logl_out,
+                    int* __restrict__ counts) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= K) return;
+    const char* base = state + (size_t)b * ns_slice_stride(d);
+    const NsSliceState* st = reinterpret_cast<const NsSliceState*>(base);
+    const double* v = reinterpret_cast<const double*>(base + sizeof(NsSliceState));
+    for (int k = 0; k < d; ++k) u_out[(size_t)b * d + k] = v[k];
+    logl_out[b] = st->L;
+    if (counts) { counts[b] = st->nev; counts[K + b] = st->nexp; counts[2 * K + b] = st->ncon; counts[3 * K + b] = st->ncap; }
 }
 
 // TMAX: 1024 lanes for dimension buckets <= 16, 256 above (the register budget of xa[D] and the query), see ns_threads.
@@ -363,6 +574,76 @@ int alabi_ns_walk(alabi_ns* ns, long long call, int walk_id0, const double* u0, 
         ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type,
             hipLaunchKernelGGL((ns_walk_kernel<D, GENERIC, ns_tmax(D), true>), dim3(K), dim3(T), 0, s, a)));
     }
+    ALABI_LAUNCH_CHECK();
+    return ALABI_OK;
+}
+
+int alabi_ns_slice(alabi_ns* ns, long long call, int walk_id0, const double* u0, const double* logl0, int K, double logl_star,
+                   const double* chol, double scale, int slices, double* u_out, double* logl_out, int* counts, void* stream) {
+    if (!ns || K < 0 || slices < 0 || slices >= 0x7FFFFFFF || walk_id0 < 0 || call < 0 || std::isnan(logl_star)) return ALABI_BAD_ARGUMENT;
+    if ((long long)walk_id0 + K > 0xFFFFFFFFLL) return ALABI_BAD_ARGUMENT;
+    if (K == 0) return ALABI_OK;
+    if (!u0 || !logl0 || !u_out || !logl_out || (slices > 0 && (!chol || !(scale > 0.0) || !std::isfinite(scale)))) return ALABI_BAD_ARGUMENT;
+    alabi_gp* gp = ns->gp;
+    if (!gp->computed || !gp->has_alpha) return ALABI_NOT_COMPUTED;
+    const hipStream_t s = ns_stream(stream);
+    const bool se = gp->kf.type == 0;
+    if (se) { const int st = ens_se_prepare(gp, s); if (st != ALABI_OK) return st; }
+    NsArgs a{};
+    a.Xsrc = se ? gp->Xc : gp->Xt; a.Asrc = se ? gp->ens_h : gp->alpha; a.centre = gp->xa_centre;
+    a.Npad = gp->Npad; a.kf = gp->kf;
+    a.amp = ns->lp_scale * std::exp(gp->log_amp); a.mean = std::fma(ns->lp_scale, gp->mean, ns->lp_shift); a.ymap = ns->ymap;
+    a.lo = ns->lo; a.width = ns->width; a.inv_len = gp->inv_len;
+    a.u0 = u0; a.logl0 = logl0; a.chol = chol; a.u_out = u_out; a.logl_out = logl_out; a.n_acc = counts;
+    a.seed = ns->seed; a.call = call; a.walk_id0 = walk_id0; a.K = K; a.d = ns->d; a.walks = slices;
+    a.logl_star = logl_star; a.scale = scale;
+    const int db = dim_bucket(ns->d), T = ns_threads(gp, db);
+    ns->last_path = (gp->Npad / 2 <= T) ? 1 : 2;
+    if (ns->last_path == 1) {
+        ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type,
+            hipLaunchKernelGGL((ns_slice_kernel<D, GENERIC, ns_tmax(D), false>), dim3(K), dim3(T), 0, s, a)));
+    } else {
+        ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type,
+            hipLaunchKernelGGL((ns_slice_kernel<D, GENERIC, ns_tmax(D), true>), dim3(K), dim3(T), 0, s, a)));
+    }
+    ALABI_LAUNCH_CHECK();
+    return ALABI_OK;
+}
+
+int alabi_ns_slice_state_bytes(alabi_ns* ns, int K, long long* bytes) {
+    if (!ns || !bytes || K < 0) return ALABI_BAD_ARGUMENT;
+    *bytes = (long long)K * (long long)ns_slice_stride(ns->d);
+    return ALABI_OK;
+}
+
+int alabi_ns_slice_begin(alabi_ns* ns, const double* u0, const double* logl0, int K, void* state, void* stream) {
+    if (!ns || K < 0) return ALABI_BAD_ARGUMENT;
+    if (K == 0) return ALABI_OK;
+    if (!u0 || !logl0 || !state) return ALABI_BAD_ARGUMENT;
+    hipLaunchKernelGGL(ns_slice_begin_kernel, dim3((K + 255) / 256), dim3(256), 0, ns_stream(stream), K, ns->d, u0, logl0,
+                       static_cast<char*>(state));
+    ALABI_LAUNCH_CHECK();
+    return ALABI_OK;
+}
+
+int alabi_ns_slice_step(alabi_ns* ns, long long call, int walk_id0, int K, double logl_star, const double* chol, double scale,
+                        int slices, void* state, const double* logl_query, double* u_query, int* active, void* stream) {
+    if (!ns || K < 0 || slices < 0 || slices >= 0x7FFFFFFF || walk_id0 < 0 || call < 0 || std::isnan(logl_star)) return ALABI_BAD_ARGUMENT;
+    if ((long long)walk_id0 + K > 0xFFFFFFFFLL) return ALABI_BAD_ARGUMENT;
+    if (K == 0) return ALABI_OK;
+    if (!state || !logl_query || !u_query || !active || !chol || !(scale > 0.0) || !std::isfinite(scale)) return ALABI_BAD_ARGUMENT;
+    hipLaunchKernelGGL(ns_slice_step_kernel, dim3(K), dim3(64), 0, ns_stream(stream), ns->seed, call, walk_id0, ns->d, slices, chol,
+                       scale, logl_star, static_cast<char*>(state), logl_query, u_query, active);
+    ALABI_LAUNCH_CHECK();
+    return ALABI_OK;
+}
+
+int alabi_ns_slice_end(alabi_ns* ns, int K, const void* state, double* u_out, double* logl_out, int* counts, void* stream) {
+    if (!ns || K < 0) return ALABI_BAD_ARGUMENT;
+    if (K == 0) return ALABI_OK;
+    if (!state || !u_out || !logl_out) return ALABI_BAD_ARGUMENT;
+    hipLaunchKernelGGL(ns_slice_end_kernel, dim3((K + 255) / 256), dim3(256), 0, ns_stream(stream), K, ns->d,
+                       static_cast<const char*>(state), u_out, logl_out, counts);
     ALABI_LAUNCH_CHECK();
     return ALABI_OK;
 }

@@ -2,8 +2,8 @@
 
 The reference drives dynesty's ``NestedSampler`` / ``DynamicNestedSampler`` (alabi/core.py:2417-2787) for the Bayesian
 evidence log Z.  Here the nested-sampling bookkeeping runs on the host in NumPy and the likelihood work -- many independent
-constrained random walks, one GP mean per step -- runs in ``ns_walk_kernel`` (alabi_amd/csrc/nested.hip) through a *walk
-backend*.  The product's only backend is ``GPUWalkBackend``; there is no CPU fallback (tests may pass their own).
+constrained random walks, one GP mean per step -- runs in ``ns_walk_kernel`` / ``ns_slice_kernel`` (alabi_amd/csrc/nested.hip)
+through a *walk backend*.  The product's only backend is ``GPUWalkBackend``; there is no CPU fallback (tests may pass their own).
 
 Algorithm (static; all in the unit cube u in [0,1]^d, the prior being uniform there)
   * Start.  ``nlive`` points uniform in the cube (device Philox), logL of each.
@@ -20,6 +20,14 @@ Algorithm (static; all in the unit cube u in [0,1]^d, the prior being uniform th
   * Scale rule.  After every iteration, with acc = accepted steps / (K walks), scale <- scale exp((acc - 0.5) / (0.5 d)),
     clipped to [1e-4, 10]; the start value is 1 (dynesty's).  Acceptance above 1/2 widens the step, below narrows it, and the
     1/d damping keeps the change per iteration small in high dimension.
+  * Slice move (``sample="rslice"``, dynesty's random-direction slice sampling; the move to use above d = 20, where 25
+    Metropolis steps no longer decorrelate a walk from its start and log Z comes out high by several logzerr).  One walk =
+    ``slices`` slice updates (default 3 (3 + d), see NOTES.md for the calibration).  Each: a direction a = scale C z / |z|;
+    an interval [t_l, t_r] = [-r, 1 - r], r ~ U(0,1), along u + t a; stepping out by 1 on each side while the end lies inside
+    the cube with logL > L* (one *expansion* each); then t ~ U(t_l, t_r) until the point lies inside the cube with logL > L*,
+    every failure pulling the end on its side in to t (one *contraction*).  A slice that has contracted 64 times ends where
+    it started and its walk is counted in ``n_stuck``.  Scale rule: with E expansions and Cn contractions over the K walks,
+    scale <- scale E / (2 max(Cn, 1)) (halved when E = 0), clipped to [1e-4, 10] (dynesty's).
   * Stop.  log(1 + exp(max logL_live + log X - log Z)) < ``dlogz`` (default 0.5), or ``maxiter`` dead points, or ``maxcall``
     likelihood evaluations (in-cube proposals; the start points count too).
   * Finish (dynesty's add_live).  The remaining live points are appended in ascending logL with n = n_live - j, j = 0..n_live-1.
@@ -39,8 +47,8 @@ Dynamic mode (the reference's default; ``wt_kwargs`` / ``stop_kwargs`` with pfra
   3. Stop when the Kish ESS (sum w)^2 / sum w^2 >= ``n_effective`` (default 10000) or after ``maxbatch`` batches.
   4. dynesty's bootstrap stopping rule is not built.
 
-Not built (listed in DESIGN.md "Differences"): bounding ellipsoids (``bound`` has no effect), ``unif`` / ``slice`` sampling,
-the bootstrap stop, other weight / stop fractions than pfrac = 1.
+Not built (listed in DESIGN.md "Differences"): bounding ellipsoids (``bound`` has no effect), ``unif`` / axis-aligned ``slice``
+/ ``hslice`` sampling, the bootstrap stop, other weight / stop fractions than pfrac = 1.
 """
 from __future__ import annotations
 
@@ -56,15 +64,29 @@ from . import _lib
 from .gp import _dev
 
 __all__ = ["NestedSampler", "NestedResults", "GPUWalkBackend", "PickleCheckpoint", "resample_equal", "compute_integrals",
-           "merge_runs", "update_scale"]
+           "merge_runs", "update_scale", "update_scale_slice", "default_slices"]
 
 MAXFRAC = 0.8
 SCALE_MIN, SCALE_MAX = 1e-4, 10.0
+SLICES_MULT = 3       # calibrated on a 24-D Gaussian (NOTES.md "Nested sampling")
 
 
 def update_scale(scale, acc, ndim):
     """The walk scale after an iteration with acceptance fraction ``acc`` (target 0.5)."""
     return float(min(max(scale * math.exp((acc - 0.5) / (0.5 * ndim)), SCALE_MIN), SCALE_MAX))
+
+
+def update_scale_slice(scale, n_expand, n_contract):
+    """The slice scale after an iteration with ``n_expand`` expansions and ``n_contract`` contractions over all its walks:
+    as many expansions as two contractions leaves it unchanged, no expansion at all halves it."""
+    n_expand, n_contract = int(n_expand), int(n_contract)
+    new = 0.5 * scale if n_expand == 0 else scale * n_expand / (2.0 * max(n_contract, 1))
+    return float(min(max(new, SCALE_MIN), SCALE_MAX))
+
+
+def default_slices(ndim):
+    """Slice updates per walk of ``sample="rslice"``: SLICES_MULT times dynesty's 3 + ndim."""
+    return SLICES_MULT * (3 + int(ndim))
 
 
 def compute_integrals(logl, samples_n):
@@ -134,7 +156,8 @@ def merge_runs(runs):
 class NestedResults:
     """dynesty's Results fields: samples (theta), samples_u, logl, logwt, logvol, logz, logzerr, information, samples_n,
     niter (dead points of the loops, add_live excluded), ncall (likelihood evaluations), eff (100 niter / ncall), nlive,
-    status ("converged", "maxiter", "maxcall", "plateau", "n_effective", "maxbatch"), n_stuck (walks without an accept)."""
+    status ("converged", "maxiter", "maxcall", "plateau", "n_effective", "maxbatch"), n_stuck (walks without an accept;
+    rslice: walks with a slice that hit the contraction cap)."""
 
     _FIELDS = ("samples", "samples_u", "logl", "logwt", "logvol", "logz", "logzerr", "information", "samples_n", "niter",
                "ncall", "eff", "nlive", "status", "n_stuck", "nbatch")
@@ -175,10 +198,13 @@ class NestedSampler:
     """Static (``dynamic=False``) or dynamic nested sampler over a walk backend.
 
     backend: ``ndim``, ``prior(call, n) -> (u, logl)``, ``walk(call, u0, logl0, logl_star, chol, scale, walks) ->
-    (u, logl, n_accept, n_eval)``, ``theta(u) -> samples``.  ``seed`` seeds the host generator (start-point choice and
+    (u, logl, n_accept, n_eval)``, ``theta(u) -> samples``, and for ``sample="rslice"`` ``rslice(call, u0, logl0, logl_star,
+    chol, scale, slices) -> (u, logl, n_eval, n_expand, n_contract, n_capped)``.  ``sample``: "rwalk" (``walks`` Metropolis
+    steps) or "rslice" (``slices`` slice updates, default ``default_slices(ndim)``).  ``seed`` seeds the host generator
+    (start-point choice and
     resampling); the device draws are keyed by the backend's own seed and the call counter kept here."""
 
-    def __init__(self, backend, nlive, dynamic=False, walks=25, batch=None, seed=0):
+    def __init__(self, backend, nlive, dynamic=False, walks=25, batch=None, seed=0, sample="rwalk", slices=None):
         self.backend = backend
         self.ndim = int(backend.ndim)
         self.nlive = int(nlive)
@@ -186,6 +212,12 @@ class NestedSampler:
             raise ValueError("nlive must be >= 2")
         self.dynamic = bool(dynamic)
         self.walks = int(walks)
+        if sample not in ("rwalk", "rslice"):
+            raise ValueError("sample must be 'rwalk' or 'rslice'")
+        self.sample = sample
+        self.slices = default_slices(self.ndim) if slices is None else int(slices)
+        if self.slices < 0:
+            raise ValueError("slices must be >= 0")
         self.batch = int(math.ceil(self.nlive / 4)) if batch is None else int(batch)
         if not 1 <= self.batch < self.nlive:
             raise ValueError("batch must lie in [1, nlive)")
@@ -206,6 +238,13 @@ class NestedSampler:
 
     # ------------------------------------------------------------------ one static loop
     def _walk(self, u0, l0, lstar, chol):
+        if self.sample == "rslice":
+            u, logl, nev, nexp, ncon, ncap = self.backend.rslice(self.call, u0, l0, lstar, chol, self.scale, self.slices)
+            self.call += 1
+            self.ncall += int(np.sum(nev))
+            self.n_stuck += int(np.count_nonzero(ncap))
+            self.scale = update_scale_slice(self.scale, np.sum(nexp), np.sum(ncon))
+            return np.asarray(u), np.asarray(logl)
         u, logl, nacc, nev = self.backend.walk(self.call, u0, l0, lstar, chol, self.scale, self.walks)
         self.call += 1
         self.ncall += int(np.sum(nev))
@@ -358,7 +397,8 @@ class GPUWalkBackend:
     Fused (``host_loglike=None``): logL(u) = map(scale * GP mean(lo + u (hi - lo)) + shift) inside ``ns_walk_kernel``;
     ``bounds`` [d,2] in the GP's scaled coordinates, ``logp_affine=(scale, shift)``, ``logp_map`` None / "nlog" / "log".
     Split: ``host_loglike(u [m,d]) -> [m]`` is called between alabi_ns_propose and alabi_ns_accept for the in-cube proposals
-    of every step.  ``to_theta(u [m,d]) -> [m,d]`` maps cube points to the samples reported."""
+    of every step.  ``to_theta(u [m,d]) -> [m,d]`` maps cube points to the samples reported.
+    ``rslice`` is the slice move on the same two paths: ``ns_slice_kernel``, or alabi_ns_slice_step around ``host_loglike``."""
 
     def __init__(self, gp, y, bounds, seed, to_theta, logp_affine=(1.0, 0.0), logp_map=None, host_loglike=None):
         self.gp, self._y = gp, y
@@ -456,3 +496,42 @@ class GPUWalkBackend:
                                                _lib.ptr(nacc), stream), "alabi_ns_accept")
         n = nacc.cpu().numpy()
         return u.cpu().numpy(), logl.cpu().numpy(), n[:K], n[K:]
+
+    def rslice(self, call, u0, logl0, logl_star, chol, scale, slices, walk_id0=0):
+        """``slices`` random-direction slice updates of every walk: (u, logl, n_eval, n_expand, n_contract, n_capped), the
+        last four per walk (in-cube likelihood evaluations, expansions, contractions, slices that hit the contraction cap)."""
+        ns, lib, dev, stream = self._ensure(), _lib.lib(), _dev(), _lib.current_stream()
+        K = int(np.asarray(u0).shape[0])
+        u = torch.as_tensor(np.ascontiguousarray(u0, dtype=np.float64), device=dev).clone()
+        logl = torch.as_tensor(np.ascontiguousarray(logl0, dtype=np.float64), device=dev).clone()
+        ch = torch.as_tensor(np.ascontiguousarray(chol, dtype=np.float64), device=dev)
+        counts = torch.zeros(4 * K, dtype=torch.int32, device=dev)
+        if self.host_loglike is None:
+            _lib.check(lib.alabi_ns_slice(ns, int(call), int(walk_id0), _lib.ptr(u), _lib.ptr(logl), K, float(logl_star),
+                                          _lib.ptr(ch), float(scale), int(slices), _lib.ptr(u), _lib.ptr(logl), _lib.ptr(counts),
+                                          stream), "alabi_ns_slice")
+        elif K > 0 and int(slices) > 0:
+            nbytes = C.c_longlong(0)
+            _lib.check(lib.alabi_ns_slice_state_bytes(ns, K, C.byref(nbytes)), "alabi_ns_slice_state_bytes")
+            state = torch.empty((int(nbytes.value) + 7) // 8, dtype=torch.float64, device=dev)
+            _lib.check(lib.alabi_ns_slice_begin(ns, _lib.ptr(u), _lib.ptr(logl), K, _lib.ptr(state), stream),
+                       "alabi_ns_slice_begin")
+            uq = torch.empty_like(u)
+            active = torch.zeros(K, dtype=torch.int32, device=dev)
+            lq = torch.zeros(K, dtype=torch.float64, device=dev)
+            while True:
+                _lib.check(lib.alabi_ns_slice_step(ns, int(call), int(walk_id0), K, float(logl_star), _lib.ptr(ch), float(scale),
+                                                   int(slices), _lib.ptr(state), _lib.ptr(lq), _lib.ptr(uq), _lib.ptr(active),
+                                                   stream),
+                           "alabi_ns_slice_step")
+                on = active.cpu().numpy() != 0
+                if not on.any():
+                    break
+                lh = np.zeros(K)
+                lh[on] = np.asarray(self.host_loglike(uq.cpu().numpy()[on]), dtype=np.float64).reshape(-1)
+                self.host_calls += int(on.sum())
+                lq = torch.as_tensor(lh, device=dev)
+            _lib.check(lib.alabi_ns_slice_end(ns, K, _lib.ptr(state), _lib.ptr(u), _lib.ptr(logl), _lib.ptr(counts), stream),
+                       "alabi_ns_slice_end")
+        n = counts.cpu().numpy()
+        return u.cpu().numpy(), logl.cpu().numpy(), n[:K], n[K:2 * K], n[2 * K:3 * K], n[3 * K:]

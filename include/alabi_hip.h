@@ -340,8 +340,29 @@ int alabi_ns_propose(alabi_ns* ns, long long call, int walk_id0, const double* u
                      double scale, double* u_prop, void* stream);
 int alabi_ns_accept(alabi_ns* ns, int K, const double* u_prop, const double* logl_prop, double logl_star, double* u_cur,
                     double* logl_cur, int* n_accept, void* stream);
-/* Path of the last alabi_ns_walk: 1 training set resident in registers, 2 tiled (point pairs beyond the block re-read
- * from L2 every step). */
+/* Random-direction slice sampling (dynesty's sample="rslice"): K independent walks of `slices` slice updates from u0 [K,d] with
+ * logL logl0 [K] (required).  Slice s: axis a = scale * chol z / |z|; interval [t_l, t_r] = [-r, 1 - r], r ~ U(0,1), along
+ * u + t a; stepping out by 1 on either side while the end lies strictly inside the cube with logL > logl_star (an expansion
+ * each; a point outside the cube ends the stepping without an evaluation); then t ~ U(t_l, t_r) until the point lies inside the
+ * cube with logL > logl_star, every failure moving the end on its side to t (a contraction).  After 64 contractions the slice
+ * ends where it started (a capped slice).  Writes u_out [K,d] (may alias u0), logl_out [K] and, if counts is not NULL, int32
+ * [4K]: likelihood evaluations (in-cube points), expansions, contractions, capped slices per walk.  slices < 2^31 - 1;
+ * slices = 0 returns the start bit for bit.  Draw keys: nested.hip. */
+int alabi_ns_slice(alabi_ns* ns, long long call, int walk_id0, const double* u0, const double* logl0, int K, double logl_star,
+                   const double* chol, double scale, int slices, double* u_out, double* logl_out, int* counts, void* stream);
+/* The same move split around a host likelihood, with the draws and arithmetic of alabi_ns_slice.  `state` is a device buffer of
+ * alabi_ns_slice_state_bytes(K) bytes (8-byte aligned) that alabi_ns_slice_begin fills from u0 / logl0.  alabi_ns_slice_step
+ * consumes logl_query [K] (read for the walks whose previous query is pending), advances every walk to its next query strictly
+ * inside the cube, writes it to u_query [K,d] and sets active [K] to 1, or to 0 for a walk that has ended; the caller
+ * evaluates the active walks' queries and calls again until no walk is active.  alabi_ns_slice_end writes the outputs of
+ * alabi_ns_slice. */
+int alabi_ns_slice_state_bytes(alabi_ns* ns, int K, long long* bytes /* host */);
+int alabi_ns_slice_begin(alabi_ns* ns, const double* u0, const double* logl0, int K, void* state, void* stream);
+int alabi_ns_slice_step(alabi_ns* ns, long long call, int walk_id0, int K, double logl_star, const double* chol, double scale,
+                        int slices, void* state, const double* logl_query, double* u_query, int* active, void* stream);
+int alabi_ns_slice_end(alabi_ns* ns, int K, const void* state, double* u_out, double* logl_out, int* counts, void* stream);
+/* Path of the last alabi_ns_walk / alabi_ns_slice: 1 training set resident in registers, 2 tiled (point pairs beyond the block
+ * re-read from L2 every step). */
 int alabi_ns_last_path(alabi_ns* ns, int* path /* host */);
 
 /* Gaussian kernel density estimate: scipy.stats.gaussian_kde(dataset, bw_method, weights) as built and evaluated by the

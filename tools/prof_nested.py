@@ -4,6 +4,8 @@ reference-shaped CPU leg (one oracle predict per likelihood call, as dynesty cal
 
     python tools/prof_nested.py            # everything, one JSON line per measurement
     python tools/prof_nested.py walk       # only the walk kernel (the part to run under rocprofv3 --kernel-trace --stats)
+    python tools/prof_nested.py slice      # ns_slice_kernel beside ns_walk_kernel (alternating, same process) at d = 10 and 24,
+                                           # and run_dynesty at C3 size with sample="rwalk" / "rslice"
 """
 import json
 import math
@@ -80,6 +82,100 @@ def walk_kernel():
     be.close()
 
 
+def slice_kernel(N, d, rounds=3, reps=10):
+    """ns_slice_kernel and ns_walk_kernel in turn, `rounds` times each per K: the spread of the walk figure over the rounds is the
+    margin for comparing the slice kernel's time per evaluation of its longest walk (the dependent chain) with the walk's per step."""
+    from alabi_amd import HipGP, _lib
+    from alabi_amd.nested import GPUWalkBackend, default_slices
+    walks, slices = 25, default_slices(d)
+    X, y, h = make_problem(N, d, 0)
+    g = HipGP(d, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"])
+    g.compute(X)
+    box = np.array([[-3.0, 3.0]] * d)
+    be = GPUWalkBackend(g, y, box, seed=1, to_theta=lambda u: u)
+    u, l = be.prior(0, 4096)
+    lstar = float(np.quantile(l, 0.5))
+    keep = np.flatnonzero(l > lstar)
+    chol = np.linalg.cholesky(np.cov(u.T))
+    lib, ns, st = _lib.lib(), be._ensure(), _lib.current_stream()
+    for K in (64, 256, 1024):
+        idx = keep[np.arange(K) % len(keep)]
+        u0 = torch.as_tensor(u[idx], device="cuda")
+        l0 = torch.as_tensor(l[idx], device="cuda")
+        ch = torch.as_tensor(chol, device="cuda")
+        uo, lo = torch.empty_like(u0), torch.empty_like(l0)
+        cnt = torch.zeros(4 * K, dtype=torch.int32, device="cuda")
+
+        def walk(call):
+            _lib.check(lib.alabi_ns_walk(ns, call, 0, _lib.ptr(u0), _lib.ptr(l0), K, lstar, _lib.ptr(ch), 0.5, walks,
+                                         _lib.ptr(uo), _lib.ptr(lo), _lib.ptr(cnt), st), "alabi_ns_walk")
+
+        def slc(call, scale=1.0):
+            _lib.check(lib.alabi_ns_slice(ns, call, 0, _lib.ptr(u0), _lib.ptr(l0), K, lstar, _lib.ptr(ch), scale, slices,
+                                          _lib.ptr(uo), _lib.ptr(lo), _lib.ptr(cnt), st), "alabi_ns_slice")
+        for fn in (walk, slc):                       # warm-up
+            fn(1)
+            fn(2)
+        torch.cuda.synchronize()
+        for rnd in range(rounds):
+            for name, fn in (("walk", walk), ("slice", slc)):
+                evals, longest, dt = 0, 0, 0.0
+                for i in range(reps):                # the same calls in every round: the same work, so the rounds compare
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn(100 + i)
+                    torch.cuda.synchronize()
+                    dt += time.perf_counter() - t0
+                    c = cnt.cpu().numpy()
+                    ev = c[K:2 * K] if name == "walk" else c[:K]
+                    evals += int(ev.sum())
+                    longest += int(ev.max()) if name == "slice" else walks
+                us = dt / reps * 1e6
+                emit(what="ns_" + name, N=N, d=d, K=K, round=rnd, path=be.last_path(), us_per_launch=us,
+                     steps_or_slices=walks if name == "walk" else slices, evals_per_launch=evals / reps,
+                     longest_chain=longest / reps, us_per_link_of_longest_chain=us * reps / longest,
+                     mean_over_max_evals=(evals / K) / longest if name == "slice" else None,
+                     evals_per_s=evals / dt)
+        if K == 64:
+            # the same launch at other scales: short axes give many stepping-out links per slice, long ones many shrink draws, so
+            # the launch time over (slices, links of the longest walk) separates the cost of setting up a slice from that of a link
+            for scale in (0.1, 0.3, 3.0):
+                slc(1, scale)
+                torch.cuda.synchronize()
+                dt, rows = 0.0, []
+                for i in range(reps):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    slc(100 + i, scale)
+                    torch.cuda.synchronize()
+                    dt += time.perf_counter() - t0
+                    rows.append(cnt.cpu().numpy().reshape(4, K).copy())
+                c = np.mean(rows, axis=0)
+                emit(what="ns_slice_scale_sweep", N=N, d=d, K=K, scale=scale, slices=slices, us_per_launch=dt / reps * 1e6,
+                     longest_chain=float(np.mean([r[0].max() for r in rows])), evals_per_walk=float(c[0].mean()),
+                     expansions_per_walk=float(c[1].mean()), contractions_per_walk=float(c[2].mean()), capped=float(c[3].sum()))
+    be.close()
+
+
+def end_to_end_moves(d=10, ntrain=2000, nlive=500):
+    import tempfile
+
+    from alabi_amd import SurrogateModel
+    sm = SurrogateModel(lnlike_fn=_gauss(d, 0), bounds=[(-2.0, 2.0)] * d, savedir=tempfile.mkdtemp(), verbose=False,
+                        random_state=0, cache=False)
+    sm.init_samples(ntrain=ntrain)
+    sm.init_gp(hyperopt_method="ml", gp_nopt=1)
+    sm.run_dynesty(mode="static", sampler_kwargs={"nlive": 100, "seed": 1}, run_kwargs={"maxiter": 500}, min_ess=0)   # warm-up
+    for sample in ("rwalk", "rslice", "rwalk", "rslice"):
+        t0 = time.perf_counter()
+        sm.run_dynesty(mode="static", sampler_kwargs={"nlive": nlive, "seed": 2, "sample": sample}, min_ess=0)
+        wall = time.perf_counter() - t0
+        r = sm.dynesty_results
+        emit(what="run_dynesty", config="C3", sample=sample, d=d, N=ntrain, nlive=nlive, wall_s=wall, niter=int(r.niter),
+             ncall=int(r.ncall), evals_per_dead_point=r.ncall / r.niter, evals_per_s=r.ncall / wall, logz=float(r.logz[-1]),
+             logzerr=float(r.logzerr[-1]), status=r.status, n_stuck=int(r.n_stuck), scale=float(sm.dynesty_sampler.scale))
+
+
 def _gauss(d, seed):
     rng = np.random.RandomState(seed)
     A = rng.randn(d, d)
@@ -126,6 +222,10 @@ if __name__ == "__main__":
     torch.cuda.set_device(0)
     if what in ("all", "walk"):
         walk_kernel()
+    if what == "slice":
+        slice_kernel(2000, 10)
+        slice_kernel(2000, 24)
+        end_to_end_moves()
     if what in ("all", "e2e"):
         end_to_end("tutorial", 2, 200, 100, "dynamic", (-4.0, 4.0))
         end_to_end("C3", 10, 2000, 500, "static", (-2.0, 2.0))
