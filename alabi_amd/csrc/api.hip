@@ -487,6 +487,45 @@ static void free_draws(DrawBuffers& b) {
     b = DrawBuffers{};
 }
 
+static hipError_t alloc_draws(DrawBuffers& b, size_t n) {
+    hipError_t err = hipSuccess;
+    if (err == hipSuccess) err = hipMalloc(&b.order, n * sizeof(int));
+    if (err == hipSuccess) err = hipMalloc(&b.cw, n * sizeof(int));
+    if (err == hipSuccess) err = hipMalloc(&b.zz, n * sizeof(double));
+    if (err == hipSuccess) err = hipMalloc(&b.lnfac, n * sizeof(double));
+    if (err == hipSuccess) err = hipMalloc(&b.lnu, n * sizeof(double));
+    if (err == hipSuccess) err = hipMalloc(&b.partner, n * sizeof(int));
+    if (err == hipSuccess) err = hipMalloc(&b.u_z, n * sizeof(double));
+    if (err == hipSuccess) err = hipMalloc(&b.u_acc, n * sizeof(double));
+    if (err == hipSuccess) err = hipMalloc(&b.packed, 4 * n * sizeof(unsigned long long));
+    if (err == hipSuccess) err = hipMalloc(&b.pos_of, n * sizeof(int));
+    if (err == hipSuccess) err = hipMalloc(&b.link, 2 * n * sizeof(unsigned long long));
+    return err;
+}
+
+// Second set of draw buffers, side stream and events for drawing one chunk ahead; created on the first multi-chunk stream call.
+// Not available (single buffer, draws on the main stream) when the set would be large or anything fails to allocate.
+static bool ens_draw_ahead_ready(alabi_ens* e) {
+    if (e->draws2_state != 0) return e->draws2_state > 0;
+    e->draws2_state = -1;
+    const size_t n = (size_t)e->chunk_cap * e->W * e->E;
+    if (n > ((size_t)1 << 20)) return false;                       // 104 bytes per record: at most 109 MB
+    bool ok = alloc_draws(e->draws2, n) == hipSuccess;
+    ok = ok && hipStreamCreateWithFlags(&e->side_stream, hipStreamNonBlocking) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&e->ev_free, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&e->ev_drawn, hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        free_draws(e->draws2);
+        if (e->side_stream) { (void)hipStreamDestroy(e->side_stream); e->side_stream = nullptr; }
+        if (e->ev_free) { (void)hipEventDestroy(e->ev_free); e->ev_free = nullptr; }
+        if (e->ev_drawn) { (void)hipEventDestroy(e->ev_drawn); e->ev_drawn = nullptr; }
+        return false;
+    }
+    e->draws2_state = 1;
+    return true;
+}
+
 static DrawBuffers offset_draws(const DrawBuffers& b, size_t off) {
     DrawBuffers r = b;
     r.order += off; r.cw += off; r.zz += off; r.lnfac += off; r.lnu += off;
@@ -523,18 +562,7 @@ int alabi_ens_create(alabi_gp* gp, int W, int d, int n_ensembles, const double* 
     e->chunk_cap = (int)cap;
     const size_t n = (size_t)e->chunk_cap * WT;
     DrawBuffers& b = e->draws;
-    hipError_t err = hipSuccess;
-    if (err == hipSuccess) err = hipMalloc(&b.order, n * sizeof(int));
-    if (err == hipSuccess) err = hipMalloc(&b.cw, n * sizeof(int));
-    if (err == hipSuccess) err = hipMalloc(&b.zz, n * sizeof(double));
-    if (err == hipSuccess) err = hipMalloc(&b.lnfac, n * sizeof(double));
-    if (err == hipSuccess) err = hipMalloc(&b.lnu, n * sizeof(double));
-    if (err == hipSuccess) err = hipMalloc(&b.partner, n * sizeof(int));
-    if (err == hipSuccess) err = hipMalloc(&b.u_z, n * sizeof(double));
-    if (err == hipSuccess) err = hipMalloc(&b.u_acc, n * sizeof(double));
-    if (err == hipSuccess) err = hipMalloc(&b.packed, 4 * n * sizeof(unsigned long long));
-    if (err == hipSuccess) err = hipMalloc(&b.pos_of, n * sizeof(int));
-    if (err == hipSuccess) err = hipMalloc(&b.link, 2 * n * sizeof(unsigned long long));
+    hipError_t err = alloc_draws(b, n);
     if (err == hipSuccess) err = hipMalloc(&e->run_state, 4 * sizeof(long long));
     if (err == hipSuccess) err = hipMalloc(&e->consts, 5 * ALABI_MAX_DIM * sizeof(double));
     // persistent dataflow path: one workgroup per list position, all co-resident (at most one per CU)
@@ -566,6 +594,10 @@ int alabi_ens_destroy(alabi_ens* e) {
     if (!e) return ALABI_OK;
     if (e->graph_exec) (void)hipGraphExecDestroy(e->graph_exec);
     free_draws(e->draws);
+    free_draws(e->draws2);
+    if (e->side_stream) (void)hipStreamDestroy(e->side_stream);
+    if (e->ev_free) (void)hipEventDestroy(e->ev_free);
+    if (e->ev_drawn) (void)hipEventDestroy(e->ev_drawn);
     if (e->run_state) (void)hipFree(e->run_state);
     if (e->consts) (void)hipFree(e->consts);
     if (e->hist) (void)hipFree(e->hist);
@@ -718,7 +750,6 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
     hipStream_t s = as_stream(stream);
     int st;
     if ((st = sync_consts(e, s)) != ALABI_OK) return st;
-    if ((st = set_run_state(e, step0, 0, s)) != ALABI_OK) return st;
     // Persistent dataflow path: training set pinned in registers (Npad <= 2048: 256 compute lanes x up to 4 point pairs), one
     // workgroup per list position.  It synchronises at the end to read the time-out flag.
     e->last_path = 0;
@@ -735,22 +766,58 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
                            ens_group_buffers(e, s);
     if (e->stream_ok && s != nullptr && (can_stream || use_group)) {
         e->last_path = use_group ? 3 : 1;
+        // ens_stream_kernel's chunks take the step counters by value and their epilogue leaves run_state as the other paths
+        // would (no upload, no host synchronisation in front of the first launch); the history is trusted to hold the
+        // sentinel only when this handle's last use of it was a stream call that ended without a time-out
+        const int need = (int)(nsteps < e->chunk_cap ? nsteps : e->chunk_cap);   // rows 1..need are polled by this call
+        const int clean_rows = e->hist_clean;
+        e->hist_clean = 0;
+        if (use_group && (st = set_run_state(e, step0, 0, s)) != ALABI_OK) return st;
         ALABI_HIP_CHECK(hipMemsetAsync(e->err, 0, sizeof(int), s));
         long long remaining = nsteps;
+        // The draws depend on nothing but the step counter: in a call of several chunks those of the next chunk are made on the
+        // side stream while this chunk's persistent kernel runs (it occupies half of the CUs), into the buffer set the previous
+        // chunk has released.
+        const bool two_sets = !use_group && nsteps > e->chunk_cap && ens_draw_ahead_ready(e);
+        bool ahead_issued = false;
         while (remaining > 0) {
             const int K = (int)(remaining < e->chunk_cap ? remaining : e->chunk_cap);
-            if ((st = launch_ens_draw(e, K, a, s)) != ALABI_OK) return st;
-            if (use_group) st = launch_ens_group(e, coords, logp, K, thin_by, chain, chain_logp, n_accept, s);
-            else st = launch_ens_stream(e, coords, logp, K, thin_by, chain, chain_logp, n_accept, s);
-            if (st != ALABI_OK) return st;
-            if ((st = launch_ens_advance(e, K, s)) != ALABI_OK) return st;
+            const long long done = nsteps - remaining;
+            if (use_group) {
+                if ((st = launch_ens_draw(e, K, a, s)) != ALABI_OK) return st;
+                if ((st = launch_ens_group(e, coords, logp, K, thin_by, chain, chain_logp, n_accept, s)) != ALABI_OK) return st;
+                if ((st = launch_ens_advance(e, K, s)) != ALABI_OK) return st;
+            } else {
+                const bool odd = two_sets && ((done / e->chunk_cap) & 1);
+                const bool ahead = two_sets && remaining > K;
+                const DrawBuffers& cur = odd ? e->draws2 : e->draws;
+                if (ahead_issued) ALABI_HIP_CHECK(hipStreamWaitEvent(s, e->ev_drawn, 0));
+                else if ((st = launch_ens_draw_at(e, cur, K, a, false, step0 + done, s)) != ALABI_OK) return st;
+                ahead_issued = false;
+                if (ahead) ALABI_HIP_CHECK(hipEventRecord(e->ev_free, s));   // everything that read the other buffer set is behind this point
+                if ((st = launch_ens_stream_kernel(e, cur, coords, logp, K, done == 0, (done == 0 && clean_rows < need) ? need : 0, s)) != ALABI_OK)
+                    return st;
+                if (ahead) {
+                    const long long rem2 = remaining - K;
+                    const int K2 = (int)(rem2 < e->chunk_cap ? rem2 : e->chunk_cap);
+                    ALABI_HIP_CHECK(hipStreamWaitEvent(e->side_stream, e->ev_free, 0));
+                    if ((st = launch_ens_draw_at(e, odd ? e->draws : e->draws2, K2, a, false, step0 + done + K, e->side_stream)) != ALABI_OK)
+                        return st;
+                    ALABI_HIP_CHECK(hipEventRecord(e->ev_drawn, e->side_stream));
+                    ahead_issued = true;
+                }
+                if ((st = launch_ens_stream_epilogue(e, coords, logp, K, thin_by, chain, chain_logp, n_accept, step0 + done + K, done, s)) != ALABI_OK)
+                    return st;
+            }
             remaining -= K;
         }
         int flag = 0;
         ALABI_HIP_CHECK(hipMemcpyAsync(&flag, e->err, sizeof(int), hipMemcpyDeviceToHost, s));
         ALABI_HIP_CHECK(hipStreamSynchronize(s));
+        e->hist_clean = (!use_group && !flag) ? (clean_rows > need ? clean_rows : need) : 0;
         return flag ? ALABI_TIMEOUT : ALABI_OK;
     }
+    if ((st = set_run_state(e, step0, 0, s)) != ALABI_OK) return st;
     HalfArgs h = base_args(e, coords, logp);
     h.chain = chain; h.chain_logp = chain_logp; h.n_accept = n_accept; h.thin_by = thin_by;
 

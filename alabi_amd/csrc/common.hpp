@@ -154,6 +154,13 @@ struct alabi_ens {
     // persistent dataflow path (ens_stream_kernel)
     unsigned long long* hist = nullptr;  // [(chunk_cap+1)][E*W][d+1] version history of every walker
     int* err = nullptr;                  // [1] spin time-out flag
+    // draws one chunk ahead (multi-chunk stream calls): second set of draw buffers, filled on a library-owned side stream while the
+    // previous chunk's persistent kernel runs (allocated on first use; draws2_state -1: not available, single buffer)
+    alabi::DrawBuffers draws2{};
+    hipStream_t side_stream = nullptr;
+    hipEvent_t ev_free = nullptr, ev_drawn = nullptr;   // main -> side: the buffer is no longer read; side -> main: the draws are there
+    int draws2_state = 0;
+    int hist_clean = 0;                  // rows 1..hist_clean hold the sentinel (left so by ens_hist_epilogue_kernel); rows beyond are filled before use
     int stream_grid = 0;                 // workgroups per ensemble of the persistent kernel
     int last_path = 0;                   // 1 persistent kernel (ens_stream_kernel), 3 group kernel (ens_group_kernel), 0 one launch per half step
     int stream_ok = 0;                   // eligible: training set fits the lanes' registers, one workgroup per CU
@@ -253,6 +260,7 @@ struct HalfArgs {
     double* sout = nullptr;
 };
 int launch_ens_draw(alabi_ens* e, int nsteps, double a, hipStream_t s);
+int launch_ens_draw_at(alabi_ens* e, const DrawBuffers& into, int nsteps, double a, bool from_state, long long step0, hipStream_t s);   // first step: run_state[0], or step0 by value
 int launch_ens_prep(alabi_ens* e, const int* order, int n0, const double* u_z, const int* partner,
                     const double* u_acc, double a, hipStream_t s);
 int launch_ens_half_args(alabi_ens* e, const HalfArgs& args, int nblocks, hipStream_t s);
@@ -266,8 +274,9 @@ int ens_sync_consts(alabi_ens* e, hipStream_t s);   // (inv_len, bounds, prior) 
 int alabi_ens_half_step_hist(alabi_ens* e, const double* coords, const double* logp, int t, int split, int part_begin, int part_end,
                              const double* shist, double* out, hipStream_t s);
 bool ens_stream_fits(const alabi_ens* e);
-int launch_ens_stream(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
-                      long long* n_accept, hipStream_t s);
+int launch_ens_stream_kernel(alabi_ens* e, const DrawBuffers& rec, double* coords, double* logp, int K, bool first, int fill_rows, hipStream_t s);
+int launch_ens_stream_epilogue(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
+                               long long* n_accept, long long step_next, long long done0, hipStream_t s);
 // ens_group.hip
 bool ens_group_fits(const alabi_ens* e);
 bool ens_group_buffers(alabi_ens* e, hipStream_t s);   // the group kernel's hand-off buffers exist (allocates on first use); false: take another path

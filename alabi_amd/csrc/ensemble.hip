@@ -60,14 +60,15 @@ __device__ inline void write_record(const DrawBuffers& b, size_t pos, int wid, i
 // LDS -- O(W log^2 W) compare-exchanges instead of the W^2 comparisons of the first version (0.21 ms per 1024-step chunk at
 // 1024 walkers, 0.62 ms at 2048: 4 % of the C4 run) -- then the two ordered lists by a prefix count over the labels.
 __global__ void __launch_bounds__(256)
-ens_draw_kernel(unsigned long long seed, const long long* __restrict__ run_state, int W, int Wp, int d, double a,
+ens_draw_kernel(unsigned long long seed, const long long* __restrict__ run_state, long long step_off, int W, int Wp, int d, double a,
                 DrawBuffers b) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint64_t* keys = reinterpret_cast<uint64_t*>(smem);                       // [Wp]; after the sort: label[W], olist[W]
     uint32_t* ids = reinterpret_cast<uint32_t*>(smem + (size_t)Wp * 8);       // [Wp]
     int* scan = reinterpret_cast<int*>(smem + (size_t)Wp * 12);               // [256]
     const int E = gridDim.y, e = blockIdx.y, tid = threadIdx.x;
-    const long long step = run_state[0] + blockIdx.x;
+    // first step of the chunk: read from run_state, or (run_state == nullptr) given by value so that the launch depends on no earlier kernel
+    const long long step = (run_state ? run_state[0] : 0) + step_off + blockIdx.x;
     const uint32_t s_lo = (uint32_t)step, s_hi = (uint32_t)((unsigned long long)step >> 32);
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     const size_t base = ((size_t)blockIdx.x * E + e) * W;
@@ -609,11 +610,7 @@ struct StreamArgs {
     const double* Xt;            // squared exponential: gp->Xc (inputs relative to their mean) ...
     const double* alpha;         // ... and gp->ens_h (se_pair_terms)
     const double* centre;        // mean of the scaled training inputs (squared exponential)
-    double* chain;
-    double* chain_logp;
-    unsigned long long* n_accept;
-    const long long* run_state;
-    int K, W, n0, d, Npad, thin_by, spin_limit, has_prior;
+    int K, W, n0, d, Npad, spin_limit, has_prior;
     double amp, mean, prior_const;
     KernelFn kf;
 };
@@ -642,32 +639,41 @@ __device__ inline double wave_partials_tree(const double* s, int nw) {
     return hi8 + lo8;
 }
 
-// blockDim.x = 64 + compute threads (a multiple of 64) + 64, three roles:
+// blockDim.x = TMAX = 64 + compute threads (a multiple of 64) + 64.  Three roles, ONE LOOP EACH over the workgroup's proposals;
+// the loops meet only at the two barriers of a proposal (A: the proposal is in LDS, B: the wave partials are in LDS), so no role
+// carries another role's registers or steps through another role's exec-mask ladders (round 5: the single loop body spilled 12
+// SGPRs into VGPR lanes and read several of them back between barrier B and the row store).
 //   wave 0          the ONLY wave on the hand-off chain: polls the two rows, forms the proposal, publishes it in LDS,
 //                   and after the reduction does the accept test and the one row store.  It computes no kernel values
 //                   and issues no other memory operation: gfx950 returns a wave's vector memory operations in issue
 //                   order (one vmcnt), so any ordinary load or store would put its latency in front of the next poll.
+//                   It takes the abort decision from its own register.
 //   waves 1..nwc    the training-set share of each lane lives in VGPRs for the whole launch; between the two barriers
-//                   of a proposal they evaluate the kernel sum and leave one partial per wave in LDS.
+//                   of a proposal they evaluate the kernel sum and leave one partial per wave in LDS.  The in-bounds flag
+//                   sits in the word behind the proposal (qs_s[par][D]): one batch of LDS reads brings both.
 //   last wave       fetches the packed proposal records (one 32-byte load) three proposals ahead into an LDS ring.
+// Waves other than wave 0 look at the abort word after barrier B, where they delay nobody.  Every role steps through the
+// proposals with the same next_item, so all waves execute the same number of barriers, early exit included.
 // The chain, the thinning and the acceptance counters are NOT written here: every version of every walker is a row of
-// `hist` (coords, logp, accepted), and ens_hist_chain_kernel copies it out after the launch at HBM speed.
+// `hist` (coords, logp, accepted), and ens_hist_epilogue_kernel copies it out after the launch at HBM speed.
 template <int D, int PPT, int TMAX, bool GENERIC>
 __global__ void __launch_bounds__(TMAX)
 ens_stream_kernel(StreamArgs p) {
     __shared__ __attribute__((aligned(16))) double scratch[2][16];   // wave partials, by proposal parity
     __shared__ unsigned long long rec_s[4][4];                       // proposal-record ring (last wave -> wave 0)
-    __shared__ __attribute__((aligned(16))) double qs_s[2][ALABI_MAX_DIM];   // scaled proposal, by proposal parity
+    __shared__ __attribute__((aligned(16))) double qs_s[2][ALABI_MAX_DIM];   // scaled proposal [0, D) and its in-bounds flag [D], by proposal parity
     __shared__ double consts_s[6][ALABI_MAX_DIM];                    // 1/length scale, lower, upper bound, prior mean, prior 1/std, centre
-    __shared__ int ctl_s[2][2];                                      // [parity][0] proposal inside the box; [0][1] abort
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int TC = blockDim.x - 128, nwc = TC >> 6;
+    __shared__ int abort_s;                                          // a bounded spin ran out: written by wave 0 before barrier A
+    static_assert(D < ALABI_MAX_DIM && TMAX >= 192 && TMAX % 64 == 0, "ens_stream_kernel: shape");
+    constexpr int TC = TMAX - 128, nwc = TC >> 6;                    // the host launches exactly TMAX threads
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);         // wave-uniform: the role branches are scalar
     const bool comm = wv == 0, service = wv == nwc + 1, compute = !comm && !service;
     const int b = blockIdx.x, e = blockIdx.y, E = gridDim.y;
     const int WT = p.W * E, row = p.d + 2;
 #ifdef ALABI_STREAM_PROF
     long long prof[5] = {0, 0, 0, 0, 0};
-    const long long prof_begin = clock64();
+    const long long prof_begin = wall_clock64();
 #endif
     // training-set share of this lane, resident for the whole launch (same lane -> point map as ens_half_kernel)
     const int half = p.Npad >> 1, ct = tid - 64;
@@ -690,7 +696,7 @@ ens_stream_kernel(StreamArgs p) {
         consts_s[5][tid] = (!GENERIC && tid < p.d) ? p.centre[tid] : 0.0;
     }
     if (tid < 32) scratch[tid >> 4][tid & 15] = 0.0;
-    if (tid < 4) ctl_s[tid >> 1][tid & 1] = 0;
+    if (tid == 0) abort_s = 0;
 
     // This workgroup's proposals: list positions b, b+G, b+2G, ... of every half step, in (step, split, position)
     // order.  Every dependency points to an EARLIER half step, so the globally oldest unfinished proposal can always
@@ -724,43 +730,41 @@ ens_stream_kernel(StreamArgs p) {
     }
     __syncthreads();
     int t = 0, split = 0, bb = b, item = 0;           // b < G <= n0: the first item is valid
-    // Wave 0 idles while the compute waves work: it uses that time to decode the NEXT proposal's record and to form the
-    // addresses it will poll and store to, so that nothing but the accept test separates barrier B from the row store and
-    // the store from the next poll.
-    int n_w = 0; double n_zz = 0.0, n_lnfac = 0.0, n_lnu = 0.0;
-    const unsigned long long *n_hw = p.hist, *n_hc = p.hist;
-    auto decode_next = [&](int it, int tt, int sp) {
-        const unsigned long long* rs = rec_s[it & 3];
-        const unsigned long long ids = rs[0];
-        n_w = (int)(unsigned)(ids & 0xffffffffull);
-        const int cw = (int)(unsigned)(ids >> 32);
-        n_zz = __longlong_as_double((long long)rs[1]);
-        n_lnfac = __longlong_as_double((long long)rs[2]); n_lnu = __longlong_as_double((long long)rs[3]);
-        // own row at version t, partner row at version t (+1 when the partner's half went first)
-        n_hw = p.hist + ((size_t)tt * WT + n_w) * row + lane;
-        n_hc = p.hist + ((size_t)(tt + sp) * WT + cw) * row + lane;
-    };
-    if (comm) decode_next(0, 0, 0);
-    while (t < p.K) {
-        int t2 = t, s2 = split, b2 = bb;
-        next_item(t2, s2, b2);
-        const int par = item & 1;
-        int w = 0, all_in = 0;
-        double qv = 0.0, sv = 0.0, lnfac = 0.0, lnu = 0.0;   // wave 0; lane k < d: coordinate k, lane d: logp
-#ifdef ALABI_STREAM_PROF
-        const long long c0 = clock64(); long long c1 = c0;
-#endif
-        unsigned long long* out_row = nullptr;
-        if (comm) {
-            w = n_w; lnfac = n_lnfac; lnu = n_lnu;
-            const double zz = n_zz;
+
+    if (comm) {
+        // ---- hand-off wave: poll -> proposal -> LDS -> A -> (prior term, next decode) -> B -> partial tree -> accept -> store
+        // While the compute waves work it decodes the NEXT proposal's record and forms the addresses it will poll and store
+        // to, so that nothing but the accept test separates barrier B from the row store and the store from the next poll.
+        int n_w = 0; double n_zz = 0.0, n_lnfac = 0.0, n_lnu = 0.0;
+        const unsigned long long *n_hw = p.hist, *n_hc = p.hist;
+        auto decode_next = [&](int it, int tt, int sp) {
+            const unsigned long long* rs = rec_s[it & 3];
+            const unsigned long long ids = rs[0];
+            n_w = (int)(unsigned)(ids & 0xffffffffull);
+            const int cw = (int)(unsigned)(ids >> 32);
+            n_zz = __longlong_as_double((long long)rs[1]);
+            n_lnfac = __longlong_as_double((long long)rs[2]); n_lnu = __longlong_as_double((long long)rs[3]);
+            // own row at version t, partner row at version t (+1 when the partner's half went first)
+            n_hw = p.hist + ((size_t)tt * WT + n_w) * row + lane;
+            n_hc = p.hist + ((size_t)(tt + sp) * WT + cw) * row + lane;
+        };
+        const double il_r = consts_s[0][lane], lo_r = consts_s[1][lane], hi_r = consts_s[2][lane], c_r = consts_s[5][lane];
+        const bool mine = lane <= p.d, needc = lane < p.d;
+        decode_next(0, 0, 0);
+        while (t < p.K) {
+            int t2 = t, s2 = split, b2 = bb;
+            next_item(t2, s2, b2);
+            const int par = item & 1;
+            const int w = n_w;
+            const double lnfac = n_lnfac, lnu = n_lnu, zz = n_zz;
             const unsigned long long *hw = n_hw, *hc = n_hc;    // this lane's words of the two rows
-            const double il_r = consts_s[0][lane], lo_r = consts_s[1][lane], hi_r = consts_s[2][lane], c_r = consts_s[5][lane];
+#ifdef ALABI_STREAM_PROF
+            const long long c0 = wall_clock64();
+#endif
             // The data IS the flag (Guideline 16 form R2): every word of a row is one aligned 8-byte sc1 store
             // over a sentinel NaN that no coordinate or log-probability can equal; lane k polls its own words.
             unsigned long long ws = ALABI_HIST_EMPTY, wc = ALABI_HIST_EMPTY;
-            int ok = 1, spins = 0;
-            const bool mine = lane <= p.d, needc = lane < p.d;
+            int okv = 1, spins = 0;
             while (true) {
                 if (mine && ws == ALABI_HIST_EMPTY) ws = ld_sc1(hw);
                 if (needc && wc == ALABI_HIST_EMPTY) wc = ld_sc1(hc);
@@ -768,15 +772,16 @@ ens_stream_kernel(StreamArgs p) {
                 if (__all(ready)) break;
                 if (++spins > p.spin_limit ||
                     ((spins & 63) == 0 && __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-                    ok = 0;
+                    okv = 0;
                     break;
                 }
             }
+            const int ok = __builtin_amdgcn_readfirstlane(okv);   // the exits above are wave-uniform
 #ifdef ALABI_STREAM_PROF
-            c1 = clock64();
+            const long long c1 = wall_clock64();
 #endif
             int inb = 1;
-            double qs = 0.0;
+            double qv = 0.0, sv = 0.0, qs = 0.0;      // lane k < d: coordinate k, lane d: logp
             if (ok && mine) {
                 sv = __longlong_as_double((long long)ws);
                 if (needc) {
@@ -787,76 +792,27 @@ ens_stream_kernel(StreamArgs p) {
                     if (!GENERIC) qs -= c_r;
                 }
             }
-            all_in = ok ? __all(inb) : 0;
-            if (lane < D) qs_s[par][lane] = qs;
-            if (lane == 63) qs_s[par][63] = all_in ? 1.0 : 0.0;   // the in-bounds flag travels with the proposal (D <= 16)
-            if (lane == 0) {
-                if (!ok) {                            // bounded spin ran out: every workgroup leaves, the host falls back
-                    ctl_s[0][1] = 1;
-                    __hip_atomic_store(p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+            const int all_in = ok ? __all(inb) : 0;
+            // the in-bounds flag travels in the word behind the proposal
+            if (lane <= D) qs_s[par][lane] = (lane == D) ? (all_in ? 1.0 : 0.0) : qs;
+            if (!ok && lane == 0) {                   // bounded spin ran out: every workgroup leaves, the host falls back
+                abort_s = 1;
+                __hip_atomic_store(p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-        }
-        __syncthreads();                              // barrier A: the proposal is in LDS
+            __syncthreads();                          // barrier A: the proposal is in LDS
 #ifdef ALABI_STREAM_PROF
-        const long long c2 = clock64();
+            const long long c2 = wall_clock64();
 #endif
-        double qraw[D];                               // one batch of LDS reads: the proposal and its in-bounds flag
-#pragma unroll
-        for (int k = 0; k < D; ++k) qraw[k] = qs_s[par][k];
-        if (!comm) all_in = __builtin_amdgcn_readfirstlane(__double2hiint(qs_s[par][63])) != 0;
-        if (compute && all_in) {
-            double q[D];                              // wave-uniform: moved to SGPRs
-#pragma unroll
-            for (int k = 0; k < D; ++k)
-                q[k] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(qraw[k])),
-                                        __builtin_amdgcn_readfirstlane(__double2loint(qraw[k])));
-            double acc = 0.0;
-            if (!GENERIC) {
-                const double nhq = se_neg_half_norm<D>(q);
-#pragma unroll
-                for (int j = 0; j < PPT; ++j) {
-                    double fa, fb;
-                    se_pair_terms<D>(xa[j], aa[j], q, nhq, fa, fb);
-                    acc += fa; acc += fb;
-                    if ((j & 1) == 1) __builtin_amdgcn_sched_barrier(0);   // four points in flight at a time
-                }
-            } else
-#pragma unroll
-            for (int j = 0; j < PPT; ++j) {
-                double r2a = 0.0, r2b = 0.0;
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                    const double da = xa[j][k].x - q[k], db = xa[j][k].y - q[k];
-                    r2a = fma(da, da, r2a);
-                    r2b = fma(db, db, r2b);
-                }
-                // same operation order as ens_half_kernel's lane (first pair by multiply, the rest by fma)
-                acc = (j == 0) ? aa[j].x * radial<GENERIC>(r2a, p.kf) : fma(aa[j].x, radial<GENERIC>(r2a, p.kf), acc);
-                acc = fma(aa[j].y, radial<GENERIC>(r2b, p.kf), acc);
-                if ((j & 1) == 1) __builtin_amdgcn_sched_barrier(0);   // four points in flight at a time: enough independent
-                                                                       // chains to cover the fp64 latency, bounded temporaries
-            }
-            const double wsum = wave_sum_dpp(acc);
-            if (lane == 63) scratch[par][wv - 1] = wsum;
-        }
-        double prior_q = 0.0;                         // normal-prior term of this proposal (0.0 adds exactly nothing)
-        if (comm) {                                   // idle until barrier B: prepare the store and the next proposal
+            // idle until barrier B: prepare the store and the next proposal
+            double prior_q = 0.0;                     // normal-prior term of this proposal (0.0 adds exactly nothing)
             if (p.has_prior) prior_q = normal_prior_sum(consts_s[3], consts_s[4], lane, p.d, qv) + p.prior_const;
-            out_row = p.hist + ((size_t)(t + 1) * WT + w) * row + lane;
+            unsigned long long* out_row = p.hist + ((size_t)(t + 1) * WT + w) * row + lane;
             if (t2 < p.K) decode_next(item + 1, t2, s2);
-        }
-        if (service) {                                // under the compute waves' kernel sum: ring slot item+2, issue item+3
-            if (lane < 4) rec_s[pslot & 3][lane] = pend;
-            next_item(pt, psplit, pbb); ++pslot;
-            pend = record_load(pt, psplit, pbb);
-        }
-        __syncthreads();                              // barrier B: the wave partials are in LDS
+            __syncthreads();                          // barrier B: the wave partials are in LDS
 #ifdef ALABI_STREAM_PROF
-        const long long c3 = clock64();
+            const long long c3 = wall_clock64();
 #endif
-        if (ctl_s[0][1]) return;
-        if (comm) {
+            if (!ok) return;
             double lp_new = -INFINITY;
             if (all_in) lp_new = fma(p.amp, wave_partials_tree(scratch[par], nwc), p.mean) + prior_q;
             const double lp_old = lane_bcast(sv, p.d);                // lane d loaded logp
@@ -866,19 +822,78 @@ ens_stream_kernel(StreamArgs p) {
             const unsigned long long outw = (lane <= p.d) ? (unsigned long long)__double_as_longlong(outv)
                                                           : (unsigned long long)acc_flag;
             if (lane <= p.d + 1) st_sc1(out_row, outw);
+            t = t2; split = s2; bb = b2; ++item;
+#ifdef ALABI_STREAM_PROF
+            { const long long c4 = wall_clock64();
+              prof[0] += c1 - c0; prof[1] += c2 - c1; prof[2] += c3 - c2; prof[3] += c4 - c3; prof[4] += 1; }
+#endif
         }
-        t = t2; split = s2; bb = b2; ++item;
 #ifdef ALABI_STREAM_PROF
-        { const long long c4 = clock64();
-          prof[0] += c1 - c0; prof[1] += c2 - c1; prof[2] += c3 - c2; prof[3] += c4 - c3; prof[4] += 1; }
+        if (tid == 0 && blockIdx.x == 3 && blockIdx.y == 0) {
+            for (int i = 0; i < 5; ++i) g_stream_prof[i] = prof[i];
+            g_stream_prof[5] = wall_clock64() - prof_begin;
+        }
 #endif
+    } else if (compute) {
+        // ---- compute waves: A -> q -> sum -> DPP -> partial -> B
+        while (t < p.K) {
+            next_item(t, split, bb);
+            const int par = item & 1;
+            __syncthreads();                          // barrier A: the proposal is in LDS
+            double qraw[D + 1];                       // one batch of LDS reads: the proposal and its in-bounds flag
+#pragma unroll
+            for (int k = 0; k <= D; ++k) qraw[k] = qs_s[par][k];
+            if (__builtin_amdgcn_readfirstlane(__double2hiint(qraw[D])) != 0) {
+                double q[D];                          // wave-uniform: moved to SGPRs
+#pragma unroll
+                for (int k = 0; k < D; ++k)
+                    q[k] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(qraw[k])),
+                                            __builtin_amdgcn_readfirstlane(__double2loint(qraw[k])));
+                double acc = 0.0;
+                if (!GENERIC) {
+                    const double nhq = se_neg_half_norm<D>(q);
+#pragma unroll
+                    for (int j = 0; j < PPT; ++j) {
+                        double fa, fb;
+                        se_pair_terms<D>(xa[j], aa[j], q, nhq, fa, fb);
+                        acc += fa; acc += fb;
+                        if ((j & 1) == 1) __builtin_amdgcn_sched_barrier(0);   // four points in flight at a time
+                    }
+                } else
+#pragma unroll
+                for (int j = 0; j < PPT; ++j) {
+                    double r2a = 0.0, r2b = 0.0;
+#pragma unroll
+                    for (int k = 0; k < D; ++k) {
+                        const double da = xa[j][k].x - q[k], db = xa[j][k].y - q[k];
+                        r2a = fma(da, da, r2a);
+                        r2b = fma(db, db, r2b);
+                    }
+                    // same operation order as ens_half_kernel's lane (first pair by multiply, the rest by fma)
+                    acc = (j == 0) ? aa[j].x * radial<GENERIC>(r2a, p.kf) : fma(aa[j].x, radial<GENERIC>(r2a, p.kf), acc);
+                    acc = fma(aa[j].y, radial<GENERIC>(r2b, p.kf), acc);
+                    if ((j & 1) == 1) __builtin_amdgcn_sched_barrier(0);   // four points in flight at a time: enough independent
+                                                                           // chains to cover the fp64 latency, bounded temporaries
+                }
+                const double wsum = wave_sum_dpp(acc);
+                if (lane == 63) scratch[par][wv - 1] = wsum;
+            }
+            __syncthreads();                          // barrier B: the wave partials are in LDS
+            if (abort_s) return;
+            ++item;
+        }
+    } else {
+        // ---- record wave: under the compute waves' kernel sum, ring slot item+2, issue the load of item+3
+        while (t < p.K) {
+            next_item(t, split, bb);
+            __syncthreads();                          // barrier A
+            if (lane < 4) rec_s[pslot & 3][lane] = pend;
+            next_item(pt, psplit, pbb); ++pslot;
+            pend = record_load(pt, psplit, pbb);
+            __syncthreads();                          // barrier B
+            if (abort_s) return;
+        }
     }
-#ifdef ALABI_STREAM_PROF
-    if (tid == 0 && blockIdx.x == 3 && blockIdx.y == 0) {
-        for (int i = 0; i < 5; ++i) g_stream_prof[i] = prof[i];
-        g_stream_prof[5] = clock64() - prof_begin;
-    }
-#endif
 }
 
 #ifdef ALABI_STREAM_PROF
@@ -929,6 +944,57 @@ ens_hist_chain_kernel(const unsigned long long* __restrict__ hist, int K, int WT
     }
 }
 
+// Fused epilogue of a persistent launch of K steps (ens_stream_kernel): ONE pass over rows 1..K of the history that writes the
+// thinned chain and chain_logp, counts the acceptances, writes (coords, logp) from row K, carries row K over to row 0 for the
+// next chunk, puts the sentinel back into every word it has read (the history is ready for the next launch without a fill
+// kernel) and advances run_state.  blockDim = (RP >= d + 2 words of a row, 256 / RP walkers); grid = (blocks of walkers,
+// groups of VG versions): the row position is the thread index, the thinning phase is divided out once per workgroup, and the
+// acceptance flags are summed per thread over its VG versions -- one atomic per (walker, workgroup).  After a time-out (*err)
+// nothing but run_state is touched: the rows are incomplete, the host restores the walkers and refills the history.
+#define ALABI_EPI_VG 16
+__global__ void __launch_bounds__(256)
+ens_hist_epilogue_kernel(unsigned long long* __restrict__ hist, int K, int WT, int d, int thin_by, long long step_next, long long done0,
+                         const int* __restrict__ err, double* __restrict__ coords, double* __restrict__ logp, double* __restrict__ chain,
+                         double* __restrict__ chain_logp, unsigned long long* __restrict__ n_accept, long long* __restrict__ run_state) {
+    const int k = threadIdx.x, row = d + 2;
+    const int w = blockIdx.x * blockDim.y + threadIdx.y;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && threadIdx.y == 0) { run_state[0] = step_next; run_state[1] = done0 + K; }
+    if (*err) return;
+    if (k >= row || w >= WT) return;
+    const int v0 = 1 + blockIdx.y * ALABI_EPI_VG;
+    const int v1 = (v0 + ALABI_EPI_VG - 1 < K) ? v0 + ALABI_EPI_VG - 1 : K;
+    long long slot = (done0 + v0) / thin_by;          // version v is stored iff (done0 + v) % thin_by == 0, in slot (done0 + v) / thin_by - 1
+    int phase = (int)((done0 + v0) % thin_by);
+    const size_t vstride = (size_t)WT * row;
+    unsigned long long* hp = hist + (size_t)v0 * vstride + (size_t)w * row + k;
+    unsigned long long nacc = 0;
+    for (int v = v0; v <= v1; v += 4, hp += 4 * vstride) {
+        unsigned long long word[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) word[j] = (v + j <= v1) ? hp[j * vstride] : 0ull;   // four rows in flight
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (v + j > v1) break;
+            hp[j * vstride] = ALABI_HIST_EMPTY;
+            if (k == d + 1) nacc += (word[j] == 1ull) ? 1ull : 0ull;
+            else {
+                const double val = __longlong_as_double((long long)word[j]);
+                if (phase == 0) {
+                    const size_t sw = (size_t)(slot - 1) * WT + w;
+                    if (k < d) { if (chain) chain[sw * d + k] = val; }
+                    else if (chain_logp) chain_logp[sw] = val;
+                }
+                if (v + j == K) {                     // the walkers after the chunk, and version 0 of the next one
+                    hist[(size_t)w * row + k] = word[j];
+                    if (k < d) coords[(size_t)w * d + k] = val; else logp[w] = val;
+                }
+            }
+            if (++phase == thin_by) { phase = 0; ++slot; }
+        }
+    }
+    if (k == d + 1 && n_accept && nacc) atomicAdd(n_accept + w, nacc);
+}
+
 // Persistent-kernel configuration: T compute lanes (+ the hand-off wave and the record wave), PPT point pairs per lane.
 // The limits are the largest dimension buckets that compile without VGPR spills
 // (hipcc -Rpass-analysis=kernel-resource-usage; 256 VGPRs at 384 threads, 168 at 640).
@@ -963,7 +1029,7 @@ bool ens_stream_fits(const alabi_ens* e) { return ens_stream_ppt(e) > 0; }
     }
 #define ALABI_STREAM_LAUNCH(PPT_, TMAX_)                                                                          \
     ALABI_STREAM_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type,                                              \
-        hipLaunchKernelGGL((ens_stream_kernel<D, PPT_, TMAX_, GENERIC>), dim3(e->stream_grid, e->E), dim3(T + 128), 0, s, a)))
+        hipLaunchKernelGGL((ens_stream_kernel<D, PPT_, TMAX_, GENERIC>), dim3(e->stream_grid, e->E), dim3(TMAX_), 0, s, a)))
 
 // Version history around a persistent launch of K steps: rows 1..K <- sentinel (`fill`: when the rows are polled), row 0 <- (coords, logp) before it;
 // (coords, logp) <- row K, chain / counters <- rows 1..K after it.  Shared by ens_stream_kernel and ens_group_kernel.
@@ -1001,18 +1067,21 @@ int launch_ens_hist_epilogue(alabi_ens* e, double* coords, double* logp, int K, 
     return ALABI_OK;
 }
 
-int launch_ens_stream(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
-                      long long* n_accept, hipStream_t s) {
+// One chunk of K steps on the persistent kernel, proposal records from `rec`.  `first`: row 0 of the history is taken from
+// (coords, logp) (later chunks of a call find it there, left by the previous chunk's epilogue); fill_rows > 0: rows 1..fill_rows
+// cannot be trusted to hold the sentinel (first use of the handle, after a time-out or the group kernel) and are refilled.
+int launch_ens_stream_kernel(alabi_ens* e, const DrawBuffers& rec, double* coords, double* logp, int K, bool first, int fill_rows,
+                             hipStream_t s) {
     alabi_gp* gp = e->gp;
     const int n0 = (e->W + 1) / 2;
-    { const int st0 = launch_ens_hist_prologue(e, coords, logp, K, true, s); if (st0 != ALABI_OK) return st0; }
+    const int WT = e->W * e->E, row = e->d + 2;
+    if (fill_rows > 0) hipLaunchKernelGGL(ens_hist_fill_kernel, dim3(1024), dim3(256), 0, s, e->hist + (size_t)WT * row, (size_t)fill_rows * WT * row);
+    if (first) hipLaunchKernelGGL(ens_hist_copy_kernel, dim3((WT * row + 255) / 256), dim3(256), 0, s, coords, logp, e->hist, WT, e->d, 1);
     StreamArgs a{};
-    a.hist = e->hist; a.err = e->err; a.rec = e->draws; a.consts = e->consts;
+    a.hist = e->hist; a.err = e->err; a.rec = rec; a.consts = e->consts;
     const bool se = gp->kf.type == 0;                 // squared exponential: centred inputs and h (se_pair_terms), built by ens_se_prepare
     a.Xt = se ? gp->Xc : gp->Xt; a.alpha = se ? gp->ens_h : gp->alpha; a.centre = gp->xa_centre;
-    a.chain = chain; a.chain_logp = chain_logp;
-    a.n_accept = reinterpret_cast<unsigned long long*>(n_accept); a.run_state = e->run_state;
-    a.K = K; a.W = e->W; a.n0 = n0; a.d = e->d; a.Npad = gp->Npad; a.thin_by = thin_by; a.spin_limit = 1 << 20;
+    a.K = K; a.W = e->W; a.n0 = n0; a.d = e->d; a.Npad = gp->Npad; a.spin_limit = 1 << 20;
     if (const char* env = getenv("ALABI_ENS_SPIN_LIMIT")) { const int v = atoi(env); if (v > 0) a.spin_limit = v; }   // tests: force a time-out
     a.amp = e->lp_scale * exp(gp->log_amp); a.mean = fma(e->lp_scale, gp->mean, e->lp_shift); a.kf = gp->kf;
     a.has_prior = e->has_prior; a.prior_const = e->prior_const;
@@ -1033,10 +1102,28 @@ int launch_ens_stream(alabi_ens* e, double* coords, double* logp, int K, int thi
         else return ALABI_BAD_ARGUMENT;
     } else return ALABI_BAD_ARGUMENT;
     ALABI_LAUNCH_CHECK();
-    return launch_ens_hist_epilogue(e, coords, logp, K, thin_by, chain, chain_logp, n_accept, s);
+    return ALABI_OK;
 }
 
-int launch_ens_draw(alabi_ens* e, int nsteps, double a, hipStream_t s) {
+// The chunk's fused epilogue.  step_next / done0: the global step after the chunk and the steps of this call done before it,
+// by value (nothing on the device is read to launch a chunk).
+int launch_ens_stream_epilogue(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
+                               long long* n_accept, long long step_next, long long done0, hipStream_t s) {
+    const int WT = e->W * e->E, row = e->d + 2;
+    int rp = 16;                                      // words of a row rounded up to a power of two: threadIdx.x is the row position
+    while (rp < row) rp <<= 1;
+    const int wb = 256 / rp;
+    hipLaunchKernelGGL(ens_hist_epilogue_kernel, dim3((WT + wb - 1) / wb, (K + ALABI_EPI_VG - 1) / ALABI_EPI_VG), dim3(rp, wb), 0, s,
+                       e->hist, K, WT, e->d, thin_by, step_next, done0, e->err, coords, logp, chain, chain_logp,
+                       reinterpret_cast<unsigned long long*>(n_accept), e->run_state);
+    ALABI_LAUNCH_CHECK();
+    return ALABI_OK;
+}
+
+int launch_ens_draw(alabi_ens* e, int nsteps, double a, hipStream_t s) { return launch_ens_draw_at(e, e->draws, nsteps, a, true, 0, s); }
+
+// from_state: the first global step of the chunk is run_state[0]; otherwise it is step0, by value
+int launch_ens_draw_at(alabi_ens* e, const DrawBuffers& into, int nsteps, double a, bool from_state, long long step0, hipStream_t s) {
     int Wp = 1;
     while (Wp < e->W) Wp <<= 1;
     const size_t lds = (size_t)Wp * 12 + 1024;
@@ -1045,8 +1132,8 @@ int launch_ens_draw(alabi_ens* e, int nsteps, double a, hipStream_t s) {
         ALABI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ens_draw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
-    hipLaunchKernelGGL(ens_draw_kernel, dim3(nsteps, e->E), dim3(256), lds, s, e->seed, e->run_state, e->W, Wp, e->d, a,
-                       e->draws);
+    hipLaunchKernelGGL(ens_draw_kernel, dim3(nsteps, e->E), dim3(256), lds, s, e->seed, from_state ? e->run_state : nullptr,
+                       from_state ? 0LL : step0, e->W, Wp, e->d, a, into);
     ALABI_LAUNCH_CHECK();
     return ALABI_OK;
 }

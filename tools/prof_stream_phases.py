@@ -1,4 +1,5 @@
-"""Phase breakdown of the persistent ensemble kernel (needs a build with -DALABI_STREAM_PROF: see tools/README.md)."""
+"""Phase breakdown of the persistent ensemble kernel, real-time stamps of the hand-off wave of one workgroup (needs a build
+with -DALABI_STREAM_PROF: see tools/README.md)."""
 import ctypes, sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -16,8 +17,11 @@ L.alabi_debug_stream_prof.argtypes = [ctypes.POINTER(ctypes.c_longlong)]
 print("rc", L.alabi_debug_stream_prof(out), "path", s.last_path, "wall us/half-step", 1e6 * dt / 2048)
 v = list(out)[:6]
 n = max(v[4], 1)
-names = ["poll wait (wave 0)", "form proposal + barrier A", "compute waves (A -> B)", "tree sum + accept + row store + loop"]
+# stamps are wall_clock64() (the constant 100 MHz counter): the shader clock under-counts when two waves share a SIMD, and the
+# hand-off wave does
+names = ["poll wait (hand-off wave)", "rows detected -> barrier A", "barrier A -> barrier B (compute waves)", "barrier B -> row store issued"]
 tot = sum(v[:4])
+tick_ns = 1e9 * dt / max(v[5], 1)                    # calibrated against the call's wall time (nominal 10 ns)
 for nm, x in zip(names, v[:4]):
-    print(f"{nm:36s} {x / n:9.1f} ticks/item  {100.0 * x / tot:5.1f}%")
-print("items", n, "ticks total", v[5], "ticks/item", v[5] / n, "=> tick ns", 1e9 * dt / v[5])
+    print(f"{nm:40s} {x / n:9.2f} ticks/item {x / n * tick_ns:9.1f} ns  {100.0 * x / tot:5.1f}%")
+print("items", n, "ticks total", v[5], "ticks/item", v[5] / n, "=> tick ns", tick_ns)
