@@ -186,7 +186,7 @@ int alabi_gp_compute(alabi_gp* gp, const double* X, int N, void* stream) {
     gp->computed = false; gp->has_alpha = false; gp->gen++;
     int st;
     if ((st = launch_prepare_inputs(gp, X, N, s)) != ALABI_OK) return st;
-    // 16..160 block columns: the task-queue factorisation (one launch); a wait that runs out there is remembered for a while
+    // 3..256 block columns: the task-queue factorisation (one launch); a wait that runs out there is remembered for a while
     static std::atomic<int> tasks_penalty{0};
     int queued = 0, ctl_ints = 0;
     const char* tq = getenv("ALABI_CHOL_TASKS");              // "1" forces the queue: then the penalty does not apply either

@@ -10,10 +10,13 @@
 
 namespace alabi {
 
-// k_i = amp f(r2(x_i, x_new)) for i < N (0 on the padding) -> kcol; the scaled coordinates of the new point -> Xt[:, N]
+// k_i = amp f(r2(x_i, x_new)) for i < N (0 on the padding) -> kcol.  The training set itself is NOT touched here: the new point's
+// scaled coordinates go into the padding column Xt[:, N] only once its pivot has passed (append_pivot_kernel) -- several prediction
+// and gradient kernels multiply the padding columns by a zero instead of masking them, so a rejected NaN / inf point left there
+// would poison a factor the API calls untouched.
 template <int D, bool GENERIC>
 __global__ void __launch_bounds__(256)
-append_kcol_kernel(double* __restrict__ Xt, int N, int Npad, const double* __restrict__ x_new, int d, DimVec inv_len,
+append_kcol_kernel(const double* __restrict__ Xt, int N, int Npad, const double* __restrict__ x_new, int d, DimVec inv_len,
                    double amp, KernelFn kf, double* __restrict__ kcol) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     double q[D];
@@ -28,8 +31,6 @@ append_kcol_kernel(double* __restrict__ Xt, int N, int Npad, const double* __res
         }
         kcol[i] = (i < N) ? amp * radial<GENERIC>(r2, kf) : 0.0;
     }
-    __syncthreads();
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < D) Xt[(size_t)threadIdx.x * Npad + N] = q[threadIdx.x];
 }
 
 // l = W k for the rows of block rb: W tile-major, W[t][i][c] = L^-1[i][64 t + c] (exact zeros above the diagonal).
@@ -57,10 +58,12 @@ append_lrow_kernel(const double* __restrict__ W, const double* __restrict__ kcol
     if (q == 0) lrow[i] = (i < N) ? acc : 0.0;
 }
 
-// pivot of the new row; writes row N of L and dinv[N] when it is positive, reports LAPACK-style info otherwise
+// pivot of the new row; writes row N of L, dinv[N] and the point's scaled coordinates (Xt[:, N]: the dim_bucket(d) <= 64 rows of
+// the layout, zeros beyond d) when it is positive, reports LAPACK-style info and writes nothing else otherwise
 __global__ void __launch_bounds__(256)
 append_pivot_kernel(double* __restrict__ L, double* __restrict__ dinv, const double* __restrict__ lrow, int N, int Npad,
-                    double kss, int* __restrict__ info, double* __restrict__ scal) {
+                    double kss, int* __restrict__ info, double* __restrict__ scal, double* __restrict__ Xt,
+                    const double* __restrict__ x_new, int d, int db, DimVec inv_len) {
     __shared__ double scratch[16];
     double s = 0.0;
     for (int i = threadIdx.x; i < N; i += 256) s = fma(lrow[i], lrow[i], s);
@@ -73,6 +76,7 @@ append_pivot_kernel(double* __restrict__ L, double* __restrict__ dinv, const dou
     const double lnn = sqrt(dd);
     for (int j = threadIdx.x; j < Npad; j += 256)
         L[(size_t)N * Npad + j] = (j < N) ? lrow[j] : (j == N ? lnn : 0.0);
+    if (threadIdx.x < db) Xt[(size_t)threadIdx.x * Npad + N] = (threadIdx.x < d) ? x_new[threadIdx.x] * inv_len.v[threadIdx.x] : 0.0;
     if (threadIdx.x == 0) { dinv[N] = 1.0 / lnn; scal[0] = lnn; *info = 0; }
 }
 
@@ -122,7 +126,8 @@ int launch_append(alabi_gp* gp, const double* x_new, hipStream_t s) {
     ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type, hipLaunchKernelGGL((append_kcol_kernel<D, GENERIC>), dim3((Npad + 255) / 256),
         dim3(256), 0, s, gp->Xt, N, Npad, x_new, gp->d, gp->inv_len, amp, gp->kf, kcol)));
     hipLaunchKernelGGL(append_lrow_kernel, dim3(nb), dim3(256), 0, s, gp->winv, kcol, N, Npad, lrow);
-    hipLaunchKernelGGL(append_pivot_kernel, dim3(1), dim3(256), 0, s, gp->L, gp->dinv, lrow, N, Npad, kss, gp->info, gp->red + 2);
+    hipLaunchKernelGGL(append_pivot_kernel, dim3(1), dim3(256), 0, s, gp->L, gp->dinv, lrow, N, Npad, kss, gp->info, gp->red + 2,
+                       gp->Xt, x_new, gp->d, db, gp->inv_len);
     hipLaunchKernelGGL(append_wrow_kernel, dim3(nb), dim3(256), 0, s, gp->winv, lrow, N, Npad, gp->red + 2);
     ALABI_LAUNCH_CHECK();
     return ALABI_OK;

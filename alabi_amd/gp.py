@@ -309,11 +309,9 @@ class HipGP:
         self._alpha_host = None
         if st == _lib.NOT_PD:
             self.computed = False
-            piv = C.c_int(0)
-            _lib.lib().alabi_gp_last_pivot(self._handle, C.byref(piv))
             if quiet:
                 return False
-            raise np.linalg.LinAlgError(f"{piv.value}-th leading minor of the array is not positive definite")
+            raise np.linalg.LinAlgError(f"{self.last_pivot}-th leading minor of the array is not positive definite")
         _lib.check(st, "alabi_gp_compute")
         self.computed = True
         self.dirty = False
@@ -540,6 +538,16 @@ class HipGP:
         self.set_parameter_vector(p0)
         self.recompute(quiet=True)
         return g
+
+    @property
+    def last_pivot(self):
+        """LAPACK's ``info`` of the handle's last factorisation or append (alabi_gp_last_pivot): 0 when it succeeded, else the
+        1-based index of the first pivot that was not positive (NaN included).  None without a handle."""
+        if self._handle is None:
+            return None
+        piv = C.c_int(0)
+        _lib.check(_lib.lib().alabi_gp_last_pivot(self._handle, C.byref(piv)), "alabi_gp_last_pivot")
+        return piv.value
 
     # -------------------------------------------------------------------- private members
     @property

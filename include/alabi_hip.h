@@ -104,7 +104,8 @@ int alabi_gp_batch_timeouts(alabi_gp_batch* batch, int* count /* host */);
 /* Extend the factorisation by ONE training point x_new[d] (device) with the hyper-parameters unchanged: the refit after every
  * active-learning iteration (alabi/core.py:1780 -> _fit_gp -> gp.compute at :1158) in O(N^2) through the cached L^-1 instead
  * of O(N^3).  Needs a free padding row (N not a multiple of 64 and N < n_cap): ALABI_BAD_ARGUMENT otherwise -- call
- * alabi_gp_compute then.  ALABI_NOT_POSITIVE_DEFINITE leaves the factor as it was.  Invalidates alpha (call alabi_gp_set_y).
+ * alabi_gp_compute then.  ALABI_NOT_POSITIVE_DEFINITE (alabi_gp_last_pivot: N + 1) leaves the factor, the training set and alpha
+ * as they were: every prediction of the old factor is bit for bit what it was.  Success invalidates alpha (call alabi_gp_set_y).
  * SYNCHRONISES the stream. */
 int alabi_gp_append(alabi_gp* gp, const double* x_new, void* stream);
 

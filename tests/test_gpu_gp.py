@@ -822,9 +822,10 @@ def test_cholesky_task_queue(torch_gpu, monkeypatch, N, waves):
         for env in ("1", "0"):
             monkeypatch.setenv("ALABI_CHOL_TASKS", env)
             gd = HipGP(6, 0.0, -80.0, 0.0, np.zeros(6))
-            with pytest.raises(np.linalg.LinAlgError):
+            with pytest.raises(np.linalg.LinAlgError, match="^2-th leading minor"):
                 gd.compute(Xd)
-            assert gd.compute(Xd, quiet=True) is False
+            assert gd.last_pivot == 2                         # K is all ones: pivot 2 = 1 - 1 (every path and position: test_gpu_not_pd.py)
+            assert gd.compute(Xd, quiet=True) is False and gd.last_pivot == 2
         # a wait that runs out: fall back, same factor
         monkeypatch.setenv("ALABI_CHOL_TASKS", "1")
         monkeypatch.setenv("ALABI_CHOL_SPIN_LIMIT", "1")
