@@ -189,8 +189,8 @@ int alabi_gp_compute(alabi_gp* gp, const double* X, int N, void* stream) {
     // 3..256 block columns: the task-queue factorisation (one launch); a wait that runs out there is remembered for a while
     static std::atomic<int> tasks_penalty{0};
     int queued = 0, ctl_ints = 0;
-    const char* tq = getenv("ALABI_CHOL_TASKS");              // "1" forces the queue: then the penalty does not apply either
-    if (!(tq && tq[0] == '1') && tasks_penalty.load(std::memory_order_relaxed) > 0) tasks_penalty.fetch_sub(1, std::memory_order_relaxed);
+    // a forced queue (chol_tasks.hpp): then the penalty does not apply either
+    if (!chol_queue_forced_on(chol_switches()) && tasks_penalty.load(std::memory_order_relaxed) > 0) tasks_penalty.fetch_sub(1, std::memory_order_relaxed);
     else if ((st = cholesky_tasks_prepare(gp, s, &ctl_ints)) != ALABI_OK) return st;
     if ((st = launch_assemble(gp, s, ctl_ints)) != ALABI_OK) return st;   // also clears the status word and the queue's control words
     if (ctl_ints > 0 && (st = launch_cholesky_tasks(gp, s, &queued)) != ALABI_OK) return st;

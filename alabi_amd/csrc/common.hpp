@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/alabi_hip.h"
+#include "chol_tasks.hpp"
 
 #define ALABI_BLK 64  // Cholesky / TRSM block edge; matrices are padded to a multiple of it
 
@@ -180,22 +181,21 @@ int launch_prepare_inputs(alabi_gp* gp, const double* X, int N, hipStream_t s);
 int launch_assemble(alabi_gp* gp, hipStream_t s, int zero_ctl_ints = 0);   // also clears gp->info and the first zero_ctl_ints words of gp->chol_ctl
 int launch_kernel_matrix(const double* X1, int n1, const double* X2, int n2, int d, double amp,
                          const DimVec& inv_len, KernelFn kf, double* K, hipStream_t s);
-// gp_cholesky.hip
+// gp_cholesky.hip (launchers; device code in chol_tiles / chol_steps / chol_queue.hpp, task lists and switches in chol_tasklist.hip)
 int launch_cholesky(alabi_gp* gp, hipStream_t s);
 int cholesky_tasks_prepare(alabi_gp* gp, hipStream_t s, int* ctl_ints);   // > 0: the task queue will run, its control words (to be zeroed by the assembly)
 int launch_cholesky_tasks(alabi_gp* gp, hipStream_t s, int* launched);
 int launch_cholesky_steps(double* L, int Npad, int* info, double* dinv, hipStream_t s);   // launch-per-step path on a bare matrix
 // batched task queue (gp_batch.hip): many independent matrices in one launch of chol_tasks8_batch_kernel
-struct CholTask;
-struct CholMat;
 struct CholBatchQueue {
-    std::vector<int> nbs;                       // key of the cached task list: block columns per matrix, lists, window
-    int nlists = 0, window = 0, B = 0, shape_sig = 0;
+    std::vector<int> nbs;                       // key of the cached task list: block columns per matrix, lists, window, list-shaping switches
+    int nlists = 0, window = 0, B = 0;
+    CholListShape shape;
     CholTask* tasks = nullptr; size_t tasks_cap = 0; int ntasks = 0;
     int* list_off = nullptr;                    // device [nlists + 1]
     CholMat* mats = nullptr; size_t mats_cap = 0;
     int* ctl = nullptr; size_t ctl_ints = 0, ctl_cap = 0;   // [32 q] list heads, [1] time-out flag, from [256] on: per matrix tile versions + slab counters
-    double* linv = nullptr; size_t linv_cap = 0;            // per matrix the slab buffers [nb][4][64][16] (gp_cholesky.hip: what the panel solves read of a diagonal tile)
+    double* linv = nullptr; size_t linv_cap = 0;            // per matrix the slab buffers [nb][4][64][16] (chol_queue.hpp: what the panel solves read of a diagonal tile)
 };
 int chol_batch_prepare(CholBatchQueue& q, int B, const int* ld, double* const* A, double* const* dinv, int* const* info, hipStream_t s);
 int chol_batch_launch(CholBatchQueue& q, hipStream_t s);

@@ -8,7 +8,7 @@
 // resident inputs X / y and
 //   batch_prepare_kernel   gathers and scales each job's training rows                      (grid: rows x jobs)
 //   batch_assemble_kernel  writes each job's kernel matrix (assemble_tile: the bits of the single-matrix path)
-//   chol_tasks8_batch_kernel  factorises ALL of them in one launch of the task queue (gp_cholesky.hip: interleaved task lists,
+//   chol_tasks8_batch_kernel  factorises ALL of them in one launch of the task queue (chol_queue.hpp; chol_tasklist.hip: interleaved task lists,
 //                          one list and head counter per XCD, chains of different matrices side by side)
 //   batch_solve_kernel     alpha = K^-1 (y - m), log-determinant, (y - m)^T alpha            (one workgroup per job)
 //   batch_predict_kernel   mean at the validation rows                                       (32 queries per workgroup)

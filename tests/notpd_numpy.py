@@ -1,6 +1,7 @@
 """Training sets whose Cholesky factorisation fails at a KNOWN pivot, and the rule that says which: netlib's dpotf2.  Shared by
 test_not_pd_host.py (the constructions against the rule and against LAPACK, on the oracle's matrix) and test_gpu_not_pd.py (every
-factorisation path of csrc/gp_cholesky.hip and csrc/gp_append.hip against ``p + 1``).  Not a test module.
+factorisation path of csrc/gp_cholesky.hip (its kernels: csrc/chol_steps.hpp, csrc/chol_queue.hpp) and csrc/gp_append.hip
+against ``p + 1``).  Not a test module.
 
 The only way into the library is K = amp f(r) + wn I, so the failing pivot is placed through the training points:
 

@@ -1,8 +1,8 @@
 """Every way the library produces a Cholesky pivot must report a matrix that is not positive definite with LAPACK's ``info``: the
 1-based index of the FIRST pivot that is not > 0 (NaN included), read through alabi_gp_last_pivot / the status array of the batch.
 
-Paths (csrc/gp_cholesky.hip, csrc/gp_append.hip): launch per step with rank-64 updates; 2/4/8-column panels with and without
-look-ahead; the one-launch task queue with four and eight waves and its grouped-update shapes; the batched queue and its
+Paths (csrc/gp_cholesky.hip with its kernels in csrc/chol_steps.hpp and csrc/chol_queue.hpp, csrc/gp_append.hip): launch per step
+with rank-64 updates; 2/4/8-column panels with and without look-ahead; the one-launch task queue with four and eight waves and its grouped-update shapes; the batched queue and its
 launch-per-step fallback; the rank-1 append.  None of them tests a pivot inside the recurrence: a bad pivot turns its own and
 every later column into NaN and the finished tile's diagonal is searched (potrf_first_bad), the first report wins through
 atomicCAS(info, 0, kb * 64 + bad).
