@@ -627,15 +627,16 @@ __device__ long long g_stream_prof[16];
 #endif
 
 // Sum of the wave partials s[0..15] (zeros beyond the last compute wave) in exactly the order wave_sum_dpp adds
-// lanes 0..15 of a row -- a balanced binary tree -- so this path and ens_half_kernel agree bit for bit.
-__device__ inline double wave_partials_tree(const double* s, int nw) {
-    const f64x2 a = reinterpret_cast<const f64x2*>(s)[0], b = reinterpret_cast<const f64x2*>(s)[1];
-    const f64x2 c = reinterpret_cast<const f64x2*>(s)[2], d = reinterpret_cast<const f64x2*>(s)[3];
-    const double lo8 = ((d.y + d.x) + (c.y + c.x)) + ((b.y + b.x) + (a.y + a.x));
-    if (nw <= 8) return lo8;
-    const f64x2 e = reinterpret_cast<const f64x2*>(s)[4], f = reinterpret_cast<const f64x2*>(s)[5];
-    const f64x2 g = reinterpret_cast<const f64x2*>(s)[6], h = reinterpret_cast<const f64x2*>(s)[7];
-    const double hi8 = ((h.y + h.x) + (g.y + g.x)) + ((f.y + f.x) + (e.y + e.x));
+// lanes 0..15 of a row -- a balanced binary tree -- so this path and ens_half_kernel agree bit for bit.  Only the pairs that
+// hold a partial are read; a pair beyond them is the +0.0 it holds, and the additions of such zeros that reach a live
+// value stay in the code: x + 0.0 is +0.0 for x = -0.0, so they are not the identity.
+template <int NW>
+__device__ inline double wave_partials_tree(const double* s) {
+    const f64x2* v = reinterpret_cast<const f64x2*>(s);
+    auto pair = [&](int i) { return 2 * i < NW ? v[i].y + v[i].x : 0.0; };
+    const double lo8 = (pair(3) + pair(2)) + (pair(1) + pair(0));
+    if (NW <= 8) return lo8;
+    const double hi8 = (pair(7) + pair(6)) + (pair(5) + pair(4));
     return hi8 + lo8;
 }
 
@@ -647,10 +648,13 @@ __device__ inline double wave_partials_tree(const double* s, int nw) {
 //                   and after the reduction does the accept test and the one row store.  It computes no kernel values
 //                   and issues no other memory operation: gfx950 returns a wave's vector memory operations in issue
 //                   order (one vmcnt), so any ordinary load or store would put its latency in front of the next poll.
-//                   It takes the abort decision from its own register.
+//                   It takes the abort decision from its own register.  Its loop has no divergent branch and no exit from
+//                   inside: either makes the compiler thread the whole loop nest through flag registers and exec-mask
+//                   ladders, which then stand on the chain of every half step (tests/test_stream_chain_isa.py counts them).
 //   waves 1..nwc    the training-set share of each lane lives in VGPRs for the whole launch; between the two barriers
 //                   of a proposal they evaluate the kernel sum and leave one partial per wave in LDS.  The in-bounds flag
-//                   sits in the word behind the proposal (qs_s[par][D]): one batch of LDS reads brings both.
+//                   sits in the word behind the proposal (qs_s[par][D]): one batch of LDS reads brings both, issued whole
+//                   before the flag is tested.
 //   last wave       fetches the packed proposal records (one 32-byte load) three proposals ahead into an LDS ring.
 // Waves other than wave 0 look at the abort word after barrier B, where they delay nobody.  Every role steps through the
 // proposals with the same next_item, so all waves execute the same number of barriers, early exit included.
@@ -732,10 +736,15 @@ ens_stream_kernel(StreamArgs p) {
     int t = 0, split = 0, bb = b, item = 0;           // b < G <= n0: the first item is valid
 
     if (comm) {
-        // ---- hand-off wave: poll -> proposal -> LDS -> A -> (prior term, next decode) -> B -> partial tree -> accept -> store
-        // While the compute waves work it decodes the NEXT proposal's record and forms the addresses it will poll and store
-        // to, so that nothing but the accept test separates barrier B from the row store and the store from the next poll.
-        int n_w = 0; double n_zz = 0.0, n_lnfac = 0.0, n_lnu = 0.0;
+        // ---- hand-off wave: poll -> proposal -> LDS -> A -> (prior term, reject row, next decode) -> B -> partials -> accept -> store
+        // The chain from the arrival of the polled words to barrier A is straight-line code over all 64 lanes: lanes beyond
+        // the row poll its last word again (every address is one of the row's own), so no load, test or LDS write needs
+        // an exec mask; what those lanes compute is masked out of the in-bounds vote and never read.  While the compute waves
+        // work the wave forms everything the accept test does not produce -- the address of the new row, the row as it is
+        // written if the proposal is rejected, the accept operands, the next proposal's addresses -- so that behind barrier B
+        // only the sum of the partials and the accept test remain.
+        const int n0_lane = lane < p.d ? lane : p.d, n1_lane = lane < p.d ? lane : p.d - 1;
+        int n_w = 0; double n_zz = 0.0;
         const unsigned long long *n_hw = p.hist, *n_hc = p.hist;
         auto decode_next = [&](int it, int tt, int sp) {
             const unsigned long long* rs = rec_s[it & 3];
@@ -743,85 +752,98 @@ ens_stream_kernel(StreamArgs p) {
             n_w = (int)(unsigned)(ids & 0xffffffffull);
             const int cw = (int)(unsigned)(ids >> 32);
             n_zz = __longlong_as_double((long long)rs[1]);
-            n_lnfac = __longlong_as_double((long long)rs[2]); n_lnu = __longlong_as_double((long long)rs[3]);
             // own row at version t, partner row at version t (+1 when the partner's half went first)
-            n_hw = p.hist + ((size_t)tt * WT + n_w) * row + lane;
-            n_hc = p.hist + ((size_t)(tt + sp) * WT + cw) * row + lane;
+            n_hw = p.hist + ((size_t)tt * WT + n_w) * row + n0_lane;
+            n_hc = p.hist + ((size_t)(tt + sp) * WT + cw) * row + n1_lane;
         };
         const double il_r = consts_s[0][lane], lo_r = consts_s[1][lane], hi_r = consts_s[2][lane], c_r = consts_s[5][lane];
-        const bool mine = lane <= p.d, needc = lane < p.d;
+        const bool needc = lane < p.d;
+        const unsigned long long coord_lanes = (1ull << p.d) - 1;
         decode_next(0, 0, 0);
         while (t < p.K) {
-            int t2 = t, s2 = split, b2 = bb;
-            next_item(t2, s2, b2);
             const int par = item & 1;
-            const int w = n_w;
-            const double lnfac = n_lnfac, lnu = n_lnu, zz = n_zz;
-            const unsigned long long *hw = n_hw, *hc = n_hc;    // this lane's words of the two rows
 #ifdef ALABI_STREAM_PROF
             const long long c0 = wall_clock64();
 #endif
             // The data IS the flag (Guideline 16 form R2): every word of a row is one aligned 8-byte sc1 store
             // over a sentinel NaN that no coordinate or log-probability can equal; lane k polls its own words.
-            unsigned long long ws = ALABI_HIST_EMPTY, wc = ALABI_HIST_EMPTY;
-            int okv = 1, spins = 0;
-            while (true) {
-                if (mine && ws == ALABI_HIST_EMPTY) ws = ld_sc1(hw);
-                if (needc && wc == ALABI_HIST_EMPTY) wc = ld_sc1(hc);
-                const int ready = (!mine || ws != ALABI_HIST_EMPTY) && (!needc || wc != ALABI_HIST_EMPTY);
-                if (__all(ready)) break;
-                if (++spins > p.spin_limit ||
-                    ((spins & 63) == 0 && __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-                    okv = 0;
-                    break;
-                }
+            unsigned long long ws, wc;
+            int spins = 0;
+            bool pending;
+            for (;;) {
+                ws = ld_sc1(n_hw);
+                wc = ld_sc1(n_hc);
+                pending = __builtin_amdgcn_ballot_w64(ws == ALABI_HIST_EMPTY || wc == ALABI_HIST_EMPTY) != 0;
+                if (!pending) break;
+                // (readfirstlane: a loaded value counts as divergent, and a divergent exit is threaded through exec-mask ladders)
+                if (__builtin_expect(++spins > p.spin_limit || ((spins & 63) == 0 && __builtin_amdgcn_readfirstlane(
+                        __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0), 0)) break;
             }
-            const int ok = __builtin_amdgcn_readfirstlane(okv);   // the exits above are wave-uniform
+            // Bounded spin ran out: every workgroup leaves, the host falls back.  The cold block rejoins the fast path instead of
+            // leaving the loops from inside (exits from a loop nest cost flag registers and ladders on the fast path too): a NaN
+            // stretch factor puts the proposal out of bounds, so the compute waves skip it; this is the last proposal, its
+            // row is not stored, and the other waves see abort_s behind barrier B.
+            if (__builtin_expect(pending, 0)) {
+                n_zz = __builtin_nan("");
+                abort_s = 1;                          // (every lane writes the same: no divergent branch in this loop)
+                __hip_atomic_store(p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
 #ifdef ALABI_STREAM_PROF
             const long long c1 = wall_clock64();
 #endif
-            int inb = 1;
-            double qv = 0.0, sv = 0.0, qs = 0.0;      // lane k < d: coordinate k, lane d: logp
-            if (ok && mine) {
-                sv = __longlong_as_double((long long)ws);
-                if (needc) {
-                    const double cv = __longlong_as_double((long long)wc);
-                    qv = cv - (cv - sv) * zz;
-                    inb = (qv > lo_r) && (qv < hi_r);
-                    qs = qv * il_r;
-                    if (!GENERIC) qs -= c_r;
-                }
-            }
-            const int all_in = ok ? __all(inb) : 0;
-            // the in-bounds flag travels in the word behind the proposal
-            if (lane <= D) qs_s[par][lane] = (lane == D) ? (all_in ? 1.0 : 0.0) : qs;
-            if (!ok && lane == 0) {                   // bounded spin ran out: every workgroup leaves, the host falls back
-                abort_s = 1;
-                __hip_atomic_store(p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            // lane k < d: coordinate k, lane d: logp
+            const double sv = __longlong_as_double((long long)ws), cv = __longlong_as_double((long long)wc);
+            const double qv = cv - (cv - sv) * n_zz;
+            // one compare mask per bound, tested against the lanes that hold a coordinate
+            const bool all_in = (__builtin_amdgcn_ballot_w64(qv > lo_r) & __builtin_amdgcn_ballot_w64(qv < hi_r) & coord_lanes)
+                                == coord_lanes;
+            double qs = qv * il_r;
+            if (!GENERIC) qs -= c_r;
+            // The in-bounds flag travels in the word behind the proposal, as the high half of 1.0 or 0.0: a second write, which
+            // the LDS performs after the first (lane D wrote 0.0 there), so no select of the flag stands in front of the first.
+            // The words behind the flag are never read.
+            qs_s[par][lane] = needc ? qs : 0.0;
+            reinterpret_cast<int*>(&qs_s[par][D])[1] = all_in ? 0x3ff00000 : 0;
             __syncthreads();                          // barrier A: the proposal is in LDS
+            __builtin_amdgcn_sched_barrier(0);        // nothing of the idle window's work in front of it
 #ifdef ALABI_STREAM_PROF
             const long long c2 = wall_clock64();
 #endif
-            // idle until barrier B: prepare the store and the next proposal
+            // idle until barrier B: everything of the store that does not need the partials, then the next proposal
+            int t2 = t, s2 = split, b2 = bb;
+            next_item(t2, s2, b2);
+            if (pending) t2 = p.K;
             double prior_q = 0.0;                     // normal-prior term of this proposal (0.0 adds exactly nothing)
-            if (p.has_prior) prior_q = normal_prior_sum(consts_s[3], consts_s[4], lane, p.d, qv) + p.prior_const;
-            unsigned long long* out_row = p.hist + ((size_t)(t + 1) * WT + w) * row + lane;
+            if (p.has_prior) {                        // normal_prior_sum with a select for its branch
+                const double u = (qv - consts_s[3][lane]) * consts_s[4][lane];
+                prior_q = lane_bcast(wave_sum_dpp(needc ? -0.5 * u * u : 0.0), 63) + p.prior_const;
+            }
+            // this lane's word of the new row; the lanes behind the row write its last word, the acceptance flag, again
+            size_t out_word = ((size_t)(t + 1) * WT + n_w) * row + (lane <= p.d ? lane : p.d + 1);
+            double lnfac = __longlong_as_double((long long)rec_s[item & 3][2]);
+            double lnu = __longlong_as_double((long long)rec_s[item & 3][3]);
+            double lp_old = lane_bcast(sv, p.d);      // lane d loaded logp
+            // the new row of the walker, lanes k < d coordinates, lane d logp, lane d+1 the acceptance flag: as it is written
+            // if the proposal is rejected, and if it is accepted (lane d of that one takes lp_new behind barrier B)
+            unsigned long long w_rej = needc ? ws : lane == p.d ? (unsigned long long)__double_as_longlong(lp_old) : 0ull;
+            // (an out-of-bounds proposal is rejected whatever the test behind barrier B says: lp_new = -inf fails it)
+            unsigned long long w_acc = !all_in ? w_rej : needc ? (unsigned long long)__double_as_longlong(qv) : 1ull;
+            const bool takes_lp = all_in && lane == p.d;
+            int part = par * (int)sizeof(scratch[0]);
             if (t2 < p.K) decode_next(item + 1, t2, s2);
+            // pin the above in front of the barrier: none of it may sink behind it, into the store's exec mask or the next poll
+            // (values, not pointers: a pointer that passed through here would lose its address space)
+            asm volatile("" : "+v"(out_word), "+v"(w_rej), "+v"(w_acc), "+v"(lp_old), "+v"(lnfac), "+v"(lnu), "+v"(prior_q), "+v"(part));
+            __builtin_amdgcn_sched_barrier(0);
             __syncthreads();                          // barrier B: the wave partials are in LDS
 #ifdef ALABI_STREAM_PROF
             const long long c3 = wall_clock64();
 #endif
-            if (!ok) return;
-            double lp_new = -INFINITY;
-            if (all_in) lp_new = fma(p.amp, wave_partials_tree(scratch[par], nwc), p.mean) + prior_q;
-            const double lp_old = lane_bcast(sv, p.d);                // lane d loaded logp
-            const int acc_flag = (lnfac + lp_new - lp_old > lnu) ? 1 : 0;
-            // new row of the walker: lanes k < d coordinates, lane d logp, lane d+1 the acceptance flag
-            const double outv = (lane < p.d) ? (acc_flag ? qv : sv) : (acc_flag ? lp_new : lp_old);
-            const unsigned long long outw = (lane <= p.d) ? (unsigned long long)__double_as_longlong(outv)
-                                                          : (unsigned long long)acc_flag;
-            if (lane <= p.d + 1) st_sc1(out_row, outw);
+            const double* partials = reinterpret_cast<const double*>(reinterpret_cast<const char*>(&scratch[0][0]) + part);
+            const double lp_new = fma(p.amp, wave_partials_tree<nwc>(partials), p.mean) + prior_q;
+            const bool acc = lnfac + lp_new - lp_old > lnu;
+            if (takes_lp) w_acc = (unsigned long long)__double_as_longlong(lp_new);
+            if (!pending) st_sc1(p.hist + out_word, acc ? w_acc : w_rej);
             t = t2; split = s2; bb = b2; ++item;
 #ifdef ALABI_STREAM_PROF
             { const long long c4 = wall_clock64();
@@ -840,15 +862,20 @@ ens_stream_kernel(StreamArgs p) {
             next_item(t, split, bb);
             const int par = item & 1;
             __syncthreads();                          // barrier A: the proposal is in LDS
-            double qraw[D + 1];                       // one batch of LDS reads: the proposal and its in-bounds flag
+            // ONE batch of LDS reads brings the proposal and its in-bounds flag: the broadcasts to SGPRs stand in front of the
+            // test (a convergent operation is not sunk into the branch, so neither are the reads that feed it)
+            double q[D];
 #pragma unroll
-            for (int k = 0; k <= D; ++k) qraw[k] = qs_s[par][k];
-            if (__builtin_amdgcn_readfirstlane(__double2hiint(qraw[D])) != 0) {
-                double q[D];                          // wave-uniform: moved to SGPRs
-#pragma unroll
-                for (int k = 0; k < D; ++k)
-                    q[k] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(qraw[k])),
-                                            __builtin_amdgcn_readfirstlane(__double2loint(qraw[k])));
+            for (int k = 0; k < D; ++k) {
+                const double r = qs_s[par][k];
+                q[k] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(r)),
+                                        __builtin_amdgcn_readfirstlane(__double2loint(r)));
+            }
+            const int inb = __builtin_amdgcn_readfirstlane(__double2hiint(qs_s[par][D]));
+            // every LDS read is issued before the first is waited for: the reads (at most D + 1), then the broadcasts
+            __builtin_amdgcn_sched_group_barrier(0x100, D + 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x2, 2 * D + 1, 0);
+            if (inb != 0) {
                 double acc = 0.0;
                 if (!GENERIC) {
                     const double nhq = se_neg_half_norm<D>(q);
