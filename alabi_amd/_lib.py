@@ -91,6 +91,8 @@ SIGNATURES = {
     "alabi_ns_create": (_i, [_vp, _i, _pd, _ull, C.POINTER(_vp)]),
     "alabi_ns_destroy": (_i, [_vp]),
     "alabi_ns_set_logp": (_i, [_vp, _d, _d, _i]),
+    "alabi_ns_set_normal_prior": (_i, [_vp, _pd, _pd]),
+    "alabi_ns_transform": (_i, [_vp, _vp, _i, _vp, _vp]),
     "alabi_ns_prior_draw": (_i, [_vp, _ll, _i, _i, _vp, _vp, _vp]),
     "alabi_ns_walk": (_i, [_vp, _ll, _i, _vp, _vp, _i, _d, _vp, _d, _i, _vp, _vp, _vp, _vp]),
     "alabi_ns_propose": (_i, [_vp, _ll, _i, _vp, _i, _i, _vp, _d, _vp, _vp]),

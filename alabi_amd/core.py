@@ -1048,12 +1048,14 @@ class SurrogateModel(object):
         """Nested sampling of the posterior and its evidence log Z on the GPU (core.py:2417-2787); the sampler is
         alabi_amd.nested.NestedSampler (its docstring states the algorithm) in place of dynesty's.
 
-        * Fused path: the surrogate likelihood (like_fn None / "surrogate" / "gp"), prior_transform None or
-          ``partial(ut.prior_transform_uniform, bounds=...)``, affine theta scaler, affine / nlog / log y scaler: every walk
-          step evaluates the GP mean inside ``ns_walk_kernel``.
+        * Fused path: the surrogate likelihood (like_fn None / "surrogate" / "gp"), prior_transform None,
+          ``partial(ut.prior_transform_uniform, bounds=...)`` or ``partial(ut.prior_transform_normal, bounds=..., data=...)``
+          (Gaussian priors: the inverse normal CDF inside the kernels, not truncated to the bounds, as in the reference),
+          affine theta scaler, affine / nlog / log y scaler: every walk step evaluates the GP mean inside ``ns_walk_kernel``.
         * Otherwise (like_fn "true" or a callable, any other prior_transform, scalers the kernel cannot fold) the device proposes
           and accepts, and the host evaluates ``like_fn(prior_transform(u))`` row by row with 1-D arrays of shape (d,), as
-          dynesty calls them (the surrogate under exotic scalers takes the whole batch in one call).
+          dynesty calls them (the surrogate under exotic scalers takes the whole batch in one call, and so does the
+          ``prior_transform_normal`` partial).
         sampler_kwargs: ``nlive`` (50 ndim), ``sample`` ("auto" / "rwalk": ``walks`` (25) Metropolis steps per walk; "rslice":
         ``slices`` (3 (3 + ndim)) random-direction slice updates per walk, 5-15 times the likelihood evaluations of the random
         walk), ``batch`` (ceil(nlive / 4)), ``seed``.  Above ndim = 20 pass ``sample="rslice"``: 25 random-walk steps no longer
@@ -1129,11 +1131,12 @@ class SurrogateModel(object):
             print(f"Running nested sampling ({mode}, {'fused GPU walks' if plan.fused else 'host likelihood'}) with {nlive} live "
                   "points...")
         all_logz = []
+        normal = {} if plan.normal_prior is None else {"normal_prior": plan.normal_prior}     # Gaussian prior coordinates
 
         def run(run_number):
             s = (self._seed() if seed is None else int(seed) + 1000003 * (run_number - 1)) + rank
             backend = GPUWalkBackend(gp_obj, y_obj, plan.box, seed=s, to_theta=plan.to_theta, logp_affine=plan.logp_affine,
-                                     logp_map=plan.logp_map, host_loglike=plan.host_like)
+                                     logp_map=plan.logp_map, host_loglike=plan.host_like, **normal)
             self.dynesty_sampler = NestedSampler(backend, nlive, dynamic=(mode == "dynamic"), walks=walks, batch=batch, seed=s,
                                                  **move)
             checkpoint = None

@@ -8,9 +8,23 @@
 //   x = lo + u * width,   logL(u) = map(amp * sum_n alpha_n k(x, x_n) + mean)
 // with amp / mean carrying an affine y scaler and map the inverse of the nlog / log scalers (apply_ymap) -- exactly the
 // log-probability of the ensemble kernels without the prior term.
+// Normal priors (alabi_ns_set_normal_prior; the reference's prior_transform_normal, alabi/utility.py:381-482): on the coordinates
+// of a 64-bit mask the cube maps through the inverse normal CDF instead, x = mean + std * ndtri(u), NOT truncated to the box, as
+// in the reference.  The host stores mean in lo and std in width (std may be negative, as width may), so ns_scaled_coord is
+//   x = fma(t, width, lo),   t = u (uniform coordinate) or ndtri(u), with ndtri(2^-54) at u = 0 (normal coordinate).
+// The clamp: u53 returns exactly 0 with probability 2^-53, ndtri(0) = -inf, and the centred squared-exponential form turns
+// x = -inf into NaN; 2^-54 maps to -8.37 std.  Every other value of u53 is >= 2^-53, so for drawn points this is
+// ndtri(max(u, 2^-54)); a positive u below 2^-54 (only a proposal of a walk can land there) keeps its own finite ndtri (-37 std
+// at 1e-300), which AS 241 gives to full accuracy.  u < 1 always holds (u53 < 1, and the walks keep 0 < u < 1).  The prior enters
+// nested sampling through this map alone: no Jacobian term.  Kernels with a non-empty mask are instantiations of their own
+// (template flag NORMAL); with an empty mask the instantiations and every result are those of the uniform-only code.
+// ndtri is Wichura's AS 241 (PPND16, Appl. Statist. 37 (1988) 477-484) in fp64 (ns_ndtri): three rational approximations of
+// degree 7 / 7, one Horner pair whose 16 coefficients each lane reads from a 48-entry table in LDS (ns_ndtri_coef, copied
+// there at the start of the kernel).  Literal coefficients -- HIP's normcdfinv has about 180 of them -- are hoisted out of the
+// step loop as loop invariants and then spilled: +1.4 KB of scratch per lane in every instantiation; LDS reads are not hoisted.
 //
 // Kernels
-//   ns_walk_kernel<D, GENERIC, TMAX, TILED>  one workgroup per walk; all `walks` Metropolis steps inside one launch (walks never talk to
+//   ns_walk_kernel<D, GENERIC, TMAX, TILED, NORMAL>  one workgroup per walk; all `walks` Metropolis steps inside one launch (walks never talk to
 //                               each other).  The workgroup's share of the training set -- centred inputs + h for the squared
 //                               exponential (se_pair_terms), inputs + alpha for the other families, one point pair per lane, the
 //                               layout of ens_half_kernel -- is loaded once into VGPRs and used for every step.  When Npad / 2
@@ -21,13 +35,14 @@
 //                               Cholesky factor C of the live points' covariance held in LDS, the cube gate 0 < u' < 1, the
 //                               GP mean at x(u'), accept iff logL(u') > L*.  A walk that accepts nothing returns its start
 //                               bit for bit.
-//   ns_slice_kernel<D, GENERIC, TMAX, TILED>  random-direction slice sampling (dynesty's "rslice"), one workgroup per walk, all slices
+//   ns_slice_kernel<D, GENERIC, TMAX, TILED, NORMAL>  random-direction slice sampling (dynesty's "rslice"), one workgroup per walk, all slices
 //                               of the walk in one launch, the training-set share in VGPRs as above.  The slice is a state machine
 //                               (ns_slice_advance: direction, stepping out, shrinking; its scalars live in LDS) advanced by wave 0
 //                               from one in-cube query to the next; the loop around it holds the single ns_logl call site.
 //   ns_slice_step_kernel        the same state machine driven one query at a time around a host likelihood: per-walk state in
 //                               device memory, consumes the host's logL of the pending query, advances to the next one.
 //   ns_prior_kernel             uniform points in the cube.
+//   ns_transform_kernel         cube points -> scaled coordinates by ns_scaled_coord, the map the walks use (alabi_ns_transform).
 //   ns_propose_kernel           the proposal of one step of every walk (host-callable likelihoods): the same draws and the same
 //                               arithmetic as the fused walk (shared functions below), so both paths move identically.
 //   ns_accept_kernel            the accept test of one step, given the host's logL of the proposals.
@@ -48,7 +63,9 @@ struct alabi_ns {
     alabi_gp* gp = nullptr;
     int d = 0;
     unsigned long long seed = 0;
-    alabi::DimVec lo{}, width{};
+    alabi::DimVec lo{}, width{};             // normal coordinate (bit of nmask set): mean, std
+    alabi::DimVec box_lo{}, box_width{};     // the box given to alabi_ns_create
+    unsigned long long nmask = 0;
     double lp_scale = 1.0, lp_shift = 0.0;
     int ymap = 0;
     int last_path = 0;   // 1 register-resident training set, 2 tiled (pairs beyond the block size re-read from L2 every step)
@@ -77,6 +94,7 @@ struct NsArgs {
     long long call;
     int walk_id0, K, d, walks;
     double logl_star, scale;
+    unsigned long long nmask;    // coordinates with a normal prior: lo = mean, width = std
 };
 
 // Normals 2j and 2j+1 of step `step` of walk `wid`.
@@ -109,10 +127,62 @@ __device__ inline double ns_prop_coord(const double* C, int ldc, const double* z
     return u + scale * acc;
 }
 
+// AS 241 PPND16: numerator, denominator (constant term 1 first) for |p - 1/2| <= 0.425 in r = 0.180625 - (p - 1/2)^2; for
+// r = sqrt(-log(min(p, 1 - p))) <= 5 in r - 1.6; for r > 5 in r - 5.  Coefficients in ascending order.
+#define ALABI_NS_NDTRI_COEFS 48
+__constant__ double ns_ndtri_coef[ALABI_NS_NDTRI_COEFS] = {
+    3.3871328727963666080, 1.3314166789178437745e+2, 1.9715909503065514427e+3, 1.3731693765509461125e+4,
+    4.5921953931549871457e+4, 6.7265770927008700853e+4, 3.3430575583588128105e+4, 2.5090809287301226727e+3,
+    1.0, 4.2313330701600911252e+1, 6.8718700749205790830e+2, 5.3941960214247511077e+3,
+    2.1213794301586595867e+4, 3.9307895800092710610e+4, 2.8729085735721942674e+4, 5.2264952788528545610e+3,
+    1.42343711074968357734, 4.63033784615654529590, 5.76949722146069140550, 3.64784832476320460504,
+    1.27045825245236838258, 2.41780725177450611770e-1, 2.27238449892691845833e-2, 7.74545014278341407640e-4,
+    1.0, 2.05319162663775882187, 1.67638483018380384940, 6.89767334985100004550e-1,
+    1.48103976427480074590e-1, 1.51986665636164571966e-2, 5.47593808499534494600e-4, 1.05075007164441684324e-9,
+    6.65790464350110377720, 5.46378491116411436990, 1.78482653991729133580, 2.96560571828504891230e-1,
+    2.65321895265761230930e-2, 1.24266094738807843860e-3, 2.71155556874348757815e-5, 2.01033439929228813265e-7,
+    1.0, 5.99832206555887937690e-1, 1.36929880922735805310e-1, 1.48753612908506148525e-2,
+    7.86869131145613259100e-4, 1.84631831751005468180e-5, 1.42151175831644588870e-7, 2.04426310338993978564e-15};
+
+// Every thread of the workgroup: the table into LDS (a barrier must follow before ns_ndtri reads it).
+__device__ inline void ns_ndtri_load(double* tab_s) {
+    for (int i = threadIdx.x; i < ALABI_NS_NDTRI_COEFS; i += blockDim.x) tab_s[i] = ns_ndtri_coef[i];
+}
+
+// Inverse of the standard normal CDF at 0 < p < 1; tab_s: the table in LDS.
+__device__ __forceinline__ double ns_ndtri(const double* tab_s, double p) {
+    const double q = p - 0.5;
+    const bool centre = fabs(q) <= 0.425;
+    double r = fma(-q, q, 0.180625);
+    int base = 0;
+    if (!centre) {
+        r = sqrt(-log(q < 0.0 ? p : 1.0 - p));
+        base = r <= 5.0 ? 16 : 32;
+        r -= r <= 5.0 ? 1.6 : 5.0;
+    }
+    const double* c = tab_s + base;
+    double num = c[7], den = c[15];
+#pragma unroll
+    for (int k = 6; k >= 0; --k) {
+        num = fma(num, r, c[k]);
+        den = fma(den, r, c[8 + k]);
+    }
+    const double v = num / den;
+    return centre ? q * v : (q < 0.0 ? -v : v);
+}
+
+// Scaled coordinate (the prior transform, before the length scales) of cube coordinate k.
+template <bool NORMAL>
+__device__ __forceinline__ double ns_scaled_coord(const NsArgs& p, const double* tab_s, int k, double u) {
+    double t = u;
+    if (NORMAL && ((p.nmask >> k) & 1ull)) t = ns_ndtri(tab_s, u > 0.0 ? u : 0x1p-54);
+    return fma(t, p.width.v[k], p.lo.v[k]);
+}
+
 // GP coordinate (scaled by the inverse length scales; centred for the squared exponential) of cube coordinate k.
-template <bool GENERIC>
-__device__ inline double ns_gp_coord(const NsArgs& p, int k, double u) {
-    double x = fma(u, p.width.v[k], p.lo.v[k]) * p.inv_len.v[k];
+template <bool GENERIC, bool NORMAL>
+__device__ __forceinline__ double ns_gp_coord(const NsArgs& p, const double* tab_s, int k, double u) {
+    double x = ns_scaled_coord<NORMAL>(p, tab_s, k, u) * p.inv_len.v[k];
     if (!GENERIC) x -= p.centre[k];
     return x;
 }
@@ -279,7 +349,7 @@ __device__ inline void ns_slice_reset(NsSliceState* st, double logl) {
 }
 
 // NsArgs as the walk kernel; p.walks = slices, p.n_acc = counts [4K]: evaluations, expansions, contractions, capped slices.
-template <int D, bool GENERIC, int TMAX, bool TILED>
+template <int D, bool GENERIC, int TMAX, bool TILED, bool NORMAL>
 __global__ void __launch_bounds__(TMAX)
 ns_slice_kernel(NsArgs p) {
     __shared__ double C_s[D * D];
@@ -287,6 +357,7 @@ ns_slice_kernel(NsArgs p) {
     __shared__ double scratch[16];
     __shared__ NsSliceState st_s;
     __shared__ int go_s;
+    __shared__ double nd_s[ALABI_NS_NDTRI_COEFS];            // NORMAL only (unused, so not allocated, otherwise)
     const int tid = threadIdx.x, T = blockDim.x, b = blockIdx.x, d = p.d;
     const uint32_t wid = (uint32_t)(p.walk_id0 + b);
     const int half = p.Npad >> 1;
@@ -305,13 +376,14 @@ ns_slice_kernel(NsArgs p) {
         a_s[tid] = 0.0; q_s[tid] = 0.0; qs_s[tid] = 0.0;
     }
     if (tid == 0) ns_slice_reset(&st_s, p.logl0[b]);
+    if (NORMAL) ns_ndtri_load(nd_s);
     __syncthreads();
     double lp = 0.0;
     for (;;) {
         if (tid < 64) {
             const int query = ns_slice_advance(&st_s, u_s, a_s, q_s, C_s, D, p.seed, p.call, wid, d, p.walks, p.scale, p.logl_star,
                                                tid, lp);
-            if (tid < d) qs_s[tid] = ns_gp_coord<GENERIC>(p, tid, q_s[tid]);
+            if (tid < d) qs_s[tid] = ns_gp_coord<GENERIC, NORMAL>(p, nd_s, tid, q_s[tid]);
             if (tid == 0) go_s = query;
         }
         __syncthreads();
@@ -379,7 +451,7 @@ ns_slice_end_kernel(int K, int d, const char* __restrict__ state, double* __rest
 }
 
 // TMAX: 1024 lanes for dimension buckets <= 16, 256 above (the register budget of xa[D] and the query), see ns_threads.
-template <int D, bool GENERIC, int TMAX, bool TILED>
+template <int D, bool GENERIC, int TMAX, bool TILED, bool NORMAL>
 __global__ void __launch_bounds__(TMAX)
 ns_walk_kernel(NsArgs p) {
     __shared__ double C_s[D * D];
@@ -387,6 +459,7 @@ ns_walk_kernel(NsArgs p) {
     __shared__ double scratch[16];
     __shared__ double L_s;
     __shared__ int acc_s, nev_s;
+    __shared__ double nd_s[ALABI_NS_NDTRI_COEFS];            // NORMAL only (unused, so not allocated, otherwise)
     const int tid = threadIdx.x, T = blockDim.x, b = blockIdx.x, d = p.d;
     const uint32_t wid = (uint32_t)(p.walk_id0 + b);
     // the training-set share of this lane: issued first, resident for the whole walk
@@ -401,11 +474,12 @@ ns_walk_kernel(NsArgs p) {
         const int r = i / D, c = i % D;
         C_s[i] = (r < d && c <= r && p.walks > 0) ? p.chol[(size_t)r * d + c] : 0.0;
     }
+    if (NORMAL) { ns_ndtri_load(nd_s); __syncthreads(); }
     if (tid < D) {
         const double u = tid < d ? p.u0[(size_t)b * d + tid] : 0.0;
         u_s[tid] = u;
         z_s[tid] = 0.0;
-        qs_s[tid] = tid < d ? ns_gp_coord<GENERIC>(p, tid, u) : 0.0;
+        qs_s[tid] = tid < d ? ns_gp_coord<GENERIC, NORMAL>(p, nd_s, tid, u) : 0.0;
     }
     if (tid == 0) { L_s = p.logl0 ? p.logl0[b] : -INFINITY; acc_s = 0; nev_s = 0; }
     __syncthreads();
@@ -420,7 +494,7 @@ ns_walk_kernel(NsArgs p) {
                 const double up = ns_prop_coord(C_s, D, z_s, tid, u_s[tid], p.scale);
                 ok = (up > 0.0) && (up < 1.0);
                 up_s[tid] = up;
-                qs_s[tid] = ns_gp_coord<GENERIC>(p, tid, up);
+                qs_s[tid] = ns_gp_coord<GENERIC, NORMAL>(p, nd_s, tid, up);
             }
         }
         const int inb = __syncthreads_and(ok);
@@ -455,6 +529,18 @@ ns_prior_kernel(unsigned long long seed, long long call, int walk_id0, int n, in
     philox4x32_10((uint32_t)call, (uint32_t)(walk_id0 + i), ALABI_NS_PRIOR_STEP, (uint32_t)j, (uint32_t)seed, (uint32_t)(seed >> 32), r);
     u_out[(size_t)i * d + 2 * j] = u53(r[0], r[1]);
     if (2 * j + 1 < d) u_out[(size_t)i * d + 2 * j + 1] = u53(r[2], r[3]);
+}
+
+// p.u0 [K, d] cube points -> p.u_out [K, d] scaled coordinates; four points per workgroup, one per wave, lane k = coordinate k.
+__global__ void __launch_bounds__(256)
+ns_transform_kernel(NsArgs p) {
+    __shared__ double nd_s[ALABI_NS_NDTRI_COEFS];
+    ns_ndtri_load(nd_s);
+    __syncthreads();
+    const int k = threadIdx.x & 63;
+    const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= p.K || k >= p.d) return;
+    p.u_out[(size_t)b * p.d + k] = ns_scaled_coord<true>(p, nd_s, k, p.u0[(size_t)b * p.d + k]);
 }
 
 // One 64-lane workgroup per walk: the normals and the proposal exactly as ns_walk_kernel forms them.
@@ -498,6 +584,12 @@ using namespace alabi;
 
 static inline hipStream_t ns_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+#define NS_DISPATCH_FLAGS(TILED_, NORMAL_, ...)                                          \
+    if (NORMAL_) { constexpr bool NORMAL = true;                                         \
+        if (TILED_) { constexpr bool TILED = true; __VA_ARGS__; } else { constexpr bool TILED = false; __VA_ARGS__; } } \
+    else { constexpr bool NORMAL = false;                                                \
+        if (TILED_) { constexpr bool TILED = true; __VA_ARGS__; } else { constexpr bool TILED = false; __VA_ARGS__; } }
+
 // Block size of the walk kernel: one training-point pair per lane when Npad / 2 <= 1024 (the register-resident path), 1024 lanes
 // otherwise (pairs beyond them re-read from L2 each step).  Dimension buckets above 16 use at most 256 lanes, and their
 // instantiations are compiled for 256 (ns_tmax) so that xa[D] gets the registers of a 256-lane block.
@@ -524,6 +616,7 @@ int alabi_ns_create(alabi_gp* gp, int d, const double* bounds, unsigned long lon
         n->lo.v[k] = k < d ? bounds[2 * k] : 0.0;
         n->width.v[k] = k < d ? bounds[2 * k + 1] - bounds[2 * k] : 0.0;
     }
+    n->box_lo = n->lo; n->box_width = n->width;
     *out = n;
     return ALABI_OK;
 }
@@ -537,6 +630,32 @@ int alabi_ns_set_logp(alabi_ns* ns, double scale, double shift, int map_kind) {
     if (!ns || !(scale > 0.0) || !std::isfinite(scale) || !std::isfinite(shift) || map_kind < 0 || map_kind > 2)
         return ALABI_BAD_ARGUMENT;
     ns->lp_scale = scale; ns->lp_shift = shift; ns->ymap = map_kind;
+    return ALABI_OK;
+}
+
+int alabi_ns_set_normal_prior(alabi_ns* ns, const double* mean, const double* std) {
+    if (!ns || !mean || !std) return ALABI_BAD_ARGUMENT;
+    for (int k = 0; k < ns->d; ++k)
+        if (std::isfinite(mean[k]) && (!std::isfinite(std[k]) || std[k] == 0.0)) return ALABI_BAD_ARGUMENT;
+    ns->nmask = 0;
+    for (int k = 0; k < ns->d; ++k) {
+        const bool normal = std::isfinite(mean[k]);
+        ns->lo.v[k] = normal ? mean[k] : ns->box_lo.v[k];
+        ns->width.v[k] = normal ? std[k] : ns->box_width.v[k];
+        if (normal) ns->nmask |= 1ull << k;
+    }
+    return ALABI_OK;
+}
+
+int alabi_ns_transform(alabi_ns* ns, const double* u, int K, double* x_out, void* stream) {
+    if (!ns || K < 0) return ALABI_BAD_ARGUMENT;
+    if (K == 0) return ALABI_OK;
+    if (!u || !x_out) return ALABI_BAD_ARGUMENT;
+    NsArgs a{};
+    a.lo = ns->lo; a.width = ns->width; a.nmask = ns->nmask;
+    a.u0 = u; a.u_out = x_out; a.K = K; a.d = ns->d;
+    hipLaunchKernelGGL(ns_transform_kernel, dim3((unsigned)(((long long)K + 3) / 4)), dim3(256), 0, ns_stream(stream), a);
+    ALABI_LAUNCH_CHECK();
     return ALABI_OK;
 }
 
@@ -561,19 +680,15 @@ int alabi_ns_walk(alabi_ns* ns, long long call, int walk_id0, const double* u0, 
     a.Xsrc = se ? gp->Xc : gp->Xt; a.Asrc = se ? gp->ens_h : gp->alpha; a.centre = gp->xa_centre;
     a.Npad = gp->Npad; a.kf = gp->kf;
     a.amp = ns->lp_scale * std::exp(gp->log_amp); a.mean = std::fma(ns->lp_scale, gp->mean, ns->lp_shift); a.ymap = ns->ymap;
-    a.lo = ns->lo; a.width = ns->width; a.inv_len = gp->inv_len;
+    a.lo = ns->lo; a.width = ns->width; a.inv_len = gp->inv_len; a.nmask = ns->nmask;
     a.u0 = u0; a.logl0 = logl0; a.chol = chol; a.u_out = u_out; a.logl_out = logl_out; a.n_acc = n_accept;
     a.seed = ns->seed; a.call = call; a.walk_id0 = walk_id0; a.K = K; a.d = ns->d; a.walks = walks;
     a.logl_star = logl_star; a.scale = scale;
     const int db = dim_bucket(ns->d), T = ns_threads(gp, db);
     ns->last_path = (gp->Npad / 2 <= T) ? 1 : 2;
-    if (ns->last_path == 1) {
-        ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type,
-            hipLaunchKernelGGL((ns_walk_kernel<D, GENERIC, ns_tmax(D), false>), dim3(K), dim3(T), 0, s, a)));
-    } else {
-        ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type,
-            hipLaunchKernelGGL((ns_walk_kernel<D, GENERIC, ns_tmax(D), true>), dim3(K), dim3(T), 0, s, a)));
-    }
+    const bool tiled = ns->last_path == 2;
+    ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type, NS_DISPATCH_FLAGS(tiled, a.nmask != 0,
+        hipLaunchKernelGGL((ns_walk_kernel<D, GENERIC, ns_tmax(D), TILED, NORMAL>), dim3(K), dim3(T), 0, s, a))));
     ALABI_LAUNCH_CHECK();
     return ALABI_OK;
 }
@@ -593,19 +708,15 @@ int alabi_ns_slice(alabi_ns* ns, long long call, int walk_id0, const double* u0,
     a.Xsrc = se ? gp->Xc : gp->Xt; a.Asrc = se ? gp->ens_h : gp->alpha; a.centre = gp->xa_centre;
     a.Npad = gp->Npad; a.kf = gp->kf;
     a.amp = ns->lp_scale * std::exp(gp->log_amp); a.mean = std::fma(ns->lp_scale, gp->mean, ns->lp_shift); a.ymap = ns->ymap;
-    a.lo = ns->lo; a.width = ns->width; a.inv_len = gp->inv_len;
+    a.lo = ns->lo; a.width = ns->width; a.inv_len = gp->inv_len; a.nmask = ns->nmask;
     a.u0 = u0; a.logl0 = logl0; a.chol = chol; a.u_out = u_out; a.logl_out = logl_out; a.n_acc = counts;
     a.seed = ns->seed; a.call = call; a.walk_id0 = walk_id0; a.K = K; a.d = ns->d; a.walks = slices;
     a.logl_star = logl_star; a.scale = scale;
     const int db = dim_bucket(ns->d), T = ns_threads(gp, db);
     ns->last_path = (gp->Npad / 2 <= T) ? 1 : 2;
-    if (ns->last_path == 1) {
-        ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type,
-            hipLaunchKernelGGL((ns_slice_kernel<D, GENERIC, ns_tmax(D), false>), dim3(K), dim3(T), 0, s, a)));
-    } else {
-        ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type,
-            hipLaunchKernelGGL((ns_slice_kernel<D, GENERIC, ns_tmax(D), true>), dim3(K), dim3(T), 0, s, a)));
-    }
+    const bool tiled = ns->last_path == 2;
+    ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type, NS_DISPATCH_FLAGS(tiled, a.nmask != 0,
+        hipLaunchKernelGGL((ns_slice_kernel<D, GENERIC, ns_tmax(D), TILED, NORMAL>), dim3(K), dim3(T), 0, s, a))));
     ALABI_LAUNCH_CHECK();
     return ALABI_OK;
 }

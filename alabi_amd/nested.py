@@ -396,11 +396,15 @@ class GPUWalkBackend:
 
     Fused (``host_loglike=None``): logL(u) = map(scale * GP mean(lo + u (hi - lo)) + shift) inside ``ns_walk_kernel``;
     ``bounds`` [d,2] in the GP's scaled coordinates, ``logp_affine=(scale, shift)``, ``logp_map`` None / "nlog" / "log".
+    ``normal_prior=(mean[d], std[d])`` in the same coordinates (NaN mean: uniform over the box; std may be negative) replaces the
+    uniform map by mean + std * ndtri(u) on its coordinates, un-truncated (the reference's prior_transform_normal);
+    ``transform(u)`` returns the scaled coordinates the kernels evaluate the GP at.
     Split: ``host_loglike(u [m,d]) -> [m]`` is called between alabi_ns_propose and alabi_ns_accept for the in-cube proposals
     of every step.  ``to_theta(u [m,d]) -> [m,d]`` maps cube points to the samples reported.
     ``rslice`` is the slice move on the same two paths: ``ns_slice_kernel``, or alabi_ns_slice_step around ``host_loglike``."""
 
-    def __init__(self, gp, y, bounds, seed, to_theta, logp_affine=(1.0, 0.0), logp_map=None, host_loglike=None):
+    def __init__(self, gp, y, bounds, seed, to_theta, logp_affine=(1.0, 0.0), logp_map=None, host_loglike=None,
+                 normal_prior=None):
         self.gp, self._y = gp, y
         self.ndim = int(gp.ndim)
         self.bounds = np.ascontiguousarray(np.asarray(bounds, dtype=np.float64).reshape(self.ndim, 2))
@@ -411,6 +415,10 @@ class GPUWalkBackend:
             raise ValueError("logp_map must be None, 'nlog' or 'log'")
         self.logp_map = logp_map
         self.host_loglike = host_loglike
+        self.normal_prior = None
+        if normal_prior is not None:
+            self.normal_prior = tuple(np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(self.ndim))
+                                      for v in normal_prior)
         self.host_calls = 0
         self._ns = None
 
@@ -428,6 +436,12 @@ class GPUWalkBackend:
                                               C.byref(ns)), "alabi_ns_create")
         kind = {None: 0, "nlog": 1, "log": 2}[self.logp_map]
         _lib.check(_lib.lib().alabi_ns_set_logp(ns, self.logp_affine[0], self.logp_affine[1], kind), "alabi_ns_set_logp")
+        if self.normal_prior is not None:
+            st = _lib.lib().alabi_ns_set_normal_prior(ns, _lib.host_doubles(self.normal_prior[0]),
+                                                      _lib.host_doubles(self.normal_prior[1]))
+            if st != _lib.OK:
+                _lib.destroy(ns, "alabi_ns_destroy")
+                _lib.check(st, "alabi_ns_set_normal_prior")
         self._ns = ns
         return ns
 
@@ -451,6 +465,15 @@ class GPUWalkBackend:
 
     def theta(self, u):
         return np.asarray(self.to_theta(np.asarray(u)), dtype=np.float64).reshape(-1, self.ndim)
+
+    def transform(self, u):
+        """Scaled coordinates [n,d] (before the length scales) of the cube points ``u`` [n,d], by the kernels' own map."""
+        ns, dev = self._ensure(), _dev()
+        ud = torch.as_tensor(np.ascontiguousarray(np.asarray(u, dtype=np.float64).reshape(-1, self.ndim)), device=dev)
+        x = torch.empty_like(ud)
+        _lib.check(_lib.lib().alabi_ns_transform(ns, _lib.ptr(ud), int(ud.shape[0]), _lib.ptr(x), _lib.current_stream()),
+                   "alabi_ns_transform")
+        return x.cpu().numpy()
 
     def _host(self, up):
         inside = np.all((up > 0.0) & (up < 1.0), axis=1)

@@ -4,7 +4,9 @@
 ``PosteriorPlan`` they get to ``EnsembleSampler`` / ``GPUWalkBackend``.  Host only: no GPU, no shared library.  The kernels fold
   * a theta scaler that is an affine map per dimension (``_affine_map``): the walkers move in scaled theta;
   * a y scaler whose inverse is affine with a positive slope, or ``nlog_scaler`` / ``log_scaler`` (``_y_unscale_kind``);
-  * the box prior; for the ensemble sampler ``lnprior_normal`` on top of it; for nested sampling the uniform prior transform.
+  * the box prior; for the ensemble sampler ``lnprior_normal`` on top of it; for nested sampling the uniform prior transform and
+    ``prior_transform_normal`` (the inverse normal CDF on the coordinates with a Gaussian prior; no Jacobian term: in nested
+    sampling the prior enters through the transform alone, so it folds behind the nlog / log y maps too).
 Everything else is a host callable on a batch of points in the sampler's coordinates ([n,d] -> [n])."""
 from __future__ import annotations
 
@@ -25,7 +27,8 @@ class PosteriorPlan:
     t_add: np.ndarray = None       # the identity with a host likelihood)
     logp_affine: tuple = (1.0, 0.0)    # (scale, shift) applied to the GP mean on the device
     logp_map: str = None           # "nlog" or "log": the non-affine y un-scaling applied after logp_affine
-    normal_prior: tuple = None     # (mean[d], std[d]) in scaled theta, NaN = no normal on that coordinate
+    normal_prior: tuple = None     # (mean[d], std[d]) in scaled theta, NaN = no normal on that coordinate (nested: std is signed,
+                                   # negative under a decreasing theta scaler)
     host_prior: Callable = None    # sampler coordinates [n,d] -> [n]
     host_like: Callable = None     # sampler coordinates [n,d] -> [n]
 
@@ -116,6 +119,25 @@ def _uniform_prior_box(prior_transform, ndim):
     return None
 
 
+def _normal_prior_transform(prior_transform, ndim):
+    """(box [ndim, 2], mean [ndim], std [ndim]) of ``partial(ut.prior_transform_normal, bounds=B, data=D)`` (keywords only, the
+    rule of ``_uniform_prior_box``), NaN mean / std on the coordinates whose data is ``(None, None)``; None for any other callable.
+    A normal coordinate with std <= 0 or a non-finite mean or std raises ValueError."""
+    f = getattr(prior_transform, "func", None)
+    kwp = dict(getattr(prior_transform, "keywords", None) or {})
+    if f is not ut.prior_transform_normal or set(kwp) != {"bounds", "data"} or getattr(prior_transform, "args", ()):
+        return None
+    box, data = np.asarray(kwp["bounds"], dtype=np.float64).reshape(ndim, 2), kwp["data"]
+    if len(data) != ndim:
+        raise ValueError(f"prior_transform_normal: data length ({len(data)}) must match the {ndim} dimensions")
+    mean = np.array([np.nan if dd[0] is None else float(dd[0]) for dd in data])
+    std = np.array([np.nan if dd[0] is None else float(dd[1]) for dd in data])
+    on = np.array([dd[0] is not None for dd in data])
+    if np.any(on & ~(np.isfinite(mean) & np.isfinite(std) & (std > 0))):
+        raise ValueError("prior_transform_normal: every (mean, std) must be finite with std > 0")
+    return box, mean, std
+
+
 def host_rows(fn, row_shape, to_theta=None):
     """[n,d] -> [n] with one call of ``fn`` per point.  ``row_shape`` is the argument shape the sampler promises: (1, -1) for the
     ensemble sampler, what lnprob hands to like_fn / prior_fn (core.py:2097-2098); (-1,) for nested sampling, as dynesty calls."""
@@ -168,19 +190,35 @@ def plan_ensemble(like_host, surrogate, prior_fn, bounds, theta_scaler, y_scaler
 
 def plan_nested(like_fn, surrogate, prior_transform, bounds, theta_scaler, y_scaler, _y):
     """Nested sampling's plan: the sampler moves in the unit cube.  Fused when ``like_fn`` is the surrogate, ``prior_transform`` is
-    the uniform one over a box and both scalers fold: ``box`` is then that box in scaled theta, lower / upper as the cube maps to
-    them.  Otherwise the host evaluates ``like_fn(prior_transform(u))`` and ``box`` is the cube."""
+    the uniform one over a box or ``partial(ut.prior_transform_normal, bounds=..., data=...)`` and both scalers fold: ``box`` is
+    then the box in scaled theta, lower / upper as the cube maps to them, and ``normal_prior`` (mean, std) in scaled theta for the
+    coordinates with a Gaussian prior (std negative under a decreasing theta scaler; None when there is none).  Otherwise the
+    host evaluates ``like_fn(prior_transform(u))`` and ``box`` is the cube; ``prior_transform_normal`` then takes a whole batch in
+    one call, any other callable is called row by row."""
     ndim = len(bounds)
-    theta_box = _uniform_prior_box(prior_transform, ndim)
+    theta_box, normal = _uniform_prior_box(prior_transform, ndim), None
+    batched = False
+    if theta_box is None:
+        normal = _normal_prior_transform(prior_transform, ndim)
+        if normal is not None:
+            theta_box, batched = normal[0], True
+            if not np.any(np.isfinite(normal[1])):
+                normal = None                                                    # all (None, None): the uniform transform
     folded = _fold_scalers(theta_scaler, y_scaler, _y, bounds) if (like_fn == surrogate and theta_box is not None) else None
     if folded is not None:
         (t_mult, t_add), logp_affine, logp_map = folded
         lo_t, hi_t = theta_box[:, 0], theta_box[:, 1]
-        return PosteriorPlan(box=np.stack([lo_t * t_mult + t_add, hi_t * t_mult + t_add], axis=1), theta_box=theta_box,
+        plan = PosteriorPlan(box=np.stack([lo_t * t_mult + t_add, hi_t * t_mult + t_add], axis=1), theta_box=theta_box,
                              to_theta=lambda u: lo_t + u * (hi_t - lo_t),        # prior_transform_uniform
                              logp_affine=logp_affine, logp_map=logp_map)
+        if normal is not None:
+            plan.normal_prior = (t_mult * normal[1] + t_add, t_mult * normal[2])
+            plan.to_theta = lambda u: np.asarray(prior_transform(np.atleast_2d(u)), dtype=np.float64)
+        return plan
 
     def to_theta(u):
+        if batched:                                              # prior_transform_normal: [n, d] in one call
+            return np.asarray(prior_transform(np.atleast_2d(u)), dtype=np.float64)
         return np.array([np.asarray(prior_transform(row), dtype=np.float64).reshape(-1) for row in np.atleast_2d(u)])
     return PosteriorPlan(box=np.tile([0.0, 1.0], (ndim, 1)), to_theta=to_theta,
                          host_like=host_likelihood(like_fn, surrogate, (-1,), to_theta))

@@ -3,6 +3,8 @@
 * scalers ``no_scaler`` / ``log_scaler`` / ``nlog_scaler`` (alabi/utility.py:45-72),
 * ``prior_sampler`` (utility.py:79-199; skopt is replaced by NumPy / scipy.stats.qmc),
 * ``lnprior_uniform`` / ``prior_transform_uniform`` (utility.py:218-367), ``logsubexp`` (:489-504),
+* ``prior_sampler_normal`` / ``lnprior_normal`` / ``prior_transform_normal`` (utility.py:202-215, 370-482): the three forms in
+  which the reference's examples hand Gaussian priors to the library,
 * the acquisition functions ``bape_utility`` / ``agp_utility`` / ``jones_utility`` with the
   reference's one-point signature ``f(theta, predict_gp, bounds)`` (utility.py:629-946),
 * ``minimize_objective`` multistart (utility.py:969-1163),
@@ -18,13 +20,14 @@ import warnings
 import numpy as np
 import torch
 from scipy.optimize import minimize
-from scipy.stats import norm, qmc
+from scipy.stats import norm, qmc, truncnorm
 from sklearn.preprocessing import FunctionTransformer
 
 from . import _lib
 
 __all__ = ["agp_utility", "bape_utility", "jones_utility", "assign_utility", "minimize_objective",
-           "prior_sampler", "lnprior_uniform", "lnprior_normal", "prior_transform_uniform", "logsubexp",
+           "prior_sampler", "prior_sampler_normal", "lnprior_uniform", "lnprior_normal", "prior_transform_uniform",
+           "prior_transform_normal", "logsubexp",
            "NewFunctionTransformer", "nlog_scaler", "log_scaler", "no_scaler",
            "utility_scan", "utility_eval_device", "grad_gp_mean_prediction", "grad_gp_var_prediction",
            "grad_agp_utility", "grad_bape_utility", "utility_value_and_grad", "polish_point"]
@@ -91,6 +94,26 @@ def prior_sampler(bounds=None, nsample=1, sampler="uniform", random_state=None):
     return lo + span * u
 
 
+def prior_sampler_normal(prior_data, bounds, nsample=1, random_state=None):
+    """Samples (nsample, ndim) of the prior of ``lnprior_normal``: a normal truncated to ``bounds[i]`` on the coordinates whose
+    ``prior_data[i] = (mean, std)`` is not ``(None, None)``, uniform over ``bounds[i]`` on the others (utility.py:202-215).
+    ``random_state`` (an addition): None draws from NumPy's global generator as the reference does, an int seeds a
+    ``RandomState``, a ``RandomState`` is used as it is -- as ``prior_sampler`` takes it."""
+    nsample = int(nsample)
+    if random_state is None:
+        rs = np.random.mtrand._rand
+    else:
+        rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
+    rvs = np.zeros((len(bounds), nsample))
+    for ii, b in enumerate(bounds):
+        if prior_data[ii][0] is not None:
+            mean, std = prior_data[ii]
+            rvs[ii] = truncnorm.rvs((b[0] - mean) / std, (b[1] - mean) / std, loc=mean, scale=std, size=nsample, random_state=rs)
+        else:
+            rvs[ii] = rs.uniform(low=b[0], high=b[1], size=nsample)
+    return rvs.T
+
+
 def lnprior_uniform(x, bounds):
     """0.0 strictly inside the open box, -inf otherwise (utility.py:218-275)."""
     b = np.asarray(bounds, dtype=np.float64)
@@ -121,6 +144,25 @@ def prior_transform_uniform(theta, bounds):
     if theta.shape[-1] != len(b):
         raise ValueError(f"Bounds length ({len(b)}) must match theta dimensions ({theta.shape[-1]})")
     return (b[:, 1] - b[:, 0]) * theta + b[:, 0]
+
+
+def prior_transform_normal(x, bounds, data):
+    """Unit hypercube -> theta under mixed priors (utility.py:381-482): coordinate i maps uniformly onto ``bounds[i]`` when
+    ``data[i] = (None, None)`` and through the inverse normal CDF ``norm.ppf(x_i, mean, std)`` when ``data[i] = (mean, std)``.
+    The normal is NOT truncated to the bounds, as in the reference.  ``x``: (ndim,) or (nsamples, ndim)."""
+    x = np.asarray(x, dtype=float)
+    if x.ndim not in (1, 2):
+        raise ValueError(f"x must be 1D or 2D array, got {x.ndim}D array with shape {x.shape}")
+    ndim = x.shape[-1]
+    if len(bounds) != ndim or len(data) != ndim:
+        raise ValueError(f"Bounds length ({len(bounds)}) and data length ({len(data)}) must match x dimensions ({ndim})")
+    pt = np.zeros(x.shape)
+    for i, b in enumerate(bounds):
+        if data[i][0] is None:
+            pt[..., i] = (b[1] - b[0]) * x[..., i] + b[0]
+        else:
+            pt[..., i] = norm.ppf(x[..., i], data[i][0], data[i][1])
+    return pt
 
 
 def logsubexp(x1, x2):

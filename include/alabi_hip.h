@@ -325,6 +325,14 @@ int alabi_ns_create(alabi_gp* gp, int d, const double* bounds /* host [d,2], sca
                     alabi_ns** out);
 int alabi_ns_destroy(alabi_ns* ns);
 int alabi_ns_set_logp(alabi_ns* ns, double scale, double shift, int map_kind /* 0 identity, 1 nlog, 2 log */);
+/* Independent normal priors on selected cube coordinates: the reference's prior_transform_normal
+ * (alabi/utility.py:381-482).  mean[d], std[d] on the HOST in the GP's scaled coordinates; non-finite mean = that
+ * coordinate keeps the uniform map over its box; std may be negative, std == 0 (or non-finite) is an error.
+ * x_k = mean_k + std_k * ndtri(u_k), not truncated to the box; u_k = 0 is evaluated at 2^-54.  Takes effect from the next call on. */
+int alabi_ns_set_normal_prior(alabi_ns* ns, const double* mean, const double* std);
+/* x_out [K,d]: the scaled coordinates (before the length scales and the centring) of cube points u [K,d], by the
+ * same device function the walks use. */
+int alabi_ns_transform(alabi_ns* ns, const double* u, int K, double* x_out, void* stream);
 /* n uniform points u_out [n,d] (dynesty's initial live points) and, if logl_out is not NULL, their logL [n]. */
 int alabi_ns_prior_draw(alabi_ns* ns, long long call, int walk_id0, int n, double* u_out, double* logl_out, void* stream);
 /* K independent walks of `walks` Metropolis steps from u0 [K,d] (logL logl0 [K]; NULL: evaluated first):

@@ -6,6 +6,10 @@ reference-shaped CPU leg (one oracle predict per likelihood call, as dynesty cal
     python tools/prof_nested.py walk       # only the walk kernel (the part to run under rocprofv3 --kernel-trace --stats)
     python tools/prof_nested.py slice      # ns_slice_kernel beside ns_walk_kernel (alternating, same process) at d = 10 and 24,
                                            # and run_dynesty at C3 size with sample="rwalk" / "rslice"
+    python tools/prof_nested.py --normal   # Gaussian priors: the walk and the slice kernel at N = 2000, d = 10, K = 64 / 256 with the
+                                           # uniform map and with a normal prior on every coordinate, three rounds each (the
+                                           # uniform rows also run on a tree without the feature, for a before / after), and the
+                                           # tutorial-sized run_dynesty with prior_transform_normal fused / as a host callable
 """
 import json
 import math
@@ -157,6 +161,97 @@ def slice_kernel(N, d, rounds=3, reps=10):
     be.close()
 
 
+def normal_prior(N=2000, d=10, rounds=3, reps=10):
+    """Per walk step and per link of the longest slice chain, uniform map against a normal prior on all d coordinates, in turn in
+    one process; the spread of a row over its rounds is the margin for comparing two rows (or two trees)."""
+    import inspect
+
+    from alabi_amd import HipGP, _lib
+    from alabi_amd.nested import GPUWalkBackend, default_slices
+    walks, slices = 25, default_slices(d)
+    X, y, h = make_problem(N, d, 0)
+    g = HipGP(d, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"])
+    g.compute(X)
+    box = np.array([[-3.0, 3.0]] * d)
+    priors = {"uniform": {}}
+    if "normal_prior" in inspect.signature(GPUWalkBackend.__init__).parameters:
+        priors["normal"] = {"normal_prior": (np.zeros(d), np.ones(d))}
+    lib, st = _lib.lib(), _lib.current_stream()
+    for K in (64, 256):
+        legs = []
+        for prior, kw in priors.items():
+            be = GPUWalkBackend(g, y, box, seed=1, to_theta=lambda u: u, **kw)
+            u, l = be.prior(0, 4096)
+            lstar = float(np.quantile(l, 0.5))
+            keep = np.flatnonzero(l > lstar)
+            idx = keep[np.arange(K) % len(keep)]
+            legs.append(dict(prior=prior, be=be, ns=be._ensure(), lstar=lstar, u0=torch.as_tensor(u[idx], device="cuda"),
+                             l0=torch.as_tensor(l[idx], device="cuda"),
+                             ch=torch.as_tensor(np.linalg.cholesky(np.cov(u.T)), device="cuda")))
+        uo, lo = torch.empty_like(legs[0]["u0"]), torch.empty_like(legs[0]["l0"])
+        cnt = torch.zeros(4 * K, dtype=torch.int32, device="cuda")
+
+        def launch(leg, move, call):
+            fn, n, name = (lib.alabi_ns_walk, walks, "alabi_ns_walk") if move == "walk" else (lib.alabi_ns_slice, slices, "alabi_ns_slice")
+            _lib.check(fn(leg["ns"], call, 0, _lib.ptr(leg["u0"]), _lib.ptr(leg["l0"]), K, leg["lstar"], _lib.ptr(leg["ch"]),
+                          0.5 if move == "walk" else 1.0, n, _lib.ptr(uo), _lib.ptr(lo), _lib.ptr(cnt), st), name)
+        for leg in legs:
+            for move in ("walk", "slice"):
+                launch(leg, move, 1)
+                launch(leg, move, 2)
+        torch.cuda.synchronize()
+        for rnd in range(rounds):
+            for move in ("walk", "slice"):
+                for leg in legs:
+                    evals, longest, dt = 0, 0, 0.0
+                    for i in range(reps):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        launch(leg, move, 100 + i)
+                        torch.cuda.synchronize()
+                        dt += time.perf_counter() - t0
+                        c = cnt.cpu().numpy()
+                        ev = c[K:2 * K] if move == "walk" else c[:K]
+                        evals += int(ev.sum())
+                        longest += int(ev.max()) if move == "slice" else walks
+                    emit(what="ns_" + move, prior=leg["prior"], N=N, d=d, K=K, round=rnd, path=leg["be"].last_path(),
+                         us_per_launch=dt / reps * 1e6, us_per_link_of_longest_chain=dt * 1e6 / longest,
+                         evals_per_launch=evals / reps)
+        for leg in legs:
+            leg["be"].close()
+
+
+def normal_prior_end_to_end(nlive=100, runs=3):
+    """The tutorial-sized run (2-D, dynamic) under a normal prior on theta_2: prior_transform_normal (fused where the tree has it)
+    against the same transform written by hand, which is a host callable."""
+    import tempfile
+    from functools import partial
+
+    from scipy.stats import norm
+
+    from alabi_amd import SurrogateModel
+    from alabi_amd import utility as ut
+    bounds = [(-4.0, 4.0)] * 2
+    sm = SurrogateModel(lnlike_fn=_gauss(2, 0), bounds=bounds, savedir=tempfile.mkdtemp(), verbose=False, random_state=0, cache=False)
+    sm.init_samples(ntrain=200)
+    sm.init_gp(hyperopt_method="ml", gp_nopt=1)
+
+    def by_hand(u):
+        return np.array([-4.0 + 8.0 * u[0], norm.ppf(u[1], 0.0, 1.0)])
+    transforms = {"by_hand": by_hand}
+    if hasattr(ut, "prior_transform_normal"):
+        transforms["prior_transform_normal"] = partial(ut.prior_transform_normal, bounds=bounds, data=[(None, None), (0.0, 1.0)])
+    for name, pt in transforms.items():
+        for run in range(runs + 1):                               # run 0: warm-up
+            t0 = time.perf_counter()
+            sm.run_dynesty(prior_transform=pt, mode="dynamic", sampler_kwargs={"nlive": nlive, "seed": 1 + run}, min_ess=0)
+            wall = time.perf_counter() - t0
+            r = sm.dynesty_results
+            if run:
+                emit(what="run_dynesty", config="tutorial_normal_prior", transform=name, path=sm.dynesty_path, nlive=nlive, run=run,
+                     wall_s=wall, niter=int(r.niter), ncall=int(r.ncall), logz=float(r.logz[-1]), logzerr=float(r.logzerr[-1]))
+
+
 def end_to_end_moves(d=10, ntrain=2000, nlive=500):
     import tempfile
 
@@ -220,6 +315,9 @@ def end_to_end(name, d, ntrain, nlive, mode, bounds):
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
     torch.cuda.set_device(0)
+    if what in ("--normal", "normal"):
+        normal_prior()
+        normal_prior_end_to_end()
     if what in ("all", "walk"):
         walk_kernel()
     if what == "slice":
