@@ -71,6 +71,7 @@ SIGNATURES = {
     "alabi_ens_surrogate": (_i, [_vp, _vp, _i, _vp, _vp]),
     "alabi_ens_propose": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "alabi_ens_accept": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "alabi_ens_set_moves": (_i, [_vp, _i, _pi, _pd, _pd, _pd]),
     "alabi_ens_set_stream": (_i, [_vp, _i]),
     "alabi_ens_last_path": (_i, [_vp, _pi]),
     "alabi_ens_group_plan": (_i, [_vp, _pi]),
@@ -88,6 +89,8 @@ SIGNATURES = {
     "alabi_ens_step_lists": (_i, [_vp, _i, _vp, _pi, _vp]),
     "alabi_ens_step_with_randoms": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _d, _vp, _vp]),
     "alabi_ens_export_draws": (_i, [_vp, _ll, _d, _vp, _pi, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "alabi_ens_export_move_draws": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "alabi_ens_step_with_randoms_de": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "alabi_ns_create": (_i, [_vp, _i, _pd, _ull, C.POINTER(_vp)]),
     "alabi_ns_destroy": (_i, [_vp]),
     "alabi_ns_set_logp": (_i, [_vp, _d, _d, _i]),

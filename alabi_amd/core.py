@@ -30,6 +30,7 @@ from . import gp_utils, mcmc_utils
 from . import posterior as post
 from . import utility as ut
 from .gp import HipGP, _dev
+from .moves import parse_moves
 from .sampler import EnsembleSampler
 
 __all__ = ["SurrogateModel", "CachedSurrogateLikelihood"]
@@ -945,6 +946,12 @@ class SurrogateModel(object):
           likelihood evaluated on the host as well (walkers then move in the original theta coordinates).
         ``opt_init=True`` starts the walkers around ``find_map()``.
 
+        ``sampler_kwargs["moves"]`` (the reference's "Custom proposal moves", core.py:2144): None for the stretch move, or
+        ``alabi_amd.moves.StretchMove`` / ``DEMove`` objects (emcee's own are recognised), a list of them, or a list of
+        (move, weight) pairs -- one move is chosen per step.  Multimodal posteriors want
+        ``[(DEMove(), 0.9), (DEMove(gamma0=1.0), 0.1)]``: the stretch move alone does not cross between separated modes.
+        Any other emcee move raises ``NotImplementedError``; a ``DEMove`` cannot be combined with ``"shard": True``.
+
         Several GPUs (the reference's parallel axis is a process pool handed to emcee, core.py:2300, :2322, built at :349-369;
         ``ncore`` / ``pool_method`` have no meaning here): run one process per GPU under ``torch.distributed`` (e.g.
         ``python -m torch.distributed.run --nproc-per-node 8 script.py``, backend "nccl" = RCCL) and have every rank make the
@@ -958,6 +965,10 @@ class SurrogateModel(object):
         from . import dist as adist
         rank, world = adist.world_info()
         kw = dict(sampler_kwargs)
+        move_set = parse_moves(kw.get("moves"), self.ndim)       # unsupported moves fail here, before anything runs
+        if kw.get("shard", False) and move_set is not None and move_set.has_de:
+            raise ValueError('sampler_kwargs={"shard": True} cannot run a DEMove: the sharded ensemble links one partner row per '
+                             'proposal')
         shard = bool(kw.pop("shard", False)) and bool(multi_proc) and world > 1
         replicas = bool(multi_proc) and world > 1 and not shard
         # ---- likelihood

@@ -526,6 +526,24 @@ static bool ens_draw_ahead_ready(alabi_ens* e) {
     return true;
 }
 
+static void free_move_buffers(MoveBuffers& m) {
+    if (m.cw2) (void)hipFree(m.cw2);
+    if (m.partner2) (void)hipFree(m.partner2);
+    if (m.move) (void)hipFree(m.move);
+    m = MoveBuffers{};
+}
+
+// The second-partner arrays of the records (first buffer set), allocated when a move set is first given or a DE step is injected.
+static int ensure_move_buffers(alabi_ens* e) {
+    if (e->mv.cw2) return ALABI_OK;
+    const size_t n = (size_t)e->chunk_cap * e->W * e->E;
+    hipError_t err = hipMalloc(&e->mv.cw2, n * sizeof(int));
+    if (err == hipSuccess) err = hipMalloc(&e->mv.partner2, n * sizeof(int));
+    if (err == hipSuccess) err = hipMalloc(&e->mv.move, (size_t)e->chunk_cap * e->E * sizeof(int));
+    if (err != hipSuccess) { free_move_buffers(e->mv); return hip_fail(err, "hipMalloc(move buffers)", __FILE__, __LINE__); }
+    return ALABI_OK;
+}
+
 static DrawBuffers offset_draws(const DrawBuffers& b, size_t off) {
     DrawBuffers r = b;
     r.order += off; r.cw += off; r.zz += off; r.lnfac += off; r.lnu += off;
@@ -595,6 +613,7 @@ int alabi_ens_destroy(alabi_ens* e) {
     if (e->graph_exec) (void)hipGraphExecDestroy(e->graph_exec);
     free_draws(e->draws);
     free_draws(e->draws2);
+    free_move_buffers(e->mv);
     if (e->side_stream) (void)hipStreamDestroy(e->side_stream);
     if (e->ev_free) (void)hipEventDestroy(e->ev_free);
     if (e->ev_drawn) (void)hipEventDestroy(e->ev_drawn);
@@ -639,6 +658,31 @@ int alabi_ens_set_logp_map(alabi_ens* e, int kind) {
     e->ymap = kind;
     e->settings_gen++;
     if (e->graph_exec) { (void)hipGraphExecDestroy(e->graph_exec); e->graph_exec = nullptr; }   // captured launches carry the old value
+    return ALABI_OK;
+}
+
+int alabi_ens_set_moves(alabi_ens* e, int n, const int* kind, const double* cum, const double* p0, const double* p1) {
+    if (!e || n < 0 || n > ALABI_MAX_MOVES || (n > 0 && (!kind || !cum || !p0 || !p1))) return ALABI_BAD_ARGUMENT;
+    MoveTable mt{};
+    bool de = false;
+    double prev = 0.0;
+    for (int k = 0; k < n; ++k) {
+        if (!(cum[k] >= prev) || !std::isfinite(cum[k])) return ALABI_BAD_ARGUMENT;   // cumulative weights do not decrease
+        prev = cum[k];
+        if (kind[k] == 0) { if (!(p0[k] > 1.0) || !std::isfinite(p0[k])) return ALABI_BAD_ARGUMENT; }          // stretch: a > 1
+        else if (kind[k] == 1) { if (!std::isfinite(p0[k]) || !std::isfinite(p1[k])) return ALABI_BAD_ARGUMENT; de = true; }
+        else return ALABI_BAD_ARGUMENT;
+        mt.kind[k] = kind[k]; mt.cum[k] = cum[k]; mt.p0[k] = p0[k]; mt.p1[k] = p1[k];
+    }
+    if (n > 0 && !(prev > 0.0)) return ALABI_BAD_ARGUMENT;
+    if (de && e->W < 4) return ALABI_BAD_ARGUMENT;       // two distinct partners in a complementary list of W / 2 walkers
+    if (n > 0) { const int st = ensure_move_buffers(e); if (st != ALABI_OK) return st; }
+    mt.n = n;
+    e->moves = mt;
+    e->has_de = de;
+    e->drawn_n = 0;                                      // records drawn under the old move set are not the new set's
+    e->settings_gen++;
+    if (e->graph_exec) { (void)hipGraphExecDestroy(e->graph_exec); e->graph_exec = nullptr; }   // captured draw launches carry the old table
     return ALABI_OK;
 }
 
@@ -733,6 +777,7 @@ static int enqueue_chunk(alabi_ens* e, HalfArgs h, int n, double a, hipStream_t 
     const size_t WT = (size_t)e->W * e->E;
     for (int t = 0; t < n; ++t) {
         h.rec = offset_draws(e->draws, (size_t)t * WT);
+        h.cw2 = e->has_de ? e->mv.cw2 + (size_t)t * WT : nullptr;
         h.local_t = t; h.part_begin = 0;
         h.split = 0;
         if ((st = launch_ens_half_args(e, h, n0, s)) != ALABI_OK) return st;
@@ -762,9 +807,11 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
     // ens_stream_kernel takes ceil(W/2 / stream_grid) proposals per workgroup one after the other (2.0 / 3.7 / 7.1 us per half step at
     // 1 / 2 / 4 of them, N = 2000); from four on the group kernel is ahead (5.3 us at W = 2048: 1.9e8 against 1.4e8 samples/s)
     const bool crowded = can_stream && e->stream_grid > 0 && ((e->W + 1) / 2 + e->stream_grid - 1) / e->stream_grid >= 4;
-    const bool use_group = e->stream_ok && s != nullptr && !group_off && (group_pref || !can_stream || crowded) && ens_group_fits(e) &&
+    const bool use_group = !e->has_de && e->stream_ok && s != nullptr && !group_off && (group_pref || !can_stream || crowded) && ens_group_fits(e) &&
                            ens_group_buffers(e, s);
-    if (e->stream_ok && s != nullptr && (can_stream || use_group)) {
+    // A differential-evolution record reads two partner rows: the persistent kernels hand one over, so such a move set runs
+    // with one launch per half step (and its graph replay).  Stretch-only sets differ in the draw kernel alone.
+    if (!e->has_de && e->stream_ok && s != nullptr && (can_stream || use_group)) {
         e->last_path = use_group ? 3 : 1;
         // ens_stream_kernel's chunks take the step counters by value and their epilogue leaves run_state as the other paths
         // would (no upload, no host synchronisation in front of the first launch); the history is trusted to hold the
@@ -879,6 +926,7 @@ int alabi_ens_half_step(alabi_ens* e, double* coords, double* logp, int t, int s
     const int nS = split == 0 ? h.n0 : e->W - h.n0;
     if (part_begin < 0 || part_end > nS || part_begin > part_end) return ALABI_BAD_ARGUMENT;
     h.rec = offset_draws(e->draws, (size_t)t * e->W);
+    h.cw2 = e->has_de ? e->mv.cw2 + (size_t)t * e->W : nullptr;
     h.local_t = t; h.split = split; h.part_begin = part_begin; h.n_accept = n_accept;
     return launch_ens_half_args(e, h, part_end - part_begin, as_stream(stream));
 }
@@ -888,7 +936,7 @@ namespace alabi {
 int ens_sync_consts(alabi_ens* e, hipStream_t s) { return sync_consts(e, s); }
 int alabi_ens_half_step_hist(alabi_ens* e, const double* coords, const double* logp, int t, int split, int part_begin, int part_end,
                              const double* shist, double* out, hipStream_t s) {
-    if (!e || t < 0 || t >= e->drawn_n || e->E != 1 || !shist || !out) return ALABI_BAD_ARGUMENT;
+    if (!e || t < 0 || t >= e->drawn_n || e->E != 1 || !shist || !out || e->has_de) return ALABI_BAD_ARGUMENT;
     int st = sync_consts(e, s);
     if (st != ALABI_OK) return st;
     HalfArgs h = base_args(e, const_cast<double*>(coords), const_cast<double*>(logp));
@@ -909,6 +957,7 @@ int alabi_ens_propose(alabi_ens* e, const double* coords, int t, int split, int 
     HalfArgs h = base_args(e, const_cast<double*>(coords), nullptr);
     const int nS = split == 0 ? h.n0 : e->W - h.n0;
     h.rec = offset_draws(e->draws, (size_t)t * e->W);
+    h.cw2 = e->has_de ? e->mv.cw2 + (size_t)t * e->W : nullptr;
     h.local_t = t; h.split = split; h.part_begin = 0;
     return launch_ens_propose(e, h, nS, gate_box, q, like, as_stream(stream));
 }
@@ -949,6 +998,35 @@ int alabi_ens_step_with_randoms(alabi_ens* e, double* coords, double* logp, cons
     if ((st = launch_ens_half_args(e, h, n0, s)) != ALABI_OK) return st;
     h.split = 1;
     return launch_ens_half_args(e, h, e->W - n0, s);
+}
+
+int alabi_ens_step_with_randoms_de(alabi_ens* e, double* coords, double* logp, const int* order, int n0, const int* j1,
+                                   const int* j2, const double* gamma, const double* u_acc, long long* n_accept, void* stream) {
+    if (!e || !coords || !logp || !order || !j1 || !j2 || !gamma || !u_acc || n0 < 0 || n0 > e->W || e->E != 1)
+        return ALABI_BAD_ARGUMENT;
+    if (!e->gp->computed || !e->gp->has_alpha) return ALABI_NOT_COMPUTED;
+    hipStream_t s = as_stream(stream);
+    int st;
+    if ((st = sync_consts(e, s)) != ALABI_OK) return st;
+    if ((st = ensure_move_buffers(e)) != ALABI_OK) return st;
+    if ((st = launch_ens_prep_de(e, order, n0, j1, j2, gamma, u_acc, s)) != ALABI_OK) return st;
+    e->drawn_n = 0;  // row 0 of the draw buffers now holds caller data
+    HalfArgs h = base_args(e, coords, logp);
+    h.rec = e->draws; h.cw2 = e->mv.cw2; h.n0 = n0; h.n_accept = n_accept; h.local_t = 0; h.part_begin = 0;
+    h.split = 0;
+    if ((st = launch_ens_half_args(e, h, n0, s)) != ALABI_OK) return st;
+    h.split = 1;
+    return launch_ens_half_args(e, h, e->W - n0, s);
+}
+
+int alabi_ens_export_move_draws(alabi_ens* e, int* move, int* j2, double* gamma, void* stream) {
+    if (!e || !move || !j2 || !gamma || e->drawn_n < 1 || !e->mv.cw2) return ALABI_BAD_ARGUMENT;
+    hipStream_t s = as_stream(stream);
+    const size_t WT = (size_t)e->W * e->E;
+    ALABI_HIP_CHECK(hipMemcpyAsync(move, e->mv.move, (size_t)e->E * sizeof(int), hipMemcpyDeviceToDevice, s));
+    ALABI_HIP_CHECK(hipMemcpyAsync(j2, e->mv.partner2, WT * sizeof(int), hipMemcpyDeviceToDevice, s));
+    ALABI_HIP_CHECK(hipMemcpyAsync(gamma, e->draws.zz, WT * sizeof(double), hipMemcpyDeviceToDevice, s));
+    return ALABI_OK;
 }
 
 int alabi_ens_export_draws(alabi_ens* e, long long step, double a, int* order, int* n0, double* u_z, int* partner,

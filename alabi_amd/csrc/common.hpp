@@ -113,8 +113,8 @@ namespace alabi {
 struct DrawBuffers {
     int* order;      // global walker id at each list position
     int* cw;         // global id of the partner walker drawn for that position
-    double* zz;      // stretch factor z
-    double* lnfac;   // (d-1) ln z
+    double* zz;      // stretch factor z (differential-evolution record: the step size gamma)
+    double* lnfac;   // (d-1) ln z (differential-evolution record: 0)
     double* lnu;     // ln u'
     int* partner;    // raw partner index into the complementary list (by list position)
     double* u_z;     // raw uniforms (by list position)
@@ -122,6 +122,25 @@ struct DrawBuffers {
     unsigned long long* packed;   // 4 words per list position: walker | partner << 32, zz, lnfac, lnu (persistent kernel)
     int* pos_of;     // list position (0..W-1 within the ensemble) of every walker, keyed by global walker id (inverse of `order`)
     unsigned long long* link;     // group kernel: 2 words per list position, where the two rows the proposal reads were produced (ens_link_kernel)
+};
+
+// Proposal moves (emcee's `moves=`): one move per step and ensemble, chosen by ens_draw_kernel from cumulative weights.
+//   kind 0 StretchMove: p0 = a.   kind 1 DEMove: p0 = gamma0 (mean step), p1 = sigma (its relative scatter).
+// n = 0 stands for the default, one stretch move with the `a` of the call.
+#define ALABI_MAX_MOVES 8
+struct MoveTable {
+    int n;
+    int kind[ALABI_MAX_MOVES];
+    double cum[ALABI_MAX_MOVES];   // np.cumsum(w / w.sum()), formed on the host
+    double p0[ALABI_MAX_MOVES], p1[ALABI_MAX_MOVES];
+};
+// What a differential-evolution record carries beyond DrawBuffers (kept apart from it: the persistent kernels take DrawBuffers by
+// value and know one partner only).  A DE record reuses the stretch record's slots -- cw = C[j1], zz = gamma, lnfac = 0 -- and adds
+// the second partner.  Allocated when a move set is given (alabi_ens_set_moves); null pointers are not written.
+struct MoveBuffers {
+    int* cw2;        // [chunk_cap, E, W] global id of the second partner C[j2] by list position; -1: a stretch record
+    int* partner2;   // [chunk_cap, E, W] raw j2 into the complementary list (-1: stretch), for export / tests
+    int* move;       // [chunk_cap, E] index of the step's move
 };
 }  // namespace alabi
 
@@ -173,6 +192,11 @@ struct alabi_ens {
     long long settings_gen = 0;          // bumped by every setter that changes what captured launches carry (graph keys)
     long long serial = 0;                // unique per handle for the life of the process (a new handle at an old address is not the old one)
     int group_plan[8] = {0};  // blocking of the last group-kernel launch: Q, G, NG, RT, tpm, ltw, KS, LDS bytes (alabi_ens_group_plan)
+    // proposal moves (alabi_ens_set_moves): the table the draw kernel chooses from, whether it holds a DE move (then every run
+    // takes the launch-per-half-step path, whose kernels read the second partner row), and the records' second-partner arrays
+    alabi::MoveTable moves{};
+    bool has_de = false;
+    alabi::MoveBuffers mv{};
 };
 
 namespace alabi {
@@ -258,11 +282,15 @@ struct HalfArgs {
     // (coords, logp, accepted) of proposal blockIdx.x goes to sout + blockIdx.x (d + 2) and coords / logp are left alone
     const double* shist = nullptr;
     double* sout = nullptr;
+    // differential-evolution records (MoveBuffers::cw2 offset to the step): set -> the kernels' two-partner instantiations run
+    const int* cw2 = nullptr;
 };
 int launch_ens_draw(alabi_ens* e, int nsteps, double a, hipStream_t s);
 int launch_ens_draw_at(alabi_ens* e, const DrawBuffers& into, int nsteps, double a, bool from_state, long long step0, hipStream_t s);   // first step: run_state[0], or step0 by value
 int launch_ens_prep(alabi_ens* e, const int* order, int n0, const double* u_z, const int* partner,
                     const double* u_acc, double a, hipStream_t s);
+int launch_ens_prep_de(alabi_ens* e, const int* order, int n0, const int* j1, const int* j2, const double* gamma,
+                       const double* u_acc, hipStream_t s);
 int launch_ens_half_args(alabi_ens* e, const HalfArgs& args, int nblocks, hipStream_t s);
 int launch_ens_lnprob(alabi_ens* e, const double* coords, int nwalkers, double* logp, int gate_box, hipStream_t s);
 int launch_ens_propose(alabi_ens* e, const HalfArgs& args, int nblocks, int gate_box, double* q, double* like, hipStream_t s);

@@ -9,6 +9,11 @@
 //   active set S: z = ((a-1)u+1)^2/a, partner r = randint(|C|), q = C[r] - (C[r]-S_k) z,
 //   accept iff (d-1) ln z + lnp(q) - lnp(S_k) > ln u'.
 //
+// Moves (emcee's moves=, alabi_ens_set_moves): one move per step and ensemble out of a table of stretch and differential-
+// evolution moves (emcee 3 moves/de.py: q = S_k + gamma (C[j2] - C[j1]), j1 != j2, gamma = gamma0 (1 + sigma n), log factor 0).
+// A DE record uses the stretch record's slots plus one second-partner id (write_de_record); the half-step, multi-proposal and
+// propose kernels have a second instantiation that reads it (tests/de_move_numpy.py is the CPU statement).
+//
 // E independent ensembles of W walkers ("independent chains") can share every launch: walker
 // ids are global (e*W + i), lists are per-ensemble segments, blockIdx.y is the ensemble.
 //
@@ -36,23 +41,36 @@
 
 namespace alabi {
 
+// One proposal record, in the arrays the launch-per-half-step kernels read and in one 32-byte line for the persistent kernel.
+__device__ inline void store_record(const DrawBuffers& b, size_t pos, int wid, int cw, double zz, double lnfac, double lnu) {
+    b.order[pos] = wid;
+    b.cw[pos] = cw;
+    b.zz[pos] = zz;
+    b.lnfac[pos] = lnfac;
+    b.lnu[pos] = lnu;
+    unsigned long long* pk = b.packed + 4 * pos;
+    pk[0] = (unsigned long long)(unsigned)wid | ((unsigned long long)(unsigned)cw << 32);
+    pk[1] = (unsigned long long)__double_as_longlong(zz);
+    pk[2] = (unsigned long long)__double_as_longlong(lnfac);
+    pk[3] = (unsigned long long)__double_as_longlong(lnu);
+}
+
 // Proposal record of list position `pos` (walker id wid = order[pos]) from raw draws keyed by
 // walker id.  z = ((a-1) u + 1)^2 / a in NumPy's operation order (no contraction).
 __device__ inline void write_record(const DrawBuffers& b, size_t pos, int wid, int cw, double u_z, double u_acc,
                                     double a, int d) {
     const double t1 = (a - 1.0) * u_z + 1.0;
     const double zz = (t1 * t1) / a;
-    const double lnfac = ((double)d - 1.0) * log(zz), lnu = log(u_acc);
-    b.order[pos] = wid;
-    b.cw[pos] = cw;
-    b.zz[pos] = zz;
-    b.lnfac[pos] = lnfac;
-    b.lnu[pos] = lnu;
-    unsigned long long* pk = b.packed + 4 * pos;   // the same record in one 32-byte line for the persistent kernel
-    pk[0] = (unsigned long long)(unsigned)wid | ((unsigned long long)(unsigned)cw << 32);
-    pk[1] = (unsigned long long)__double_as_longlong(zz);
-    pk[2] = (unsigned long long)__double_as_longlong(lnfac);
-    pk[3] = (unsigned long long)__double_as_longlong(lnu);
+    store_record(b, pos, wid, cw, zz, ((double)d - 1.0) * log(zz), log(u_acc));
+}
+
+// Differential-evolution record (emcee 3 moves/de.py: q = s + gamma (C[j2] - C[j1]), log factor 0) in the slots of a stretch
+// record: cw = C[j1], zz = gamma, lnfac = 0.0 -- the accept test lnfac + lp_new - lp_old > ln u' needs no second form -- and the
+// second partner beside it.  A stretch record is marked by cw2 = -1.
+__device__ inline void write_de_record(const DrawBuffers& b, const MoveBuffers& mv, size_t pos, int wid, int cw, int cw2, int j2,
+                                       double gamma, double u_acc) {
+    store_record(b, pos, wid, cw, gamma, 0.0, log(u_acc));
+    if (mv.cw2) { mv.cw2[pos] = cw2; mv.partner2[pos] = j2; }
 }
 
 // grid = (steps of the chunk, ensembles); dynamic LDS = Wp * 12 + 1024 bytes, Wp = W rounded up to a power of two.
@@ -60,8 +78,8 @@ __device__ inline void write_record(const DrawBuffers& b, size_t pos, int wid, i
 // LDS -- O(W log^2 W) compare-exchanges instead of the W^2 comparisons of the first version (0.21 ms per 1024-step chunk at
 // 1024 walkers, 0.62 ms at 2048: 4 % of the C4 run) -- then the two ordered lists by a prefix count over the labels.
 __global__ void __launch_bounds__(256)
-ens_draw_kernel(unsigned long long seed, const long long* __restrict__ run_state, long long step_off, int W, int Wp, int d, double a,
-                DrawBuffers b) {
+ens_draw_kernel(unsigned long long seed, const long long* __restrict__ run_state, long long step_off, int W, int Wp, int d, MoveTable mt,
+                DrawBuffers b, MoveBuffers mv) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint64_t* keys = reinterpret_cast<uint64_t*>(smem);                       // [Wp]; after the sort: label[W], olist[W]
     uint32_t* ids = reinterpret_cast<uint32_t*>(smem + (size_t)Wp * 8);       // [Wp]
@@ -133,6 +151,23 @@ ens_draw_kernel(unsigned long long seed, const long long* __restrict__ run_state
         }
     }
     __syncthreads();
+    // The step's move, one per step and ensemble as in emcee: stream 3 at the ensemble's walker 0, index = #{k: cum[k] <= u}
+    // (what np.searchsorted(cum, u, side="right") returns), clipped.  The table is read with constant indices only: it lives in
+    // the kernel arguments, and a variable index would copy it to scratch memory.
+    int mi = 0;
+    if (mt.n > 1) {
+        philox4x32_10(s_lo, s_hi, g0, 3u, k0, k1, r);
+        const double um = u53(r[0], r[1]);
+#pragma unroll
+        for (int k = 0; k < ALABI_MAX_MOVES; ++k) mi += (k < mt.n && mt.cum[k] <= um) ? 1 : 0;
+        if (mi > mt.n - 1) mi = mt.n - 1;
+    }
+    int kind = mt.kind[0];
+    double mp0 = mt.p0[0], mp1 = mt.p1[0];
+#pragma unroll
+    for (int k = 1; k < ALABI_MAX_MOVES; ++k)
+        if (k == mi) { kind = mt.kind[k]; mp0 = mt.p0[k]; mp1 = mt.p1[k]; }
+    if (tid == 0 && mv.move) mv.move[(size_t)blockIdx.x * E + e] = mi;
     for (int pos = tid; pos < W; pos += 256) {
         const int i = olist[pos];
         const int li = pos >= n0;
@@ -141,13 +176,30 @@ ens_draw_kernel(unsigned long long seed, const long long* __restrict__ run_state
         const uint64_t nc = li ? (uint64_t)n0 : (uint64_t)(W - n0);
         const int pr = (int)(((uint64_t)r[2] * nc) >> 32);
         const int cw = olist[(li ? 0 : n0) + pr];
+        const uint32_t r3 = r[3];
         philox4x32_10(s_lo, s_hi, g0 + (uint32_t)i, 2u, k0, k1, r);
         const double ua = u53(r[0], r[1]);
+        // streams 0-2 and what is exported of them do not depend on the move
         b.partner[base + pos] = pr;
         b.u_z[base + pos] = uz;
         b.u_acc[base + pos] = ua;
         b.pos_of[base + i] = pos;
-        write_record(b, base + pos, (int)g0 + i, (int)g0 + cw, uz, ua, a, d);
+        if (kind == 0) {
+            write_record(b, base + pos, (int)g0 + i, (int)g0 + cw, uz, ua, mp0, d);
+            if (mv.cw2) { mv.cw2[base + pos] = -1; mv.partner2[base + pos] = -1; }
+        } else {
+            // j1 = pr and j2 != j1 from the fourth word: uniform over the nc (nc - 1) ordered pairs (emcee's _get_nondiagonal_pairs);
+            // nc >= 2 is checked where the moves are set
+            const int j2p = (int)(((uint64_t)r3 * (nc - 1)) >> 32);
+            const int j2 = j2p + (j2p >= pr ? 1 : 0);
+            const int cw2 = olist[(li ? 0 : n0) + j2];
+            // gamma = g0 (1 + sigma n), n standard normal by Box-Muller from stream 4
+            philox4x32_10(s_lo, s_hi, g0 + (uint32_t)i, 4u, k0, k1, r);
+            const double u1 = u53(r[0], r[1]), u2 = u53(r[2], r[3]);
+            const double nrm = sqrt(-2.0 * log(1.0 - u1)) * cos(6.283185307179586 * u2);
+            const double gamma = mp0 * (1.0 + mp1 * nrm);
+            write_de_record(b, mv, base + pos, (int)g0 + i, (int)g0 + cw, (int)g0 + cw2, j2, gamma, ua);
+        }
     }
 }
 
@@ -173,6 +225,27 @@ ens_prep_kernel(const int* __restrict__ order, int n0, int W, const double* __re
         }
     }
     write_record(b, pos, wid, cw, uz, ua, a, d);
+}
+
+// The same for differential-evolution records: j1 / j2 index the complementary list (j1 != j2), gamma is the step size.
+__global__ void __launch_bounds__(256)
+ens_prep_de_kernel(const int* __restrict__ order, int n0, int W, const int* __restrict__ j1, const int* __restrict__ j2,
+                   const double* __restrict__ gamma, const double* __restrict__ u_acc, DrawBuffers b, MoveBuffers mv) {
+    const int pos = blockIdx.x * 256 + threadIdx.x;
+    if (pos >= W) return;
+    const int w = order[pos];
+    const int li = pos >= n0;
+    const int nC = li ? n0 : W - n0;
+    int wid = -1, cw = -1, cw2 = -1, jj = -1;
+    double g = 0.0, ua = 0.5;
+    if ((unsigned)w < (unsigned)W) {
+        const int a1 = j1[w], a2 = j2[w];
+        if ((unsigned)a1 < (unsigned)nC && (unsigned)a2 < (unsigned)nC && a1 != a2) {
+            const int c1 = order[(li ? 0 : n0) + a1], c2 = order[(li ? 0 : n0) + a2];
+            if ((unsigned)c1 < (unsigned)W && (unsigned)c2 < (unsigned)W) { wid = w; cw = c1; cw2 = c2; jj = a2; g = gamma[w]; ua = u_acc[w]; }
+        }
+    }
+    write_de_record(b, mv, pos, wid, cw, cw2, jj, g, ua);
 }
 
 // Normal-prior term of coordinate `lane` (< d) of a proposal, summed over the wave: lanes >= d contribute 0.
@@ -209,9 +282,16 @@ __device__ inline double normal_prior_sum(const double* pmean, const double* pis
     return lane_bcast(wave_sum_dpp(t), 63);
 }
 
-template <int D, bool GENERIC>
-__global__ void __launch_bounds__(1024)
-ens_half_kernel(HalfArgs p) {
+// The proposal of a record from the rows it names, in NumPy's operation order (the library is built without contraction):
+// stretch q = c - (c - s) z; differential evolution q = s + gamma (c2 - c), c = C[j1], c2 = C[j2] (diff = np.diff(c[pairs])).
+__device__ inline double propose_coord(bool de, double sv, double cv, double c2v, double zz) {
+    return de ? sv + zz * (c2v - cv) : cv - (cv - sv) * zz;
+}
+
+// DE: the instantiation that reads the records' second partner (HalfArgs::cw2) and branches, workgroup-uniformly, on the
+// record's kind; without it the code is the stretch move's alone.
+template <int D, bool GENERIC, bool DE>
+__device__ __forceinline__ void ens_half_body(const HalfArgs& p) {
     __shared__ double q_s[ALABI_MAX_DIM], qs_s[ALABI_MAX_DIM], old_s[ALABI_MAX_DIM];
     __shared__ double scratch[16];
     const int tid = threadIdx.x, T = blockDim.x;
@@ -235,10 +315,13 @@ ens_half_kernel(HalfArgs p) {
     if (w < 0) return;  // inert record (range-checked test input); workgroup-uniform
     const int cw = p.rec.cw[pos];
     const double zz = p.rec.zz[pos];
+    const int cw2 = DE ? p.cw2[pos] : -1;         // second partner of a differential-evolution record, -1: a stretch record
+    const bool de = DE && cw2 >= 0;
     // where the two rows live: in place (coords / logp), or -- sharded ensemble -- in the history of published rows
     const double* own_c = p.coords + (size_t)w * p.d;
     const double* own_lp = p.logp + w;
     const double* par_c = p.coords + (size_t)cw * p.d;
+    const double* par2_c = p.coords + (size_t)(de ? cw2 : cw) * p.d;
     if (p.shist) {
         const unsigned long long lw = p.rec.link[2 * pos];
         const int so = (int)(unsigned)(lw & 0xffffffffull), sp = (int)(unsigned)(lw >> 32);
@@ -256,7 +339,7 @@ ens_half_kernel(HalfArgs p) {
         if (tid < p.d) {
             const double cv = par_c[tid];
             const double sv = own_c[tid];
-            qv = cv - (cv - sv) * zz;
+            qv = DE ? propose_coord(de, sv, cv, par2_c[tid], zz) : cv - (cv - sv) * zz;
             ok = (qv > lo[tid]) && (qv < hi[tid]);
             q_s[tid] = qv; old_s[tid] = sv;
             qv *= inv_len[tid];
@@ -351,13 +434,20 @@ ens_half_kernel(HalfArgs p) {
     }
 }
 
+template <int D, bool GENERIC>
+__global__ void __launch_bounds__(1024)
+ens_half_kernel(HalfArgs p) { ens_half_body<D, GENERIC, false>(p); }
+
+template <int D, bool GENERIC>
+__global__ void __launch_bounds__(1024)
+ens_half_de_kernel(HalfArgs p) { ens_half_body<D, GENERIC, true>(p); }
+
 // NP proposals of the same half step per workgroup: the training set is streamed ONCE per workgroup and used for all of them.
 // With more proposals than CUs (W/2 > 256, or E ensembles) ens_half_kernel is bound by L2 -> CU bandwidth: every workgroup
 // pulls the whole X (440 KB at N = 5000, d = 10) for one proposal.  Per proposal the arithmetic, the lane -> point map and the
 // reduction order are those of ens_half_kernel with the same block size, so the two kernels agree bit for bit.
-template <int D, bool GENERIC, int NP>
-__global__ void __launch_bounds__(512)
-ens_half_multi_kernel(HalfArgs p) {
+template <int D, bool GENERIC, int NP, bool DE>
+__device__ __forceinline__ void ens_half_multi_body(const HalfArgs& p) {
     __shared__ double q_s[NP][ALABI_MAX_DIM], qs_s[NP][ALABI_MAX_DIM], old_s[NP][ALABI_MAX_DIM];
     __shared__ double scratch[NP][16];
     __shared__ int ok_s[NP], w_s[NP];
@@ -384,7 +474,10 @@ ens_half_multi_kernel(HalfArgs p) {
                     const double zz = p.rec.zz[pos];
                     const double cv = p.coords[(size_t)cw * p.d + k];
                     const double sv = p.coords[(size_t)w * p.d + k];
-                    qv = cv - (cv - sv) * zz;
+                    if (DE) {
+                        const int cw2 = p.cw2[pos];
+                        qv = propose_coord(cw2 >= 0, sv, cv, p.coords[(size_t)(cw2 >= 0 ? cw2 : cw) * p.d + k], zz);
+                    } else qv = cv - (cv - sv) * zz;
                     if (!((qv > lo[k]) && (qv < hi[k]))) ok_s[pp] = 0;
                     q_s[pp][k] = qv; old_s[pp][k] = sv;
                     qv *= inv_len[k];
@@ -489,6 +582,14 @@ ens_half_multi_kernel(HalfArgs p) {
     }
 }
 
+template <int D, bool GENERIC, int NP>
+__global__ void __launch_bounds__(512)
+ens_half_multi_kernel(HalfArgs p) { ens_half_multi_body<D, GENERIC, NP, false>(p); }
+
+template <int D, bool GENERIC, int NP>
+__global__ void __launch_bounds__(512)
+ens_half_multi_de_kernel(HalfArgs p) { ens_half_multi_body<D, GENERIC, NP, true>(p); }
+
 template <int D>
 __global__ void __launch_bounds__(1024)
 ens_lnprob_kernel(const double* __restrict__ coords, int d, const double* __restrict__ Xt,
@@ -531,9 +632,8 @@ ens_lnprob_kernel(const double* __restrict__ coords, int d, const double* __rest
 //   (host)              lp_new = like + prior_fn(q)   [or like_fn(q) + prior_fn(q)]
 //   ens_accept_kernel   one thread per proposal: accept test with the record's (d-1) ln z and ln u', state update.
 // The ensemble, the draws and the accept decisions stay on the device; only the proposals of a half step travel.
-template <int D, bool GENERIC>
-__global__ void __launch_bounds__(1024)
-ens_propose_kernel(HalfArgs p, int gate_box, double* __restrict__ q_out, double* __restrict__ like_out) {
+template <int D, bool GENERIC, bool DE>
+__device__ __forceinline__ void ens_propose_body(const HalfArgs& p, int gate_box, double* __restrict__ q_out, double* __restrict__ like_out) {
     __shared__ double qs_s[ALABI_MAX_DIM];
     __shared__ double scratch[16];
     const int tid = threadIdx.x;
@@ -546,13 +646,15 @@ ens_propose_kernel(HalfArgs p, int gate_box, double* __restrict__ q_out, double*
     }
     const int cw = p.rec.cw[pos];
     const double zz = p.rec.zz[pos];
+    const int cw2 = DE ? p.cw2[pos] : -1;
+    const bool de = DE && cw2 >= 0;
     int ok = 1;
     if (tid < D) {
         double qv = 0.0;
         if (tid < p.d) {
             const double cv = p.coords[(size_t)cw * p.d + tid];
             const double sv = p.coords[(size_t)w * p.d + tid];
-            qv = cv - (cv - sv) * zz;
+            qv = DE ? propose_coord(de, sv, cv, p.coords[(size_t)(de ? cw2 : cw) * p.d + tid], zz) : cv - (cv - sv) * zz;
             ok = (qv > p.consts[ALABI_MAX_DIM + tid]) && (qv < p.consts[2 * ALABI_MAX_DIM + tid]);
             q_out[(size_t)blockIdx.x * p.d + tid] = qv;
             qv *= p.consts[tid];
@@ -564,6 +666,18 @@ ens_propose_kernel(HalfArgs p, int gate_box, double* __restrict__ q_out, double*
     double lp = -INFINITY;
     if (inb) lp = apply_ymap(fma(p.amp, gp_kernel_dot_block<D, GENERIC>(p.Xt, p.alpha, p.Npad, qs_s, scratch, p.kf), p.mean), p.ymap);
     if (tid == 0) like_out[blockIdx.x] = lp;
+}
+
+template <int D, bool GENERIC>
+__global__ void __launch_bounds__(1024)
+ens_propose_kernel(HalfArgs p, int gate_box, double* __restrict__ q_out, double* __restrict__ like_out) {
+    ens_propose_body<D, GENERIC, false>(p, gate_box, q_out, like_out);
+}
+
+template <int D, bool GENERIC>
+__global__ void __launch_bounds__(1024)
+ens_propose_de_kernel(HalfArgs p, int gate_box, double* __restrict__ q_out, double* __restrict__ like_out) {
+    ens_propose_body<D, GENERIC, true>(p, gate_box, q_out, like_out);
 }
 
 __global__ void __launch_bounds__(256)
@@ -1159,8 +1273,12 @@ int launch_ens_draw_at(alabi_ens* e, const DrawBuffers& into, int nsteps, double
         ALABI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ens_draw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
+    // the default move set is one stretch move with the call's `a`; the second-partner arrays belong to the first buffer set
+    MoveTable mt = e->moves;
+    if (mt.n == 0) { mt = MoveTable{}; mt.n = 1; mt.kind[0] = 0; mt.cum[0] = 1.0; mt.p0[0] = a; }
+    const MoveBuffers mv = (into.order == e->draws.order) ? e->mv : MoveBuffers{};
     hipLaunchKernelGGL(ens_draw_kernel, dim3(nsteps, e->E), dim3(256), lds, s, e->seed, from_state ? e->run_state : nullptr,
-                       from_state ? 0LL : step0, e->W, Wp, e->d, a, into);
+                       from_state ? 0LL : step0, e->W, Wp, e->d, mt, into, mv);
     ALABI_LAUNCH_CHECK();
     return ALABI_OK;
 }
@@ -1169,6 +1287,14 @@ int launch_ens_prep(alabi_ens* e, const int* order, int n0, const double* u_z, c
                     const double* u_acc, double a, hipStream_t s) {
     hipLaunchKernelGGL(ens_prep_kernel, dim3((e->W + 255) / 256), dim3(256), 0, s, order, n0, e->W, u_z, partner, u_acc,
                        a, e->d, e->draws);
+    ALABI_LAUNCH_CHECK();
+    return ALABI_OK;
+}
+
+int launch_ens_prep_de(alabi_ens* e, const int* order, int n0, const int* j1, const int* j2, const double* gamma,
+                       const double* u_acc, hipStream_t s) {
+    hipLaunchKernelGGL(ens_prep_de_kernel, dim3((e->W + 255) / 256), dim3(256), 0, s, order, n0, e->W, j1, j2, gamma, u_acc,
+                       e->draws, e->mv);
     ALABI_LAUNCH_CHECK();
     return ALABI_OK;
 }
@@ -1195,7 +1321,18 @@ int launch_ens_half_args(alabi_ens* e, const HalfArgs& args_in, int nblocks, hip
         if (env && env[0] == '2') np = 2;
         if (env && env[0] == '1') np = 1;
     }
-    if (np == 4) {
+    if (args.cw2) {                                   // records with a second partner: the two-partner instantiations
+        if (args.shist) return ALABI_BAD_ARGUMENT;    // the sharded history links one partner row
+        if (np == 4) {
+            ALABI_STREAM_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(e->gp->kf.type, hipLaunchKernelGGL((ens_half_multi_de_kernel<D, GENERIC, 4>),
+                dim3((nblocks + 3) / 4, e->E), dim3(threads), 0, s, args)));
+        } else if (np == 2) {
+            ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(e->gp->kf.type, hipLaunchKernelGGL((ens_half_multi_de_kernel<D, GENERIC, 2>),
+                dim3((nblocks + 1) / 2, e->E), dim3(threads), 0, s, args)));
+        } else {
+            ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(e->gp->kf.type, hipLaunchKernelGGL((ens_half_de_kernel<D, GENERIC>), dim3(nblocks, e->E), dim3(threads), 0, s, args)));
+        }
+    } else if (np == 4) {
         ALABI_STREAM_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(e->gp->kf.type, hipLaunchKernelGGL((ens_half_multi_kernel<D, GENERIC, 4>),
             dim3((nblocks + 3) / 4, e->E), dim3(threads), 0, s, args)));
     } else if (np == 2) {
@@ -1222,8 +1359,13 @@ int launch_ens_lnprob(alabi_ens* e, const double* coords, int nwalkers, double* 
 int launch_ens_propose(alabi_ens* e, const HalfArgs& args, int nblocks, int gate_box, double* q, double* like, hipStream_t s) {
     if (nblocks <= 0) return ALABI_OK;
     const int db = dim_bucket(e->d);
-    ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(e->gp->kf.type, hipLaunchKernelGGL((ens_propose_kernel<D, GENERIC>), dim3(nblocks),
-                                                                                    dim3(e->threads), 0, s, args, gate_box, q, like)));
+    if (args.cw2) {
+        ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(e->gp->kf.type, hipLaunchKernelGGL((ens_propose_de_kernel<D, GENERIC>), dim3(nblocks),
+                                                                                        dim3(e->threads), 0, s, args, gate_box, q, like)));
+    } else {
+        ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(e->gp->kf.type, hipLaunchKernelGGL((ens_propose_kernel<D, GENERIC>), dim3(nblocks),
+                                                                                        dim3(e->threads), 0, s, args, gate_box, q, like)));
+    }
     ALABI_LAUNCH_CHECK();
     return ALABI_OK;
 }

@@ -21,6 +21,7 @@ import torch
 from . import _lib
 from .gp import HipGP, _dev, _to_dev
 from .mcmc_utils import integrated_time
+from .moves import parse_moves
 
 __all__ = ["EnsembleSampler", "State"]
 
@@ -39,7 +40,7 @@ class State:
 class EnsembleSampler:
     def __init__(self, nwalkers, ndim, gp, y, bounds, seed=None, a=2.0, pool=None, live_dangerously=False,
                  n_ensembles=1, logp_affine=(1.0, 0.0), normal_prior=None, logp_map=None, prior_fn=None, like_fn=None,
-                 gate_box=True, shard=False, group=None, **unused):
+                 gate_box=True, shard=False, group=None, moves=None, **unused):
         """``n_ensembles`` > 1 runs that many INDEPENDENT ensembles of ``nwalkers`` walkers in the same kernel
         launches (rows [e*nwalkers, (e+1)*nwalkers) of every array belong to ensemble e).
         ``logp_affine=(scale, shift)``: log-probability = scale * GP mean + shift inside the box (an affine y scaler).
@@ -53,6 +54,10 @@ class EnsembleSampler:
         (alabi_ens_propose / alabi_ens_accept): the ensemble, the draws and the accept test stay on the device.  With
         ``like_fn=None`` the surrogate part is evaluated by the propose kernel; ``gate_box`` says whether that value is
         -inf outside ``bounds`` (True when the prior is the box itself, False when ``prior_fn`` is the whole prior).
+        ``moves``: emcee's proposal moves (alabi_amd.moves) -- None (the stretch move with ``a``), a ``StretchMove`` or
+        ``DEMove``, a list of them, or a list of (move, weight) pairs from which one move is chosen per step; emcee's own move
+        objects of these two classes are recognised.  Works with ``n_ensembles`` > 1 and with host callables; a set holding a
+        ``DEMove`` needs ``nwalkers >= 4``, runs with one launch per half step, and cannot be sharded.
         ``shard=True`` under an initialised ``torch.distributed`` group of more than one rank (``group``: default WORLD): ONE
         ensemble whose active half is partitioned over the ranks, an all-gather of the new rows per half step
         (alabi_amd.dist.ShardedRun -> alabi_ens_run_sharded); every rank must construct the sampler with the same arguments and
@@ -91,6 +96,12 @@ class EnsembleSampler:
         self.shard, self.group, self._sharded, self._sharded_ens = bool(shard), group, None, None
         if self.shard and (self.generic or self.n_ensembles != 1):
             raise ValueError("shard=True needs the fused log-probability (no host callables) and n_ensembles == 1")
+        self._move_set = parse_moves(moves, self.ndim)
+        if self._move_set is not None and self._move_set.has_de:
+            if self.nwalkers < 4:
+                raise ValueError("DEMove draws two distinct walkers from the complementary half: nwalkers >= 4")
+            if self.shard:
+                raise ValueError("shard=True cannot run a DEMove: the sharded history links one partner row per proposal")
         if seed is None:
             seed = int(np.random.SeedSequence().generate_state(2, dtype=np.uint32).view(np.uint64)[0])
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -127,8 +138,21 @@ class EnsembleSampler:
                        "alabi_ens_set_normal_prior")
         if self.logp_map is not None:
             _lib.check(_lib.lib().alabi_ens_set_logp_map(e, {"nlog": 1, "log": 2}[self.logp_map]), "alabi_ens_set_logp_map")
+        if self._move_set is not None:
+            m = self._move_set
+            _lib.check(_lib.lib().alabi_ens_set_moves(e, len(m), (C.c_int * len(m))(*[int(k) for k in m.kind]),
+                                                      _lib.host_doubles(m.cum), _lib.host_doubles(m.p0), _lib.host_doubles(m.p1)),
+                       "alabi_ens_set_moves")
         self._ens = e
         self._ens_gp_handle = C.c_void_p(h.value)
+
+    @property
+    def moves(self):
+        """The configured moves as (move, normalised weight) pairs; the default is one StretchMove(a)."""
+        if getattr(self, "_move_set", None) is None:
+            from .moves import StretchMove
+            return [(StretchMove(self.a), 1.0)]
+        return list(zip(self._move_set.moves, (float(w) for w in self._move_set.weights)))
 
     def _release(self):
         _lib.destroy(getattr(self, "_ens", None), "alabi_ens_destroy", sync=True)
@@ -158,6 +182,7 @@ class EnsembleSampler:
         self.__dict__.update(st)
         if "_rng_step" not in st:                       # saved before the draw counter was separated from `iteration`
             self._rng_step = st.get("iteration", 0)
+        self.__dict__.setdefault("_move_set", None)     # saved before the sampler had moves
         if torch.cuda.is_available():
             self._stream = torch.cuda.Stream()
             for k in ("_coords", "_logp", "_naccept"):

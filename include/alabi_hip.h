@@ -219,6 +219,17 @@ int alabi_ens_set_logp_affine(alabi_ens* ens, double scale, double shift);
  * 2 log_scaler's inverse 10^x.  Applied inside every ensemble kernel, once per proposal. */
 int alabi_ens_set_logp_map(alabi_ens* ens, int kind);
 
+/* Proposal moves, emcee's EnsembleSampler(moves=...) (documented by the reference as sampler_kwargs['moves'], "Custom proposal
+ * moves", alabi/core.py:2144, and handed to emcee.EnsembleSampler at alabi/core.py:2319).  A table of n <= 8 moves, all HOST
+ * arrays: kind 0 = StretchMove with p0 = a (> 1); kind 1 = DEMove (emcee 3 moves/de.py) with p0 = gamma0 and p1 = sigma,
+ * proposal q = s + gamma0 (1 + sigma n) (C[j2] - C[j1]), n standard normal, j1 != j2 drawn from the complementary set, log
+ * factor 0.  cum = np.cumsum(w / w.sum()) in fp64: ONE move is chosen per step and ensemble, index = #{k: cum[k] <= u}
+ * (clipped to n - 1) with u from Philox stream 3 at the ensemble's walker 0.  n = 0 restores the default (one stretch move with
+ * the `a` of each call); with n > 0 the `a` arguments of run / draw / export_draws are not used.  Streams 0-2 (labels, u_z and
+ * partner, u') do not depend on the moves.  A set holding a DE move needs W >= 4, runs alabi_ens_run with one launch per half
+ * step, and is refused by the sharded run.  Takes effect from the next call on. */
+int alabi_ens_set_moves(alabi_ens* ens, int n, const int* kind, const double* cum, const double* p0, const double* p1);
+
 /* Enable / disable the persistent dataflow kernel for alabi_ens_run on this handle (default: enabled when the
  * ensemble fits one workgroup per CU).  Returns ALABI_BAD_ARGUMENT when enabling is impossible. */
 int alabi_ens_set_stream(alabi_ens* ens, int enabled);
@@ -312,6 +323,18 @@ int alabi_ens_step_with_randoms(alabi_ens* ens, double* coords, double* logp,
 int alabi_ens_export_draws(alabi_ens* ens, long long step, double a, int* order, int* n0,
                            double* u_z, int* partner, double* u_acc, int* cw, double* zz,
                            void* stream);
+
+/* Test entries of the moves (alabi_ens_set_moves; reference call site alabi/core.py:2144, :2319).
+ * alabi_ens_export_move_draws: for the step last drawn by alabi_ens_export_draws on a handle with a move set -- move [E] the
+ * index of each ensemble's move, and in LIST order j2 [E*W] the second partner's index into the complementary list (-1 at a
+ * stretch step) and gamma [E*W] the DE step size (at a stretch step: the stretch factor).  j1 is export_draws' `partner`.
+ * alabi_ens_step_with_randoms_de (n_ensembles == 1): one full DE step from caller-supplied draws keyed by WALKER id, the
+ * sibling of alabi_ens_step_with_randoms: j1[W] / j2[W] int32 index the complementary list (j1 != j2), gamma[W] is the
+ * step size, u_acc[W] the accept uniform.  Out-of-range indices make that proposal a no-op.  All arrays on the device. */
+int alabi_ens_export_move_draws(alabi_ens* ens, int* move, int* j2, double* gamma, void* stream);
+int alabi_ens_step_with_randoms_de(alabi_ens* ens, double* coords, double* logp, const int* order, int n0,
+                                   const int* j1, const int* j2, const double* gamma, const double* u_acc,
+                                   long long* n_accept, void* stream);
 
 /* Nested sampling (dynesty's NestedSampler / DynamicNestedSampler with sample="rwalk" as driven by
  * SurrogateModel.run_dynesty, alabi/core.py:2417-2787, likelihood = surrogate_log_likelihood core.py:1446-1508, prior =
