@@ -10,7 +10,9 @@ Keeps the public surface of ``alabi.core.SurrogateModel`` that BASELINE.json's n
 george.GP -> ``HipGP``, emcee.EnsembleSampler -> ``alabi_amd.sampler.EnsembleSampler`` and
 dynesty's nested samplers -> ``alabi_amd.nested.NestedSampler``.
 
-Out of scope here: pymultinest / ultranest, plotting, MPI / process pools, the
+``run_pymultinest`` (:2790) runs the same sampler with MultiNest's move, uniform draws inside bounding ellipsoids.
+
+Out of scope here: ultranest, plotting, MPI / process pools, the
 parallel-chain trainer.  Deliberate differences are listed in DESIGN.md ("Differences").
 """
 from __future__ import annotations
@@ -114,6 +116,7 @@ class SurrogateModel(object):
         self.mpi_is_active = False
         self.emcee_run = False
         self.dynesty_run = False
+        self.pymultinest_run = False
         self.ultranest_run = False
 
     # ------------------------------------------------------------------------- persistence
@@ -911,9 +914,9 @@ class SurrogateModel(object):
             self.eval_gp_at_iteration(-1)
         return self.gp, self._y
 
-    def _write_samples(self, sampler, samples, samples_file):
-        """After a sampler run (the caller lets rank 0 only through): the cached model, quietly, and the .npz of samples, whose
-        name is returned."""
+    def _write_samples(self, sampler, samples, samples_file, **more):
+        """After a sampler run (the caller lets rank 0 only through): the cached model, quietly, and the .npz of samples (and of
+        ``more`` arrays), whose name is returned."""
         if self.cache:
             try:
                 self.save()
@@ -927,7 +930,7 @@ class SurrogateModel(object):
             res = getattr(self, "training_results", {"iteration": []})
             it = res["iteration"][-1] if len(res["iteration"]) else 0
             fname = f"{self.savedir}/{sampler}_samples_final_{self.like_fn_name}_iter_{it}.npz"
-        np.savez(fname, samples=samples)
+        np.savez(fname, samples=samples, **more)
         return fname
 
     def run_emcee(self, like_fn=None, prior_fn=None, nwalkers=None, nsteps=int(5e4), sampler_kwargs={}, run_kwargs={},
@@ -1054,30 +1057,10 @@ class SurrogateModel(object):
     run_mcmc = run_emcee  # BASELINE.json's name for the same entry point
 
     # ------------------------------------------------------------------------ nested sampling
-    def run_dynesty(self, like_fn=None, prior_transform=None, mode="dynamic", sampler_kwargs={}, run_kwargs={},
-                    multi_proc=False, save_iter=None, prior_transform_comment=None, samples_file=None, min_ess=int(1e4)):
-        """Nested sampling of the posterior and its evidence log Z on the GPU (core.py:2417-2787); the sampler is
-        alabi_amd.nested.NestedSampler (its docstring states the algorithm) in place of dynesty's.
-
-        * Fused path: the surrogate likelihood (like_fn None / "surrogate" / "gp"), prior_transform None,
-          ``partial(ut.prior_transform_uniform, bounds=...)`` or ``partial(ut.prior_transform_normal, bounds=..., data=...)``
-          (Gaussian priors: the inverse normal CDF inside the kernels, not truncated to the bounds, as in the reference),
-          affine theta scaler, affine / nlog / log y scaler: every walk step evaluates the GP mean inside ``ns_walk_kernel``.
-        * Otherwise (like_fn "true" or a callable, any other prior_transform, scalers the kernel cannot fold) the device proposes
-          and accepts, and the host evaluates ``like_fn(prior_transform(u))`` row by row with 1-D arrays of shape (d,), as
-          dynesty calls them (the surrogate under exotic scalers takes the whole batch in one call, and so does the
-          ``prior_transform_normal`` partial).
-        sampler_kwargs: ``nlive`` (50 ndim), ``sample`` ("auto" / "rwalk": ``walks`` (25) Metropolis steps per walk; "rslice":
-        ``slices`` (3 (3 + ndim)) random-direction slice updates per walk, 5-15 times the likelihood evaluations of the random
-        walk), ``batch`` (ceil(nlive / 4)), ``seed``.  Above ndim = 20 pass ``sample="rslice"``: 25 random-walk steps no longer
-        forget the start point there, and log Z comes out too high by several logzerr ("auto" stays the random walk at every
-        dimension).  ``bound``, ``pool``, ``queue_size`` and ``multi_proc`` have no effect.  run_kwargs: ``dlogz`` (0.5),
-        ``maxiter`` (5e4), ``maxcall``, and for mode="dynamic" ``dlogz_init`` (0.5), ``nlive_init``, ``nlive_batch``,
-        ``maxbatch`` (10), ``n_effective`` (1e4), ``wt_kwargs`` / ``stop_kwargs`` (pfrac = 1.0 only).  Under
-        ``torch.distributed`` every rank runs its own sampler (seed + rank) and rank 0 writes the files."""
-        from . import dist as adist
-        from .nested import GPUWalkBackend, NestedSampler, PickleCheckpoint
-        rank, world = adist.world_info()
+    def _nested_setup(self, like_fn, prior_transform, prior_transform_comment):
+        """What run_dynesty and run_pymultinest share: resolves ``like_fn`` and ``prior_transform`` as the reference does
+        (core.py:2533-2598, :2977-3025) into ``like_fn_name`` / ``like_fn`` / ``prior_transform`` / ``prior_transform_comment``, and
+        returns (plan, gp, y): fused device likelihood, or the host evaluates like_fn(prior_transform(u))."""
         # ---- likelihood (core.py:2533-2573)
         if like_fn is None or (isinstance(like_fn, str) and like_fn.lower() in ("surrogate", "gp", "surrogate_log_likelihood")) \
                 or (callable(like_fn) and like_fn == self.surrogate_log_likelihood):
@@ -1105,6 +1088,37 @@ class SurrogateModel(object):
             if prior_transform_comment is None:
                 self.prior_transform_comment = ("User defined prior transform."
                                                 f"Prior function: {getattr(prior_transform, '__name__', 'unrecorded')}")
+        plan = post.plan_nested(self.like_fn, self.surrogate_log_likelihood, self.prior_transform, self.bounds,
+                                getattr(self, "theta_scaler", None), getattr(self, "y_scaler", None), getattr(self, "_y", None))
+        gp_obj, y_obj = self._handle_owner()
+        return plan, gp_obj, y_obj
+
+    def run_dynesty(self, like_fn=None, prior_transform=None, mode="dynamic", sampler_kwargs={}, run_kwargs={},
+                    multi_proc=False, save_iter=None, prior_transform_comment=None, samples_file=None, min_ess=int(1e4)):
+        """Nested sampling of the posterior and its evidence log Z on the GPU (core.py:2417-2787); the sampler is
+        alabi_amd.nested.NestedSampler (its docstring states the algorithm) in place of dynesty's.
+
+        * Fused path: the surrogate likelihood (like_fn None / "surrogate" / "gp"), prior_transform None,
+          ``partial(ut.prior_transform_uniform, bounds=...)`` or ``partial(ut.prior_transform_normal, bounds=..., data=...)``
+          (Gaussian priors: the inverse normal CDF inside the kernels, not truncated to the bounds, as in the reference),
+          affine theta scaler, affine / nlog / log y scaler: every walk step evaluates the GP mean inside ``ns_walk_kernel``.
+        * Otherwise (like_fn "true" or a callable, any other prior_transform, scalers the kernel cannot fold) the device proposes
+          and accepts, and the host evaluates ``like_fn(prior_transform(u))`` row by row with 1-D arrays of shape (d,), as
+          dynesty calls them (the surrogate under exotic scalers takes the whole batch in one call, and so does the
+          ``prior_transform_normal`` partial).
+        sampler_kwargs: ``nlive`` (50 ndim), ``sample`` ("auto" / "rwalk": ``walks`` (25) Metropolis steps per walk; "rslice":
+        ``slices`` (3 (3 + ndim)) random-direction slice updates per walk, 5-15 times the likelihood evaluations of the random
+        walk), ``batch`` (ceil(nlive / 4)), ``seed``.  Above ndim = 20 pass ``sample="rslice"``: 25 random-walk steps no longer
+        forget the start point there, and log Z comes out too high by several logzerr ("auto" stays the random walk at every
+        dimension).  ``sample="unif"`` is not reached from here (it raises ``NotImplementedError``): uniform draws inside bounding
+        ellipsoids are ``run_pymultinest``'s move, and ``alabi_amd.nested.NestedSampler(sample="unif")`` directly.
+        ``bound``, ``pool``, ``queue_size`` and ``multi_proc`` have no effect.  run_kwargs: ``dlogz`` (0.5),
+        ``maxiter`` (5e4), ``maxcall``, and for mode="dynamic" ``dlogz_init`` (0.5), ``nlive_init``, ``nlive_batch``,
+        ``maxbatch`` (10), ``n_effective`` (1e4), ``wt_kwargs`` / ``stop_kwargs`` (pfrac = 1.0 only).  Under
+        ``torch.distributed`` every rank runs its own sampler (seed + rank) and rank 0 writes the files."""
+        from . import dist as adist
+        from .nested import GPUWalkBackend, NestedSampler, PickleCheckpoint
+        rank, world = adist.world_info()
         dynesty_t0 = time.time()
         # ---- sampler / run settings (core.py:2603-2649)
         skw = dict(sampler_kwargs)
@@ -1134,10 +1148,8 @@ class SurrogateModel(object):
                    "wt_kwargs", "stop_kwargs"}
         if set(rkw) - allowed:
             raise TypeError(f"run_dynesty: unsupported run_kwargs {sorted(set(rkw) - allowed)}")
-        # ---- plan: fused walks, or the host evaluates like_fn(prior_transform(u))
-        plan = post.plan_nested(self.like_fn, self.surrogate_log_likelihood, self.prior_transform, self.bounds,
-                                getattr(self, "theta_scaler", None), getattr(self, "y_scaler", None), getattr(self, "_y", None))
-        gp_obj, y_obj = self._handle_owner()
+        # ---- likelihood, prior transform and the plan: fused walks, or the host evaluates like_fn(prior_transform(u))
+        plan, gp_obj, y_obj = self._nested_setup(like_fn, prior_transform, prior_transform_comment)
         if self.verbose:
             print(f"Running nested sampling ({mode}, {'fused GPU walks' if plan.fused else 'host likelihood'}) with {nlive} live "
                   "points...")
@@ -1176,3 +1188,90 @@ class SurrogateModel(object):
         fname = self._write_samples("dynesty", self.dynesty_samples, samples_file)
         if self.verbose:
             print(f"Saved dynesty samples to {fname}")
+
+    _PYMULTINEST_DEFAULTS = {"n_live_points": 1000, "evidence_tolerance": 0.5, "sampling_efficiency": 0.8,
+                             "n_iter_before_update": 100, "null_log_evidence": -1e90, "max_modes": 100, "mode_tolerance": -1e90,
+                             "seed": -1, "verbose": True, "importance_nested_sampling": True, "multimodal": True,
+                             "const_efficiency_mode": False, "max_iter": 0, "batch": None}
+
+    def run_pymultinest(self, like_fn=None, prior_transform=None, sampler_kwargs={}, multi_proc=True,
+                        prior_transform_comment=None, samples_file=None, prefix=None, resume=False,
+                        n_clustering_params=None, outputfiles_basename=None, min_ess=int(1e4)):
+        """MultiNest's algorithm on the GPU (core.py:2790-3238): static nested sampling whose replacement points are drawn
+        uniformly inside ellipsoids around the live points (``alabi_amd.nested.NestedSampler(sample="unif")``; its module
+        docstring states the algorithm).  Independent points without a walk length or step scale, 2-4 likelihood evaluations per
+        dead point where the random walk of ``run_dynesty`` spends 25, and one ellipsoid per separated mode.
+
+        ``like_fn`` / ``prior_transform`` and the fused / host-callback paths are those of ``run_dynesty``.  sampler_kwargs (the
+        reference's defaults): ``n_live_points`` (1000), ``evidence_tolerance`` (0.5; the dlogz stop), ``sampling_efficiency``
+        (0.8; every ellipsoid's volume is enlarged by 1 / efficiency), ``multimodal`` (True: up to ``min(max_modes, 32)``
+        ellipsoids by recursive 2-means; False: one), ``max_modes`` (100), ``seed`` (-1: the model's seed stream), ``max_iter``
+        (0: no limit), and ``batch`` (dead points per iteration, an extension; ceil(nlive / 4)).  ``n_iter_before_update``,
+        ``null_log_evidence``, ``mode_tolerance``, ``verbose`` and ``importance_nested_sampling`` are accepted and have no effect:
+        log Z is the plain nested-sampling estimate.  ``const_efficiency_mode=True`` and ``resume=True`` raise
+        ``NotImplementedError``; any other key raises ``TypeError``.  ``multi_proc``, ``prefix``, ``n_clustering_params`` and
+        ``outputfiles_basename`` have no effect (no MultiNest text files are written; ``pymultinest_analyzer`` is None).
+        Use at least 50 live points per dimension: ellipsoids fitted to fewer can cut the likelihood contour and bias log Z high
+        (a ``UserWarning`` says so).  Runs repeat until ``min_ess`` samples exist (at most 10) and are combined as the reference
+        does: log Z averaged with sample-count weights, its error the root of the weighted mean square.  Under
+        ``torch.distributed`` every rank runs its own sampler (seed + rank) and rank 0 writes the file."""
+        from . import dist as adist
+        from .nested import GPUWalkBackend, NestedSampler
+        rank, world = adist.world_info()
+        skw = dict(self._PYMULTINEST_DEFAULTS)
+        unknown = set(sampler_kwargs) - set(skw)
+        if unknown:
+            raise TypeError(f"run_pymultinest: unsupported sampler_kwargs {sorted(unknown)}")
+        skw.update(sampler_kwargs)
+        if skw["const_efficiency_mode"]:
+            raise NotImplementedError("run_pymultinest: const_efficiency_mode=True is not built")
+        if resume:
+            raise NotImplementedError("run_pymultinest: resume=True is not built (no MultiNest output files are written)")
+        nlive = int(skw["n_live_points"])
+        eff = float(skw["sampling_efficiency"])
+        if not 0.0 < eff <= 1.0:
+            raise ValueError("sampling_efficiency must lie in (0, 1]")
+        bound = "multi" if skw["multimodal"] else "single"
+        max_ell = max(1, min(int(skw["max_modes"]), 32))
+        seed = None if int(skw["seed"]) < 0 else int(skw["seed"])
+        maxiter = None if int(skw["max_iter"]) <= 0 else int(skw["max_iter"])
+        t0 = time.time()
+        plan, gp_obj, y_obj = self._nested_setup(like_fn, prior_transform, prior_transform_comment)
+        if self.verbose:
+            print(f"Running ellipsoidal nested sampling ({'fused GPU draws' if plan.fused else 'host likelihood'}) with {nlive} "
+                  "live points...")
+        normal = {} if plan.normal_prior is None else {"normal_prior": plan.normal_prior}
+        logz, logz_err, counts = [], [], []
+
+        def run(run_number):
+            s = (self._seed() if seed is None else seed + 1000003 * (run_number - 1)) + rank
+            backend = GPUWalkBackend(gp_obj, y_obj, plan.box, seed=s, to_theta=plan.to_theta, logp_affine=plan.logp_affine,
+                                     logp_map=plan.logp_map, host_loglike=plan.host_like, **normal)
+            self.pymultinest_sampler = NestedSampler(backend, nlive, dynamic=False, batch=skw["batch"], seed=s, sample="unif",
+                                                     bound=bound, enlarge=1.0 / eff, max_ellipsoids=max_ell)
+            res = self.pymultinest_sampler.run_nested(dlogz=float(skw["evidence_tolerance"]), maxiter=maxiter)
+            backend.close()
+            self.pymultinest_results, self.pymultinest_path = res, backend.path
+            eq = res.samples_equal(np.random.default_rng(s))
+            logz.append(float(res.logz[-1])); logz_err.append(float(res.logzerr[-1])); counts.append(eq.shape[0])
+            return eq
+
+        note = (lambda total: f", logZ = {logz[-1]:.3f} +/- {logz_err[-1]:.3f}") if self.verbose else None
+        self.pymultinest_samples = post.run_until_min_ess(run, min_ess, note)
+        self.pymultinest_weights = np.ones(self.pymultinest_samples.shape[0])
+        w = np.asarray(counts, dtype=np.float64) / float(np.sum(counts))          # core.py:3175-3190
+        self.pymultinest_logz = float(np.average(logz, weights=w))
+        self.pymultinest_logz_err = float(np.sqrt(np.average(np.square(logz_err), weights=w)))
+        self.pymultinest_analyzer = None
+        if self.like_fn_name == "true":
+            self.pymultinest_samples_true = self.pymultinest_samples
+        else:
+            self.pymultinest_samples_surrogate = self.pymultinest_samples
+        self.pymultinest_run = True
+        self.pymultinest_runtime = time.time() - t0
+        if rank != 0:
+            return                                   # files are rank 0's
+        fname = self._write_samples("pymultinest", self.pymultinest_samples, samples_file, weights=self.pymultinest_weights,
+                                    logz=self.pymultinest_logz, logz_err=self.pymultinest_logz_err)
+        if self.verbose:
+            print(f"Saved PyMultiNest samples to {fname}")

@@ -1,4 +1,4 @@
-"""Nested sampling on the GPU: the static and dynamic samplers behind ``SurrogateModel.run_dynesty``.
+"""Nested sampling on the GPU: the static and dynamic samplers behind ``SurrogateModel.run_dynesty`` and ``run_pymultinest``.
 
 The reference drives dynesty's ``NestedSampler`` / ``DynamicNestedSampler`` (alabi/core.py:2417-2787) for the Bayesian
 evidence log Z.  Here the nested-sampling bookkeeping runs on the host in NumPy and the likelihood work -- many independent
@@ -47,8 +47,27 @@ Dynamic mode (the reference's default; ``wt_kwargs`` / ``stop_kwargs`` with pfra
   3. Stop when the Kish ESS (sum w)^2 / sum w^2 >= ``n_effective`` (default 10000) or after ``maxbatch`` batches.
   4. dynesty's bootstrap stopping rule is not built.
 
-Not built (listed in DESIGN.md "Differences"): bounding ellipsoids (``bound`` has no effect), ``unif`` / axis-aligned ``slice``
-/ ``hslice`` sampling, the bootstrap stop, other weight / stop fractions than pfrac = 1.
+Uniform draws inside bounding ellipsoids (``sample="unif"``: MultiNest's algorithm, the reference's run_pymultinest,
+alabi/core.py:2790-3238; dynesty's ``sample="unif"`` with ``bound="single"`` / ``"multi"``)
+  * Bounds (host, once per iteration, from the point set the walks take their covariance from).  One ellipsoid {c + A z : |z| <= 1}:
+    c the mean, A = L sqrt(f) enlarge^(1/d) with L the Cholesky factor of the sample covariance and f = max_i |L^-1 (p_i - c)|^2,
+    i.e. the tightest scaled-covariance ellipsoid that holds every point, its volume enlarged by ``enlarge`` (default 1.25).
+    ``bound="multi"``: a node with n >= 4d points is split by 2-means (Lloyd, at most 20 iterations, started at the two points
+    extreme along the major principal axis: no random numbers); the split is kept iff both clusters hold >= 2d points and their
+    ellipsoids' volumes add up to less than half the node's; then both halves are split further, breadth first, up to
+    ``max_ellipsoids`` (32 at most).
+  * Move.  Candidates c = 0, 1, 2, ... of the call, each from its own device draws: an ellipsoid e chosen by volume, a point uniform
+    in it (u = c_e + rho A_e z / |z|, z ~ N(0, I), rho = v^(1/d)); rejected when outside the cube; kept with probability 1 / q when
+    it lies in q ellipsoids (which makes the draw uniform over their union); logL evaluated for the rest.  The K replacements are
+    the first K candidates with logL > L*, in candidate order.  ``ncall`` grows by the evaluations up to the last one taken.  No
+    start points, no walk length, no scale rule; ``n_stuck`` stays 0.
+  * The K new points are independent draws from the constrained prior as far as the ellipsoids cover {logL > L*} within the cube.
+    An ellipsoid fitted to too few points cuts that region and log Z comes out high: keep nlive >= 50 d (the constructor warns below
+    that; at nlive = 200 a separable 24-D Gaussian is high by 12 logzerr).  A search that does not find K points within
+    max(1e5, 1e4 K) candidates ends the run with status "inefficient" and a warning.
+
+Not built (listed in DESIGN.md "Differences"): axis-aligned ``slice`` / ``hslice`` sampling, the bootstrap stop, other weight /
+stop fractions than pfrac = 1; ``run_dynesty`` does not reach ``unif`` (``bound`` has no effect there).
 """
 from __future__ import annotations
 
@@ -64,11 +83,13 @@ from . import _lib
 from .gp import _dev
 
 __all__ = ["NestedSampler", "NestedResults", "GPUWalkBackend", "PickleCheckpoint", "resample_equal", "compute_integrals",
-           "merge_runs", "update_scale", "update_scale_slice", "default_slices"]
+           "merge_runs", "update_scale", "update_scale_slice", "default_slices", "Ellipsoids", "bounding_ellipsoids"]
 
 MAXFRAC = 0.8
 SCALE_MIN, SCALE_MAX = 1e-4, 10.0
 SLICES_MULT = 3       # calibrated on a 24-D Gaussian (NOTES.md "Nested sampling")
+MAX_ELLIPSOIDS = 32   # ALABI_NS_MAX_ELLIPSOIDS
+LIVE_PER_DIM = 50     # below this many live points per dimension an ellipsoid fitted to them can cut the likelihood contour
 
 
 def update_scale(scale, acc, ndim):
@@ -156,7 +177,7 @@ def merge_runs(runs):
 class NestedResults:
     """dynesty's Results fields: samples (theta), samples_u, logl, logwt, logvol, logz, logzerr, information, samples_n,
     niter (dead points of the loops, add_live excluded), ncall (likelihood evaluations), eff (100 niter / ncall), nlive,
-    status ("converged", "maxiter", "maxcall", "plateau", "n_effective", "maxbatch"), n_stuck (walks without an accept;
+    status ("converged", "maxiter", "maxcall", "plateau", "inefficient", "n_effective", "maxbatch"), n_stuck (walks without an accept;
     rslice: walks with a slice that hit the contraction cap)."""
 
     _FIELDS = ("samples", "samples_u", "logl", "logwt", "logvol", "logz", "logzerr", "information", "samples_n", "niter",
@@ -194,6 +215,85 @@ def _chol(u):
     return np.diag(np.sqrt(np.maximum(np.diag(cov), 1e-30)))
 
 
+class Ellipsoids:
+    """E ellipsoids {c + A z : |z| <= 1}: ``centres`` [E,d], ``axes`` [E,d,d] (A, lower triangular), ``inv_axes`` [E,d,d] (A^-1,
+    lower triangular), ``logvol`` [E] (log volume) and ``cum`` [E], the cumulative volume fractions with ``cum[-1] == 1.0``."""
+
+    def __init__(self, centres, axes, inv_axes, logvol):
+        self.centres = np.ascontiguousarray(centres, dtype=np.float64)
+        self.axes = np.ascontiguousarray(axes, dtype=np.float64)
+        self.inv_axes = np.ascontiguousarray(inv_axes, dtype=np.float64)
+        self.logvol = np.ascontiguousarray(logvol, dtype=np.float64)
+        w = np.exp(self.logvol - self.logvol.max())
+        self.cum = np.cumsum(w) / np.sum(w)
+        self.cum[-1] = 1.0
+
+    def __len__(self):
+        return int(self.centres.shape[0])
+
+
+def _log_unit_ball(d):
+    return 0.5 * d * math.log(math.pi) - math.lgamma(0.5 * d + 1.0)
+
+
+def _one_ellipsoid(points, enlarge):
+    """(c, A, A^-1, log volume): the covariance ellipsoid of ``points`` scaled to hold them all, its volume times ``enlarge``."""
+    d = points.shape[1]
+    c = points.mean(axis=0)
+    L = _chol(points)
+    y = np.linalg.solve(L, (points - c).T)
+    f = max(float(np.max(np.sum(y * y, axis=0))), 1e-300)
+    A = np.tril(L * (math.sqrt(f) * enlarge ** (1.0 / d)))
+    Ainv = np.tril(np.linalg.inv(A))
+    return c, A, Ainv, float(np.sum(np.log(np.diag(A)))) + _log_unit_ball(d)
+
+
+def _two_means(points):
+    """Boolean membership of cluster 1 after at most 20 Lloyd iterations from the two points extreme along the major principal
+    axis (no random numbers), or None when a cluster empties."""
+    c = points.mean(axis=0)
+    cov = np.atleast_2d(np.cov(points.T))
+    t = (points - c) @ np.linalg.eigh(cov)[1][:, -1]
+    m0, m1 = points[int(np.argmin(t))], points[int(np.argmax(t))]
+    lab = None
+    for _ in range(20):
+        new = np.sum((points - m1) ** 2, axis=1) < np.sum((points - m0) ** 2, axis=1)
+        if new.all() or not new.any():
+            return None
+        if lab is not None and np.array_equal(new, lab):
+            break
+        lab = new
+        m0, m1 = points[~lab].mean(axis=0), points[lab].mean(axis=0)
+    return lab
+
+
+def bounding_ellipsoids(points, bound="multi", enlarge=1.25, max_ellipsoids=MAX_ELLIPSOIDS):
+    """Ellipsoids around ``points`` [n,d] (MultiNest's bounds).  One ellipsoid: centre = the mean, shape = the sample covariance
+    scaled so that the tightest such ellipsoid holds every point, volume then enlarged by ``enlarge``.  ``bound="multi"``: a node
+    with n >= 4d points (and budget left) is split by 2-means; the split is kept iff both clusters hold >= 2d points and their
+    ellipsoids' volumes add up to less than half the node's, and then both halves are split further, breadth first, until
+    ``max_ellipsoids`` exist.  ``bound="single"``: one ellipsoid."""
+    if bound not in ("single", "multi"):
+        raise ValueError("bound must be 'single' or 'multi'")
+    p = np.ascontiguousarray(points, dtype=np.float64)
+    if p.ndim != 2 or p.shape[0] < 2:
+        raise ValueError("bounding_ellipsoids needs points [n,d] with n >= 2")
+    d = p.shape[1]
+    budget = 1 if bound == "single" else max(1, min(int(max_ellipsoids), MAX_ELLIPSOIDS))
+    queue, done = [(p, _one_ellipsoid(p, enlarge))], []
+    while queue:
+        pts, ell = queue.pop(0)
+        if len(queue) + len(done) + 1 < budget and pts.shape[0] >= 4 * d:
+            lab = _two_means(pts)
+            if lab is not None and min(int(lab.sum()), int((~lab).sum())) >= 2 * d:
+                a, b = _one_ellipsoid(pts[~lab], enlarge), _one_ellipsoid(pts[lab], enlarge)
+                if np.logaddexp(a[3], b[3]) < ell[3] + math.log(0.5):
+                    queue += [(pts[~lab], a), (pts[lab], b)]
+                    continue
+        done.append(ell)
+    return Ellipsoids(*(np.stack([e[k] for e in done]) for k in range(3)), np.array([e[3] for e in done]))
+
+
 class NestedSampler:
     """Static (``dynamic=False``) or dynamic nested sampler over a walk backend.
 
@@ -202,9 +302,15 @@ class NestedSampler:
     chol, scale, slices) -> (u, logl, n_eval, n_expand, n_contract, n_capped)``.  ``sample``: "rwalk" (``walks`` Metropolis
     steps) or "rslice" (``slices`` slice updates, default ``default_slices(ndim)``).  ``seed`` seeds the host generator
     (start-point choice and
-    resampling); the device draws are keyed by the backend's own seed and the call counter kept here."""
+    resampling); the device draws are keyed by the backend's own seed and the call counter kept here.
+    ``sample="unif"``: the replacements are uniform draws inside ellipsoids around the surviving live points
+    (``bounding_ellipsoids`` with ``bound`` "multi" / "single" and ``enlarge``; at most ``max_ellipsoids``) from
+    ``unif(call, ells, logl_star, K) -> (u [K,d], logl [K], n_eval, n_cand)``; no walk length, no scale.  ``n_ellipsoids`` lists
+    the number of ellipsoids of every such call.  A backend that returns fewer than K points ends the run with status
+    "inefficient"."""
 
-    def __init__(self, backend, nlive, dynamic=False, walks=25, batch=None, seed=0, sample="rwalk", slices=None):
+    def __init__(self, backend, nlive, dynamic=False, walks=25, batch=None, seed=0, sample="rwalk", slices=None, bound="multi",
+                 enlarge=1.25, max_ellipsoids=MAX_ELLIPSOIDS):
         self.backend = backend
         self.ndim = int(backend.ndim)
         self.nlive = int(nlive)
@@ -212,8 +318,8 @@ class NestedSampler:
             raise ValueError("nlive must be >= 2")
         self.dynamic = bool(dynamic)
         self.walks = int(walks)
-        if sample not in ("rwalk", "rslice"):
-            raise ValueError("sample must be 'rwalk' or 'rslice'")
+        if sample not in ("rwalk", "rslice", "unif"):
+            raise ValueError("sample must be 'rwalk', 'rslice' or 'unif'")
         self.sample = sample
         self.slices = default_slices(self.ndim) if slices is None else int(slices)
         if self.slices < 0:
@@ -221,6 +327,19 @@ class NestedSampler:
         self.batch = int(math.ceil(self.nlive / 4)) if batch is None else int(batch)
         if not 1 <= self.batch < self.nlive:
             raise ValueError("batch must lie in [1, nlive)")
+        if bound not in ("single", "multi"):
+            raise ValueError("bound must be 'single' or 'multi'")
+        self.bound, self.enlarge, self.max_ellipsoids = bound, float(enlarge), int(max_ellipsoids)
+        if not self.enlarge >= 1.0 or self.max_ellipsoids < 1:
+            raise ValueError("enlarge must be >= 1 and max_ellipsoids >= 1")
+        self.n_ellipsoids = []
+        if sample == "unif":
+            if self.nlive - self.batch < self.ndim + 2:
+                raise ValueError(f"sample='unif': {self.nlive - self.batch} surviving live points per iteration (nlive - batch) "
+                                 f"cannot bound an ellipsoid in {self.ndim} dimensions; at least ndim + 2 are needed")
+            if self.nlive < LIVE_PER_DIM * self.ndim:
+                warnings.warn("ellipsoid bounds from fewer than 50 live points per dimension can cut the likelihood contour and "
+                              "bias log Z high", UserWarning, stacklevel=2)
         self.rng = np.random.default_rng(seed)
         self.call = 0
         self.scale = 1.0
@@ -251,6 +370,21 @@ class NestedSampler:
         self.n_stuck += int(np.sum(nacc == 0))
         self.scale = update_scale(self.scale, float(np.sum(nacc)) / (len(u0) * max(self.walks, 1)), self.ndim)
         return np.asarray(u), np.asarray(logl)
+
+    def _unif(self, points, lstar, K):
+        """K points with logL > ``lstar`` drawn uniformly inside ellipsoids around ``points`` (fewer: the backend gave up)."""
+        if points.shape[0] < self.ndim + 2:
+            raise ValueError(f"sample='unif': {points.shape[0]} points cannot bound an ellipsoid in {self.ndim} dimensions")
+        ells = bounding_ellipsoids(points, self.bound, self.enlarge, self.max_ellipsoids)
+        self.n_ellipsoids.append(len(ells))
+        u, logl, nev, _ = self.backend.unif(self.call, ells, lstar, K)
+        self.call += 1
+        self.ncall += int(nev)
+        return np.asarray(u, dtype=np.float64).reshape(-1, self.ndim), np.asarray(logl, dtype=np.float64).reshape(-1)
+
+    def _inefficient(self, got, K):
+        warnings.warn(f"nested sampling: the ellipsoid draws found {got} of {K} points above L* before the candidate cap; the run "
+                      "stops here")
 
     def _static(self, live_u, live_l, logl_lo, logl_hi, dlogz, maxiter, maxcall, checkpoint=None):
         live_u, live_l = np.array(live_u, dtype=np.float64), np.array(live_l, dtype=np.float64)
@@ -286,9 +420,17 @@ class NestedSampler:
                 status = "plateau"
                 live_u, live_l = live_u[surv], live_l[surv]
                 break
-            chol = _chol(live_u[surv])
-            starts = cand[self.rng.integers(0, cand.shape[0], size=K)]
-            nu, nl = self._walk(live_u[starts], live_l[starts], lstar, chol)
+            if self.sample == "unif":
+                nu, nl = self._unif(live_u[surv], lstar, K)
+                if nl.shape[0] < K:
+                    self._inefficient(nl.shape[0], K)
+                    status = "inefficient"
+                    live_u, live_l = live_u[surv], live_l[surv]
+                    break
+            else:
+                chol = _chol(live_u[surv])
+                starts = cand[self.rng.integers(0, cand.shape[0], size=K)]
+                nu, nl = self._walk(live_u[starts], live_l[starts], lstar, chol)
             live_u[rem], live_l[rem] = nu, nl
             if checkpoint is not None:
                 self._current = self._with_live(du, dl, dn, live_u, live_l, logl_lo)
@@ -347,13 +489,20 @@ class NestedSampler:
                     self.ncall += nb
                 else:
                     cand = np.flatnonzero(ml > l_lo)
-                    chol = _chol(mu[cand])
-                    starts = cand[self.rng.integers(0, cand.shape[0], size=nb)]
-                    bu, bl = self._walk(mu[starts], ml[starts], l_lo, chol)
+                    if self.sample == "unif":
+                        bu, bl = self._unif(mu[cand], l_lo, nb)
+                        if bl.shape[0] < nb:
+                            self._inefficient(bl.shape[0], nb)
+                            status = "inefficient"
+                            break
+                    else:
+                        chol = _chol(mu[cand])
+                        starts = cand[self.rng.integers(0, cand.shape[0], size=nb)]
+                        bu, bl = self._walk(mu[starts], ml[starts], l_lo, chol)
                 run, st = self._static(bu, bl, l_lo, l_hi, dlogz, maxiter, maxcall, checkpoint)
                 self.runs.append(run)
                 nbatch += 1
-                if st == "plateau":
+                if st in ("plateau", "inefficient"):
                     status = st
                     break
         self.results = self._results(status, nbatch)
@@ -401,7 +550,9 @@ class GPUWalkBackend:
     ``transform(u)`` returns the scaled coordinates the kernels evaluate the GP at.
     Split: ``host_loglike(u [m,d]) -> [m]`` is called between alabi_ns_propose and alabi_ns_accept for the in-cube proposals
     of every step.  ``to_theta(u [m,d]) -> [m,d]`` maps cube points to the samples reported.
-    ``rslice`` is the slice move on the same two paths: ``ns_slice_kernel``, or alabi_ns_slice_step around ``host_loglike``."""
+    ``rslice`` is the slice move on the same two paths: ``ns_slice_kernel``, or alabi_ns_slice_step around ``host_loglike``;
+    ``unif`` the uniform draws inside ellipsoids: ``ns_unif_draw_kernel`` + ``ns_unif_select_kernel``, with ``host_loglike``
+    between the two."""
 
     def __init__(self, gp, y, bounds, seed, to_theta, logp_affine=(1.0, 0.0), logp_map=None, host_loglike=None,
                  normal_prior=None):
@@ -420,6 +571,8 @@ class GPUWalkBackend:
             self.normal_prior = tuple(np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(self.ndim))
                                       for v in normal_prior)
         self.host_calls = 0
+        self.evals_launched = 0          # unif: every evaluation the device (or the host) made, discarded chunk tails included
+        self._unif_eff = 0.25            # accept fraction of the previous unif call
         self._ns = None
 
     @property
@@ -558,3 +711,50 @@ class GPUWalkBackend:
                        "alabi_ns_slice_end")
         n = counts.cpu().numpy()
         return u.cpu().numpy(), logl.cpu().numpy(), n[:K], n[K:2 * K], n[2 * K:3 * K], n[3 * K:]
+
+    def unif(self, call, ells, logl_star, K, cand_id0=0, chunk=None):
+        """K points with logL > ``logl_star`` uniform in the union of the ellipsoids ``ells`` (``Ellipsoids``) inside the cube:
+        (u [k,d], logl [k], n_eval, n_cand) with k = K unless the search gave up after max(1e5, 1e4 K) candidates.  Candidates
+        ``cand_id0``, ``cand_id0`` + 1, ... are drawn and tested in chunks (``ns_unif_draw_kernel``) and taken in candidate order
+        (``ns_unif_select_kernel``), so the result does not depend on ``chunk``; the default is ceil(1.25 need / eff) rounded up to
+        64 within [256, 65536], eff being the accept fraction of the previous call (0.25 at first).  ``n_eval`` / ``n_cand``:
+        likelihood evaluations / candidates up to the last one taken; ``evals_launched`` also counts the discarded tail.  With
+        ``host_loglike`` the device stops after the thinning test and the host evaluates the chunk's surviving candidates."""
+        ns, lib, dev, stream = self._ensure(), _lib.lib(), _dev(), _lib.current_stream()
+        K, d, E = int(K), self.ndim, len(ells)
+        tab = [torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)
+               for a in (ells.centres, ells.axes, ells.inv_axes, ells.cum)]
+        u_out = torch.empty((max(K, 1), d), dtype=torch.float64, device=dev)
+        l_out = torch.empty(max(K, 1), dtype=torch.float64, device=dev)
+        counts = torch.zeros(5, dtype=torch.int32, device=dev)
+        cap = max(100000, 10000 * K)
+        taken = n_eval = n_cand = launched = 0
+        cid = int(cand_id0)
+        while taken < K and launched < cap:
+            need = K - taken
+            if chunk is None:
+                M = min(max(64 * int(math.ceil(1.25 * need / max(self._unif_eff, 1e-6) / 64.0)), 256), 65536)
+            else:
+                M = int(chunk)
+            cu = torch.empty((M, d), dtype=torch.float64, device=dev)
+            cl = torch.empty(M, dtype=torch.float64, device=dev)
+            cs = torch.empty(M, dtype=torch.int32, device=dev)
+            _lib.check(lib.alabi_ns_unif_draw(ns, int(call), cid, M, 0 if self.host_loglike is not None else 1, E, _lib.ptr(tab[0]),
+                                              _lib.ptr(tab[1]), _lib.ptr(tab[2]), _lib.ptr(tab[3]), _lib.ptr(cu), _lib.ptr(cl),
+                                              _lib.ptr(cs), stream), "alabi_ns_unif_draw")
+            status = cs.cpu().numpy()
+            ev = status == 2
+            if self.host_loglike is not None and ev.any():
+                lh = np.full(M, -np.inf)
+                lh[ev] = self._host(cu.cpu().numpy()[ev])
+                cl = torch.as_tensor(lh, device=dev)
+            self.evals_launched += int(ev.sum())
+            _lib.check(lib.alabi_ns_unif_select(ns, M, _lib.ptr(cu), _lib.ptr(cl), _lib.ptr(cs), float(logl_star), need,
+                                                C.c_void_p(u_out.data_ptr() + 8 * d * taken), C.c_void_p(l_out.data_ptr() + 8 * taken),
+                                                _lib.ptr(counts), stream), "alabi_ns_unif_select")
+            c = counts.cpu().numpy()
+            taken += int(c[0]); n_cand += int(c[1]); n_eval += int(c[2])
+            cid += M
+            launched += M
+        self._unif_eff = max(taken, 1) / max(n_cand, 1)
+        return u_out[:taken].cpu().numpy(), l_out[:taken].cpu().numpy(), n_eval, n_cand

@@ -393,8 +393,26 @@ int alabi_ns_slice_begin(alabi_ns* ns, const double* u0, const double* logl0, in
 int alabi_ns_slice_step(alabi_ns* ns, long long call, int walk_id0, int K, double logl_star, const double* chol, double scale,
                         int slices, void* state, const double* logl_query, double* u_query, int* active, void* stream);
 int alabi_ns_slice_end(alabi_ns* ns, int K, const void* state, double* u_out, double* logl_out, int* counts, void* stream);
-/* Path of the last alabi_ns_walk / alabi_ns_slice: 1 training set resident in registers, 2 tiled (point pairs beyond the block
- * re-read from L2 every step). */
+/* Uniform draws inside bounding ellipsoids (MultiNest's move, the replacement step of SurrogateModel.run_pymultinest,
+ * alabi/core.py:2790-3238; dynesty's sample="unif").  The table, device arrays: E ellipsoids {c_e + A_e z : |z| <= 1}, centres [E,d],
+ * axes [E,d,d] (A, row-major, lower triangle read), inv_axes [E,d,d] (A^-1 likewise), cum [E] cumulative volume fractions with
+ * cum[E-1] = 1.  Candidate i of the launch has the global id cand_id0 + i; its draws are keyed by (seed, call, id) alone (layout in
+ * nested_unif.hip), so a call split into several launches by cand_id0 gives the same bits.  A candidate is drawn uniformly in the
+ * ellipsoid chosen by volume and gets cand_status 0 (outside the cube), 1 (thinned: inside q ellipsoids it survives with probability
+ * 1 / q, which makes the draw uniform over the union) or 2 (evaluated: cand_logl = logL); cand_logl = -inf below 2; cand_u [M,d]
+ * holds every candidate's point.  evaluate = 0 stops after the thinning test (status 2, cand_logl = -inf, for a host likelihood to
+ * fill) and needs no training set.  E outside [1, ALABI_NS_MAX_ELLIPSOIDS], M < 0 or a NULL table: ALABI_BAD_ARGUMENT. */
+#define ALABI_NS_MAX_ELLIPSOIDS 32
+int alabi_ns_unif_draw(alabi_ns* ns, long long call, int cand_id0, int M, int evaluate, int E, const double* centres,
+                       const double* axes, const double* inv_axes, const double* cum, double* cand_u, double* cand_logl,
+                       int* cand_status, void* stream);
+/* The first `need` candidates, in candidate order, with status 2 and cand_logl > logl_star: rows to u_out [need,d] / logl_out
+ * [need]; counts, device int32 [5]: taken, consumed (the index after the last taken candidate when `need` were found, else M; 0 for
+ * need = 0), and the evaluated / outside / thinned candidates among the consumed. */
+int alabi_ns_unif_select(alabi_ns* ns, int M, const double* cand_u, const double* cand_logl, const int* cand_status,
+                         double logl_star, int need, double* u_out, double* logl_out, int* counts, void* stream);
+/* Path of the last alabi_ns_walk / alabi_ns_slice / alabi_ns_unif_draw (evaluate = 1): 1 training set resident in registers, 2
+ * tiled (point pairs beyond the block re-read from L2 every step). */
 int alabi_ns_last_path(alabi_ns* ns, int* path /* host */);
 
 /* Gaussian kernel density estimate: scipy.stats.gaussian_kde(dataset, bw_method, weights) as built and evaluated by the

@@ -10,6 +10,11 @@ reference-shaped CPU leg (one oracle predict per likelihood call, as dynesty cal
                                            # uniform map and with a normal prior on every coordinate, three rounds each (the
                                            # uniform rows also run on a tree without the feature, for a before / after), and the
                                            # tutorial-sized run_dynesty with prior_transform_normal fused / as a host callable
+    python tools/prof_nested.py --unif     # uniform draws in bounding ellipsoids (run_pymultinest's move): HIP-event time of one draw +
+                                           # select launch pair at M = 256 / 1024 / 4096 candidates for N = 2000, d = 10 and N = 200,
+                                           # d = 2; wall time, ncall, evals_launched and evaluations per dead point of the tutorial
+                                           # setting and of C3 size with sample="unif" beside sample="rwalk" on the same build.
+                                           # Writes profiles/nested_unif.txt as well.
 """
 import json
 import math
@@ -27,8 +32,14 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from conftest import make_problem  # noqa: E402
 
 
+_SINK = None
+
+
 def emit(**kw):
     print(json.dumps(kw), flush=True)
+    if _SINK is not None:
+        _SINK.write(json.dumps(kw) + "\n")
+        _SINK.flush()
 
 
 def walk_kernel():
@@ -271,6 +282,84 @@ def end_to_end_moves(d=10, ntrain=2000, nlive=500):
              logzerr=float(r.logzerr[-1]), status=r.status, n_stuck=int(r.n_stuck), scale=float(sm.dynesty_sampler.scale))
 
 
+def unif_kernels(N, d, rounds=3, reps=10):
+    """One ns_unif_draw_kernel + ns_unif_select_kernel pair by HIP events, `rounds` times per M; the ellipsoids are the sampler's own
+    bounds around the prior draws above the median logL, need = M / 4."""
+    from alabi_amd import HipGP, _lib
+    from alabi_amd.nested import GPUWalkBackend, bounding_ellipsoids
+    X, y, h = make_problem(N, d, 0)
+    g = HipGP(d, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"])
+    g.compute(X)
+    box = np.array([[-3.0, 3.0]] * d)
+    be = GPUWalkBackend(g, y, box, seed=1, to_theta=lambda u: u)
+    u, l = be.prior(0, 4096)
+    lstar = float(np.quantile(l, 0.5))
+    ells = bounding_ellipsoids(u[l > lstar], "multi")
+    lib, ns, st = _lib.lib(), be._ensure(), _lib.current_stream()
+    tab = [torch.as_tensor(a, device="cuda") for a in (ells.centres, ells.axes, ells.inv_axes, ells.cum)]
+    for M in (256, 1024, 4096):
+        need = M // 4
+        cu = torch.empty((M, d), dtype=torch.float64, device="cuda")
+        cl = torch.empty(M, dtype=torch.float64, device="cuda")
+        cs = torch.empty(M, dtype=torch.int32, device="cuda")
+        uo = torch.empty((need, d), dtype=torch.float64, device="cuda")
+        lo = torch.empty(need, dtype=torch.float64, device="cuda")
+        counts = torch.zeros(5, dtype=torch.int32, device="cuda")
+
+        def pair(call):
+            _lib.check(lib.alabi_ns_unif_draw(ns, call, 0, M, 1, len(ells), *[_lib.ptr(t) for t in tab], _lib.ptr(cu), _lib.ptr(cl),
+                                              _lib.ptr(cs), st), "alabi_ns_unif_draw")
+            _lib.check(lib.alabi_ns_unif_select(ns, M, _lib.ptr(cu), _lib.ptr(cl), _lib.ptr(cs), lstar, need, _lib.ptr(uo),
+                                                _lib.ptr(lo), _lib.ptr(counts), st), "alabi_ns_unif_select")
+        pair(1)
+        pair(2)
+        torch.cuda.synchronize()
+        for rnd in range(rounds):
+            ms, ev = 0.0, 0
+            for i in range(reps):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                pair(100 + i)
+                b.record()
+                torch.cuda.synchronize()
+                ms += a.elapsed_time(b)
+                ev += int((cs == 2).sum().item())
+            c = counts.cpu().numpy()
+            emit(what="ns_unif_draw+select", N=N, d=d, M=M, need=need, ellipsoids=len(ells), round=rnd, path=be.last_path(),
+                 us_per_pair=ms / reps * 1e3, evals_per_launch=ev / reps, us_per_evaluated_candidate=ms * 1e3 / max(ev, 1),
+                 last_counts=[int(v) for v in c])
+    be.close()
+
+
+def unif_end_to_end(name, d, ntrain, nlive, bounds, runs=2):
+    """run_pymultinest (sample="unif") beside run_dynesty static with sample="rwalk", same model, same build, alternating."""
+    import tempfile
+
+    from alabi_amd import SurrogateModel
+    sm = SurrogateModel(lnlike_fn=_gauss(d, 0), bounds=[bounds] * d, savedir=tempfile.mkdtemp(), verbose=False,
+                        random_state=0, cache=False)
+    sm.init_samples(ntrain=ntrain)
+    sm.init_gp(hyperopt_method="ml", gp_nopt=1)
+    for run in range(runs + 1):                                   # run 0: warm-up
+        t0 = time.perf_counter()
+        sm.run_pymultinest(sampler_kwargs={"n_live_points": nlive, "seed": 1 + run}, min_ess=0)
+        wall = time.perf_counter() - t0
+        r, s = sm.pymultinest_results, sm.pymultinest_sampler
+        if run:
+            emit(what="run_pymultinest", config=name, sample="unif", d=d, N=ntrain, nlive=nlive, run=run, wall_s=wall,
+                 niter=int(r.niter), ncall=int(r.ncall), evals_launched=int(s.backend.evals_launched),
+                 evals_per_dead_point=r.ncall / r.niter, launched_per_dead_point=s.backend.evals_launched / r.niter,
+                 max_ellipsoids=int(max(s.n_ellipsoids)), logz=float(r.logz[-1]), logzerr=float(r.logzerr[-1]), status=r.status)
+        t0 = time.perf_counter()
+        sm.run_dynesty(mode="static", sampler_kwargs={"nlive": nlive, "seed": 1 + run, "sample": "rwalk"}, min_ess=0)
+        wall = time.perf_counter() - t0
+        r = sm.dynesty_results
+        if run:
+            emit(what="run_dynesty", config=name, sample="rwalk", d=d, N=ntrain, nlive=nlive, run=run, wall_s=wall,
+                 niter=int(r.niter), ncall=int(r.ncall), evals_per_dead_point=r.ncall / r.niter, logz=float(r.logz[-1]),
+                 logzerr=float(r.logzerr[-1]), status=r.status)
+
+
 def _gauss(d, seed):
     rng = np.random.RandomState(seed)
     A = rng.randn(d, d)
@@ -315,6 +404,16 @@ def end_to_end(name, d, ntrain, nlive, mode, bounds):
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
     torch.cuda.set_device(0)
+    if what in ("--unif", "unif"):
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        _SINK = open(os.path.join(ROOT, "profiles", "nested_unif.txt"), "w")
+        _SINK.write("# python tools/prof_nested.py --unif : one JSON line per measurement (times: HIP events for the launch pairs, "
+                    "wall clock for the runs)\n")
+        unif_kernels(2000, 10)
+        unif_kernels(200, 2)
+        unif_end_to_end("tutorial", 2, 200, 100, (-4.0, 4.0))
+        unif_end_to_end("C3", 10, 2000, 500, (-2.0, 2.0))
+        _SINK.close()
     if what in ("--normal", "normal"):
         normal_prior()
         normal_prior_end_to_end()
