@@ -107,6 +107,8 @@ SIGNATURES = {
     "alabi_ns_slice_end": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "alabi_ns_unif_draw": (_i, [_vp, _ll, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "alabi_ns_unif_select": (_i, [_vp, _i, _vp, _vp, _vp, _d, _i, _vp, _vp, _vp, _vp]),
+    "alabi_ns_mlf_radius": (_i, [_vp, _ll, _i, _vp, _i, _vp, _vp]),
+    "alabi_ns_mlf_draw": (_i, [_vp, _ll, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
     "alabi_ns_last_path": (_i, [_vp, _pi]),
     "alabi_kde_create": (_i, [_i, C.POINTER(_vp)]),
     "alabi_kde_destroy": (_i, [_vp]),

@@ -10,14 +10,16 @@ Keeps the public surface of ``alabi.core.SurrogateModel`` that BASELINE.json's n
 george.GP -> ``HipGP``, emcee.EnsembleSampler -> ``alabi_amd.sampler.EnsembleSampler`` and
 dynesty's nested samplers -> ``alabi_amd.nested.NestedSampler``.
 
-``run_pymultinest`` (:2790) runs the same sampler with MultiNest's move, uniform draws inside bounding ellipsoids.
+``run_pymultinest`` (:2790) runs the same sampler with MultiNest's move, uniform draws inside bounding ellipsoids, and
+``run_ultranest`` (:3241) with UltraNest's MLFriends region over those ellipsoids.
 
-Out of scope here: ultranest, plotting, MPI / process pools, the
+Out of scope here: plotting, MPI / process pools, the
 parallel-chain trainer.  Deliberate differences are listed in DESIGN.md ("Differences").
 """
 from __future__ import annotations
 
 import copy
+import math
 import os
 import pickle
 import time
@@ -1275,3 +1277,106 @@ class SurrogateModel(object):
                                     logz=self.pymultinest_logz, logz_err=self.pymultinest_logz_err)
         if self.verbose:
             print(f"Saved PyMultiNest samples to {fname}")
+
+    # the reference's defaults (core.py:3490-3522); the keys without an entry in the docstring are accepted and have no effect
+    _ULTRANEST_SAMPLER_DEFAULTS = {"derived_param_names": [], "wrapped_params": None, "num_test_samples": 2, "draw_multiple": True,
+                                   "num_bootstraps": 30, "vectorized": False, "ndraw_min": 128, "ndraw_max": 65536,
+                                   "storage_backend": "hdf5", "warmstart_max_tau": -1, "resume": "subfolder", "run_num": None,
+                                   "seed": -1, "batch": None}
+    _ULTRANEST_RUN_DEFAULTS = {"update_interval_volume_fraction": 0.8, "update_interval_ncall": None, "log_interval": None,
+                               "show_status": True, "viz_callback": False, "dlogz": 0.5, "dKL": 0.5, "frac_remain": 0.01,
+                               "Lepsilon": 0.001, "min_ess": 400, "max_iters": None, "max_ncalls": None,
+                               "max_num_improvement_loops": 1, "min_num_live_points": 400, "cluster_num_live_points": 40,
+                               "insertion_test_zscore_threshold": 4, "insertion_test_window": 10, "region_class": None,
+                               "widen_before_initial_plateau_num_warn": 10000, "widen_before_initial_plateau_num_max": None}
+
+    def run_ultranest(self, like_fn=None, prior_transform=None, sampler_kwargs={}, run_kwargs={}, multi_proc=False,
+                      prior_transform_comment=None, samples_file=None, log_dir=None, resume="overwrite", min_ess=int(1e4),
+                      slice_steps=0):
+        """UltraNest's algorithm on the GPU (core.py:3241-3690): nested sampling whose replacement points are drawn uniformly in
+        the MLFriends region -- the union of the bounding ellipsoids of ``run_pymultinest``, cut down to the points within a
+        bootstrapped radius of some live point (``alabi_amd.nested.NestedSampler(sample="mlfriends")``; its module docstring states
+        the algorithm).  The balls follow a curved likelihood contour that ellipsoids cannot.
+
+        ``like_fn`` / ``prior_transform`` and the fused / host-callback paths are those of ``run_dynesty``.  sampler_kwargs:
+        ``num_bootstraps`` (30), and the extensions ``seed`` (-1: the model's seed stream) and ``batch`` (dead points per iteration;
+        ceil(nlive / 4)); a non-empty ``derived_param_names`` and a ``wrapped_params`` with any True raise ``NotImplementedError``;
+        the reference's other keys are accepted and have no effect.  run_kwargs: ``min_num_live_points`` (400: nlive),
+        ``frac_remain`` (0.01; the run stops when Z_live / Z < frac_remain, i.e. at dlogz = log1p(frac_remain)), ``max_iters``,
+        ``max_ncalls``, ``max_num_improvement_loops`` (1; 0: a static run, n > 0: up to n dynamic batches, negative: 10),
+        ``min_ess`` (400: the effective sample size the dynamic batches aim at); ``region_class`` other than None raises
+        ``NotImplementedError``; the reference's other keys (``dlogz``, ``dKL``, ``Lepsilon``, the insertion test, ...) are accepted
+        and have no effect.  An unknown key in either raises ``TypeError``.  ``slice_steps`` > 0 replaces the region draws by
+        ``slice_steps`` random-direction slice updates per point (``sample="rslice"``), where the reference swaps in a slice step
+        sampler.  ``log_dir`` and ``resume`` are accepted: nothing is logged and no directory is created; ``multi_proc`` is ignored.
+        Use at least 50 live points per dimension, as for ``run_pymultinest``.  Runs repeat until the argument ``min_ess`` samples
+        exist (at most 10) and are combined as the reference does: samples stacked, each run's weights 1 / (its sample count), log Z
+        and its error those of the run with the largest log Z.  Under ``torch.distributed`` every rank runs its own sampler
+        (seed + rank) and rank 0 writes the file."""
+        from . import dist as adist
+        from .nested import GPUWalkBackend, NestedSampler
+        rank, world = adist.world_info()
+        skw, rkw = dict(self._ULTRANEST_SAMPLER_DEFAULTS), dict(self._ULTRANEST_RUN_DEFAULTS)
+        for name, given, known in (("sampler_kwargs", sampler_kwargs, skw), ("run_kwargs", run_kwargs, rkw)):
+            if set(given) - set(known):
+                raise TypeError(f"run_ultranest: unsupported {name} {sorted(set(given) - set(known))}")
+            known.update(given)
+        if skw["derived_param_names"] is not None and len(skw["derived_param_names"]) > 0:
+            raise NotImplementedError("run_ultranest: derived_param_names (derived parameters) are not built")
+        if skw["wrapped_params"] is not None and np.any(skw["wrapped_params"]):
+            raise NotImplementedError("run_ultranest: wrapped_params (circular parameters) are not built")
+        if rkw["region_class"] is not None:
+            raise NotImplementedError("run_ultranest: region_class is not built; the region is MLFriends over bounding ellipsoids")
+        nlive = int(rkw["min_num_live_points"])
+        frac = float(rkw["frac_remain"])
+        if not frac > 0.0:
+            raise ValueError("frac_remain must be > 0")
+        dlogz = math.log1p(frac)
+        loops = int(rkw["max_num_improvement_loops"])
+        dynamic, maxbatch = loops != 0, (loops if loops > 0 else 10)
+        seed = None if int(skw["seed"]) < 0 else int(skw["seed"])
+        if int(slice_steps) > 0:
+            move = {"sample": "rslice", "slices": int(slice_steps)}
+        else:
+            move = {"sample": "mlfriends", "num_bootstraps": int(skw["num_bootstraps"])}
+        run_args = {"dlogz": dlogz, "maxiter": rkw["max_iters"], "maxcall": rkw["max_ncalls"]}
+        if dynamic:
+            run_args.update(dlogz_init=dlogz, maxbatch=maxbatch, n_effective=rkw["min_ess"])
+        t0 = time.time()
+        plan, gp_obj, y_obj = self._nested_setup(like_fn, prior_transform, prior_transform_comment)
+        if self.verbose:
+            print(f"Running MLFriends nested sampling ({'fused GPU draws' if plan.fused else 'host likelihood'}) with {nlive} "
+                  "live points...")
+        normal = {} if plan.normal_prior is None else {"normal_prior": plan.normal_prior}
+        logz, logz_err, weights = [], [], []
+
+        def run(run_number):
+            s = (self._seed() if seed is None else seed + 1000003 * (run_number - 1)) + rank
+            backend = GPUWalkBackend(gp_obj, y_obj, plan.box, seed=s, to_theta=plan.to_theta, logp_affine=plan.logp_affine,
+                                     logp_map=plan.logp_map, host_loglike=plan.host_like, **normal)
+            self.ultranest_sampler = NestedSampler(backend, nlive, dynamic=dynamic, batch=skw["batch"], seed=s, **move)
+            res = self.ultranest_sampler.run_nested(**run_args)
+            backend.close()
+            self.ultranest_results, self.ultranest_path = res, backend.path
+            eq = res.samples_equal(np.random.default_rng(s))
+            logz.append(float(res.logz[-1])); logz_err.append(float(res.logzerr[-1]))
+            weights.append(np.full(eq.shape[0], 1.0 / eq.shape[0]))
+            return eq
+
+        note = (lambda total: f", logZ = {logz[-1]:.3f} +/- {logz_err[-1]:.3f}") if self.verbose else None
+        self.ultranest_samples = post.run_until_min_ess(run, min_ess, note)
+        self.ultranest_weights = np.concatenate(weights)
+        best = int(np.argmax(logz))                  # core.py:3629-3642: the run with the highest log evidence
+        self.ultranest_logz, self.ultranest_logz_err = logz[best], logz_err[best]
+        if self.like_fn_name == "true":
+            self.ultranest_samples_true = self.ultranest_samples
+        else:
+            self.ultranest_samples_surrogate = self.ultranest_samples
+        self.ultranest_run = True
+        self.ultranest_runtime = time.time() - t0
+        if rank != 0:
+            return                                   # files are rank 0's
+        fname = self._write_samples("ultranest", self.ultranest_samples, samples_file, weights=self.ultranest_weights,
+                                    logz=self.ultranest_logz, logz_err=self.ultranest_logz_err)
+        if self.verbose:
+            print(f"Saved UltraNest samples to {fname}")

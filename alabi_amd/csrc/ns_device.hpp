@@ -1,6 +1,7 @@
 // Device code shared by the nested-sampling kernels (nested.hip: the random walk and the slice move; nested_unif.hip: uniform draws
-// inside bounding ellipsoids): the sampler handle, the kernel arguments, the Philox normals, the inverse normal CDF, the prior
-// transform and the GP mean at one point (ns_logl), plus the block-size rule and the flag dispatch of the templated kernels.
+// inside bounding ellipsoids; nested_mlf.hip: the MLFriends region over them): the sampler handle, the kernel arguments, the Philox
+// normals, the inverse normal CDF, the prior transform, the GP mean at one point (ns_logl) and the ellipsoid candidate
+// (ns_unif_candidate), plus the block-size rule and the flag dispatch of the templated kernels.
 // The draw layout (which Philox counter feeds which draw) is stated in nested.hip.
 #pragma once
 #include <cmath>
@@ -192,6 +193,70 @@ __device__ inline double ns_logl(const NsArgs& p, const f64x2 (&xa)[D], f64x2 aa
     }
     return lp;
 }
+// ---- the uniform-in-ellipsoids candidate (nested_unif.hip states the draw layout; nested_mlf.hip adds the neighbour test to it)
+struct NsUnifArgs {
+    const double* centres;       // [E, d]
+    const double* axes;          // [E, d, d] lower triangular A
+    const double* inv_axes;      // [E, d, d] lower triangular A^-1
+    const double* cum;           // [E]
+    double* cand_u;              // [M, d]
+    double* cand_logl;           // [M]
+    int* cand_status;            // [M]
+    unsigned long long seed;
+    long long call;
+    int E, M, cand_id0, d;
+};
+
+#define ALABI_NS_UNIF_STEP 0x80000000u
+
+// Candidate `cid` up to the thinning test.  Called by EVERY thread of the workgroup (blockDim.x a multiple of 64, at most 1024) with
+// identical arguments; returns the workgroup-uniform status 0 / 1 / 2 and leaves the point in u_s[0 .. d).  z_s, u_s: d doubles of
+// LDS each, cnt_s: 16 ints.  Three barriers on every path that reaches them; the caller may touch u_s / z_s / cnt_s again only in
+// ways the next call's own barriers order (it reads u_s after the return, which follows the last barrier).
+__device__ inline int ns_unif_candidate(const NsUnifArgs& q, uint32_t cid, double* z_s, double* u_s, int* cnt_s) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6, d = q.d;
+    if (tid < 64) ns_draw_normals(q.seed, q.call, cid, 0u, d, tid, z_s);
+    uint32_t r[4];
+    philox4x32_10((uint32_t)q.call, cid, ALABI_NS_UNIF_STEP, 0u, (uint32_t)q.seed, (uint32_t)(q.seed >> 32), r);
+    const double v_ell = u53(r[0], r[1]), v_rad = u53(r[2], r[3]);
+    philox4x32_10((uint32_t)q.call, cid, ALABI_NS_UNIF_STEP, 1u, (uint32_t)q.seed, (uint32_t)(q.seed >> 32), r);
+    const double v_thin = u53(r[0], r[1]);
+    int e = 0;
+    while (e < q.E - 1 && !(v_ell < q.cum[e])) ++e;
+    __syncthreads();
+    double n2 = 0.0;
+    for (int i = 0; i < d; ++i) n2 = fma(z_s[i], z_s[i], n2);
+    const double s = pow(v_rad, 1.0 / (double)d) / sqrt(n2);
+    int ok = 1;
+    if (tid < d) {
+        const double u = ns_prop_coord(q.axes + (size_t)e * d * d, d, z_s, tid, q.centres[(size_t)e * d + tid], s);
+        ok = (u > 0.0) && (u < 1.0);
+        u_s[tid] = u;
+    }
+    if (!__syncthreads_and(ok)) return 0;
+    // wave w tests ellipsoids w, w + nw, ...: lane k forms row k of A^-1 (u - c), the squared norm is summed in row order
+    int cnt = 0;
+    for (int e2 = wave; e2 < q.E; e2 += nw) {
+        if (e2 == e) continue;
+        double y = 0.0;
+        if (lane < d) {
+            const double* R = q.inv_axes + ((size_t)e2 * d + lane) * d;
+            const double* c = q.centres + (size_t)e2 * d;
+            for (int i = 0; i <= lane; ++i) y = fma(R[i], u_s[i] - c[i], y);
+        }
+        double m = 0.0;
+        for (int k = 0; k < d; ++k) {
+            const double yk = __shfl(y, k, 64);
+            m = fma(yk, yk, m);
+        }
+        cnt += (m <= 1.0) ? 1 : 0;
+    }
+    if (lane == 0) cnt_s[wave] = cnt;
+    __syncthreads();
+    int nq = 1;
+    for (int w = 0; w < nw; ++w) nq += cnt_s[w];
+    return (v_thin * (double)nq >= 1.0) ? 1 : 2;
+}
 }  // namespace alabi
 
 static inline hipStream_t ns_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -211,4 +276,19 @@ static inline int ns_threads(const alabi_gp* gp, int db) {
     int T = alabi::round_up(half, 64);
     if (T < 64) T = 64;
     return T < cap ? T : cap;
+}
+
+// The NsArgs of a kernel that evaluates logL at single points (no walk): the GP's training set in the layout of its kernel family,
+// the affine map of the log-probability and the prior transform.  ALABI_NOT_COMPUTED without a factorised GP with alpha.
+static inline int ns_point_args(alabi_ns* ns, long long call, hipStream_t s, alabi::NsArgs& a) {
+    alabi_gp* gp = ns->gp;
+    if (!gp->computed || !gp->has_alpha) return ALABI_NOT_COMPUTED;
+    const bool se = gp->kf.type == 0;
+    if (se) { const int st = alabi::ens_se_prepare(gp, s); if (st != ALABI_OK) return st; }
+    a.Xsrc = se ? gp->Xc : gp->Xt; a.Asrc = se ? gp->ens_h : gp->alpha; a.centre = gp->xa_centre;
+    a.Npad = gp->Npad; a.kf = gp->kf;
+    a.amp = ns->lp_scale * std::exp(gp->log_amp); a.mean = std::fma(ns->lp_scale, gp->mean, ns->lp_shift); a.ymap = ns->ymap;
+    a.lo = ns->lo; a.width = ns->width; a.inv_len = gp->inv_len; a.nmask = ns->nmask;
+    a.seed = ns->seed; a.call = call; a.d = ns->d;
+    return ALABI_OK;
 }

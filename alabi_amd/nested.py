@@ -1,4 +1,5 @@
-"""Nested sampling on the GPU: the static and dynamic samplers behind ``SurrogateModel.run_dynesty`` and ``run_pymultinest``.
+"""Nested sampling on the GPU: the static and dynamic samplers behind ``SurrogateModel.run_dynesty``, ``run_pymultinest`` and
+``run_ultranest``.
 
 The reference drives dynesty's ``NestedSampler`` / ``DynamicNestedSampler`` (alabi/core.py:2417-2787) for the Bayesian
 evidence log Z.  Here the nested-sampling bookkeeping runs on the host in NumPy and the likelihood work -- many independent
@@ -66,6 +67,28 @@ alabi/core.py:2790-3238; dynesty's ``sample="unif"`` with ``bound="single"`` / `
     that; at nlive = 200 a separable 24-D Gaussian is high by 12 logzerr).  A search that does not find K points within
     max(1e5, 1e4 K) candidates ends the run with status "inefficient" and a warning.
 
+The MLFriends region (``sample="mlfriends"``: UltraNest's bound, the reference's run_ultranest, alabi/core.py:3241-3690).  Everything as
+for ``sample="unif"`` -- the same point set per iteration, the same ellipsoids, the "inefficient" status and candidate cap, the
+nlive >= 50 d warning, use from the dynamic batches -- with one more test in the replacement step: a candidate counts only if it
+lies within a radius r of some live point, in a metric whitened by the live points' covariance.  A union of ellipsoids cannot follow
+a curved contour; a union of small balls around the live points can.
+  * Bounds.  ``ells = bounding_ellipsoids(points, bound, enlarge, max_ellipsoids)``, unchanged.
+  * Metric (UltraNest's cluster-wise whitening, the ellipsoid leaves as the clusters; ``mlfriends_metric``).  label_i = argmin_e
+    |A_e^-1 (p_i - c_e)|^2; S = sum_i (p_i - c_label_i)(p_i - c_label_i)^T / (n - E); L = Cholesky(S) with the jitter ladder of the
+    walk covariance; ``metric_inv`` = L^-1, lower triangular; w_i = L^-1 p_i, [n,d], computed once on the host and uploaded.
+  * Radius.  B = ``num_bootstraps`` (30) rounds; round b draws n indices idx_k = min(floor(v_k n), n - 1) with v_k from the device's
+    Philox stream (counter (call, b, 0x80000001, k)); selected = the set of drawn indices; r2_b = max over unselected i of min over
+    selected j of |w_i - w_j|^2, 0 when nothing is left out; r^2 = max_b r2_b, taken on the host from the B values and listed in
+    ``radius2``.  r^2 = 0 is legal and rejects everything but exact hits.
+  * Candidate.  Exactly the ``unif`` candidate (the same keys, ellipsoid choice, cube test and 1 / q thinning); one that would be
+    evaluated is evaluated iff some j has |metric_inv u - w_j|^2 <= r^2.  The K replacements are the first K evaluated candidates
+    with logL > L*, as before.
+  * Beyond 16384 points (dynamic batches over a long merged run) the balls are put around every ceil(n / 16384)-th point; the
+    ellipsoids are still fitted to all of them.
+  * Not carried over from UltraNest: the shrink-only region update, the wrapping-ellipsoid bootstrap
+    (``enlarge`` plays that part), the from-points / bounding-box / transformed-box draw methods, the insertion-order test, the
+    dlogz / dKL improvement criteria, wrapped and derived parameters, HDF5 / CSV logs and resume.
+
 Not built (listed in DESIGN.md "Differences"): axis-aligned ``slice`` / ``hslice`` sampling, the bootstrap stop, other weight /
 stop fractions than pfrac = 1; ``run_dynesty`` does not reach ``unif`` (``bound`` has no effect there).
 """
@@ -83,12 +106,14 @@ from . import _lib
 from .gp import _dev
 
 __all__ = ["NestedSampler", "NestedResults", "GPUWalkBackend", "PickleCheckpoint", "resample_equal", "compute_integrals",
-           "merge_runs", "update_scale", "update_scale_slice", "default_slices", "Ellipsoids", "bounding_ellipsoids"]
+           "merge_runs", "update_scale", "update_scale_slice", "default_slices", "Ellipsoids", "bounding_ellipsoids",
+           "mlfriends_metric"]
 
 MAXFRAC = 0.8
 SCALE_MIN, SCALE_MAX = 1e-4, 10.0
 SLICES_MULT = 3       # calibrated on a 24-D Gaussian (NOTES.md "Nested sampling")
 MAX_ELLIPSOIDS = 32   # ALABI_NS_MAX_ELLIPSOIDS
+MLF_MAX_POINTS = 16384  # ALABI_NS_MLF_MAX_POINTS
 LIVE_PER_DIM = 50     # below this many live points per dimension an ellipsoid fitted to them can cut the likelihood contour
 
 
@@ -204,7 +229,11 @@ class NestedResults:
 
 
 def _chol(u):
-    cov = np.atleast_2d(np.cov(np.asarray(u).T))
+    return _chol_cov(np.atleast_2d(np.cov(np.asarray(u).T)))
+
+
+def _chol_cov(cov):
+    """Lower Cholesky factor of ``cov`` [d,d] with a jitter ladder; the square roots of the diagonal when every rung fails."""
     d = cov.shape[0]
     jit = 1e-12 * max(float(np.trace(cov)) / d, 1e-300)
     for _ in range(8):
@@ -294,6 +323,25 @@ def bounding_ellipsoids(points, bound="multi", enlarge=1.25, max_ellipsoids=MAX_
     return Ellipsoids(*(np.stack([e[k] for e in done]) for k in range(3)), np.array([e[3] for e in done]))
 
 
+def mlfriends_metric(points, ells):
+    """The whitening of the MLFriends region: (labels [n], metric_inv [d,d], w [n,d]).  ``labels[i]`` is the ellipsoid of ``ells``
+    whose centre is nearest to point i in that ellipsoid's own metric; S the covariance of the points about their own ellipsoid's
+    centre, pooled over the ellipsoids (n - E degrees of freedom), so that separated clusters do not inflate it; ``metric_inv`` =
+    L^-1 with S = L L^T, lower triangular; ``w`` = the whitened points L^-1 p_i."""
+    p = np.ascontiguousarray(points, dtype=np.float64)
+    n, d = p.shape
+    E = len(ells)
+    m = np.empty((E, n))
+    for e in range(E):
+        y = np.einsum("ki,ni->nk", ells.inv_axes[e], p - ells.centres[e])
+        m[e] = np.sum(y * y, axis=1)
+    labels = np.argmin(m, axis=0)
+    r = p - ells.centres[labels]
+    L = _chol_cov((r.T @ r) / max(n - E, 1))
+    metric_inv = np.ascontiguousarray(np.tril(np.linalg.inv(L)))
+    return labels, metric_inv, np.ascontiguousarray(p @ metric_inv.T)
+
+
 class NestedSampler:
     """Static (``dynamic=False``) or dynamic nested sampler over a walk backend.
 
@@ -307,10 +355,13 @@ class NestedSampler:
     (``bounding_ellipsoids`` with ``bound`` "multi" / "single" and ``enlarge``; at most ``max_ellipsoids``) from
     ``unif(call, ells, logl_star, K) -> (u [K,d], logl [K], n_eval, n_cand)``; no walk length, no scale.  ``n_ellipsoids`` lists
     the number of ellipsoids of every such call.  A backend that returns fewer than K points ends the run with status
-    "inefficient"."""
+    "inefficient".
+    ``sample="mlfriends"``: the same with the MLFriends region on top (module docstring): per call ``mlf_radius(call, w, B) -> r2``
+    with B = ``num_bootstraps`` and ``mlfriends(call, ells, w, metric_inv, r2, logl_star, K)`` returning what ``unif`` returns;
+    ``radius2`` lists the r^2 of every such call beside ``n_ellipsoids``."""
 
     def __init__(self, backend, nlive, dynamic=False, walks=25, batch=None, seed=0, sample="rwalk", slices=None, bound="multi",
-                 enlarge=1.25, max_ellipsoids=MAX_ELLIPSOIDS):
+                 enlarge=1.25, max_ellipsoids=MAX_ELLIPSOIDS, num_bootstraps=30):
         self.backend = backend
         self.ndim = int(backend.ndim)
         self.nlive = int(nlive)
@@ -318,8 +369,8 @@ class NestedSampler:
             raise ValueError("nlive must be >= 2")
         self.dynamic = bool(dynamic)
         self.walks = int(walks)
-        if sample not in ("rwalk", "rslice", "unif"):
-            raise ValueError("sample must be 'rwalk', 'rslice' or 'unif'")
+        if sample not in ("rwalk", "rslice", "unif", "mlfriends"):
+            raise ValueError("sample must be 'rwalk', 'rslice', 'unif' or 'mlfriends'")
         self.sample = sample
         self.slices = default_slices(self.ndim) if slices is None else int(slices)
         if self.slices < 0:
@@ -332,10 +383,14 @@ class NestedSampler:
         self.bound, self.enlarge, self.max_ellipsoids = bound, float(enlarge), int(max_ellipsoids)
         if not self.enlarge >= 1.0 or self.max_ellipsoids < 1:
             raise ValueError("enlarge must be >= 1 and max_ellipsoids >= 1")
-        self.n_ellipsoids = []
-        if sample == "unif":
+        self.num_bootstraps = int(num_bootstraps)
+        if self.num_bootstraps < 1:
+            raise ValueError("num_bootstraps must be >= 1")
+        self.n_ellipsoids, self.radius2 = [], []
+        self._bounded = sample in ("unif", "mlfriends")       # replacements drawn inside bounds around the live points
+        if self._bounded:
             if self.nlive - self.batch < self.ndim + 2:
-                raise ValueError(f"sample='unif': {self.nlive - self.batch} surviving live points per iteration (nlive - batch) "
+                raise ValueError(f"sample='{sample}': {self.nlive - self.batch} surviving live points per iteration (nlive - batch) "
                                  f"cannot bound an ellipsoid in {self.ndim} dimensions; at least ndim + 2 are needed")
             if self.nlive < LIVE_PER_DIM * self.ndim:
                 warnings.warn("ellipsoid bounds from fewer than 50 live points per dimension can cut the likelihood contour and "
@@ -374,10 +429,17 @@ class NestedSampler:
     def _unif(self, points, lstar, K):
         """K points with logL > ``lstar`` drawn uniformly inside ellipsoids around ``points`` (fewer: the backend gave up)."""
         if points.shape[0] < self.ndim + 2:
-            raise ValueError(f"sample='unif': {points.shape[0]} points cannot bound an ellipsoid in {self.ndim} dimensions")
+            raise ValueError(f"sample='{self.sample}': {points.shape[0]} points cannot bound an ellipsoid in {self.ndim} dimensions")
         ells = bounding_ellipsoids(points, self.bound, self.enlarge, self.max_ellipsoids)
         self.n_ellipsoids.append(len(ells))
-        u, logl, nev, _ = self.backend.unif(self.call, ells, lstar, K)
+        if self.sample == "mlfriends":
+            friends = points[::-(-points.shape[0] // MLF_MAX_POINTS)]      # every point up to the device's limit
+            _, metric_inv, w = mlfriends_metric(friends, ells)
+            r2 = float(self.backend.mlf_radius(self.call, w, self.num_bootstraps))
+            self.radius2.append(r2)
+            u, logl, nev, _ = self.backend.mlfriends(self.call, ells, w, metric_inv, r2, lstar, K)
+        else:
+            u, logl, nev, _ = self.backend.unif(self.call, ells, lstar, K)
         self.call += 1
         self.ncall += int(nev)
         return np.asarray(u, dtype=np.float64).reshape(-1, self.ndim), np.asarray(logl, dtype=np.float64).reshape(-1)
@@ -420,7 +482,7 @@ class NestedSampler:
                 status = "plateau"
                 live_u, live_l = live_u[surv], live_l[surv]
                 break
-            if self.sample == "unif":
+            if self._bounded:
                 nu, nl = self._unif(live_u[surv], lstar, K)
                 if nl.shape[0] < K:
                     self._inefficient(nl.shape[0], K)
@@ -489,7 +551,7 @@ class NestedSampler:
                     self.ncall += nb
                 else:
                     cand = np.flatnonzero(ml > l_lo)
-                    if self.sample == "unif":
+                    if self._bounded:
                         bu, bl = self._unif(mu[cand], l_lo, nb)
                         if bl.shape[0] < nb:
                             self._inefficient(bl.shape[0], nb)
@@ -552,7 +614,8 @@ class GPUWalkBackend:
     of every step.  ``to_theta(u [m,d]) -> [m,d]`` maps cube points to the samples reported.
     ``rslice`` is the slice move on the same two paths: ``ns_slice_kernel``, or alabi_ns_slice_step around ``host_loglike``;
     ``unif`` the uniform draws inside ellipsoids: ``ns_unif_draw_kernel`` + ``ns_unif_select_kernel``, with ``host_loglike``
-    between the two."""
+    between the two; ``mlf_radius`` / ``mlfriends`` the MLFriends region over them: ``ns_mlf_radius_kernel``, and
+    ``ns_mlf_draw_kernel`` in the place of ``ns_unif_draw_kernel``."""
 
     def __init__(self, gp, y, bounds, seed, to_theta, logp_affine=(1.0, 0.0), logp_map=None, host_loglike=None,
                  normal_prior=None):
@@ -720,10 +783,46 @@ class GPUWalkBackend:
         64 within [256, 65536], eff being the accept fraction of the previous call (0.25 at first).  ``n_eval`` / ``n_cand``:
         likelihood evaluations / candidates up to the last one taken; ``evals_launched`` also counts the discarded tail.  With
         ``host_loglike`` the device stops after the thinning test and the host evaluates the chunk's surviving candidates."""
-        ns, lib, dev, stream = self._ensure(), _lib.lib(), _dev(), _lib.current_stream()
-        K, d, E = int(K), self.ndim, len(ells)
+        lib, dev, E = _lib.lib(), _dev(), len(ells)
         tab = [torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)
                for a in (ells.centres, ells.axes, ells.inv_axes, ells.cum)]
+
+        def draw(ns, cid, M, evaluate, cu, cl, cs, stream):
+            _lib.check(lib.alabi_ns_unif_draw(ns, int(call), cid, M, evaluate, E, _lib.ptr(tab[0]), _lib.ptr(tab[1]), _lib.ptr(tab[2]),
+                                              _lib.ptr(tab[3]), _lib.ptr(cu), _lib.ptr(cl), _lib.ptr(cs), stream),
+                       "alabi_ns_unif_draw")
+        return self._draw_select(draw, logl_star, K, cand_id0, chunk)
+
+    def mlf_radius(self, call, w, B):
+        """r^2 of the MLFriends region around the whitened points ``w`` [n,d]: the largest, over ``B`` bootstrap rounds, of the
+        squared distance from a point left out of the round to the nearest point drawn (``ns_mlf_radius_kernel``; the maximum of the
+        B values is taken here)."""
+        ns, dev = self._ensure(), _dev()
+        wd = torch.as_tensor(np.ascontiguousarray(np.asarray(w, dtype=np.float64).reshape(-1, self.ndim)), device=dev)
+        r2 = torch.empty(max(int(B), 1), dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().alabi_ns_mlf_radius(ns, int(call), int(wd.shape[0]), _lib.ptr(wd), int(B), _lib.ptr(r2),
+                                                  _lib.current_stream()), "alabi_ns_mlf_radius")
+        return float(r2.max().item())
+
+    def mlfriends(self, call, ells, w, metric_inv, r2, logl_star, K, cand_id0=0, chunk=None):
+        """``unif`` with the MLFriends test: a candidate is evaluated only if some row of ``w`` [n,d] lies within ``r2`` (squared)
+        of ``metric_inv`` u (``ns_mlf_draw_kernel``).  The same loop, chunk rule, counters and host-likelihood split."""
+        lib, dev, E = _lib.lib(), _dev(), len(ells)
+        tab = [torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)
+               for a in (ells.centres, ells.axes, ells.inv_axes, ells.cum, np.asarray(w).reshape(-1, self.ndim), metric_inv)]
+        n = int(tab[4].shape[0])
+
+        def draw(ns, cid, M, evaluate, cu, cl, cs, stream):
+            _lib.check(lib.alabi_ns_mlf_draw(ns, int(call), cid, M, evaluate, E, _lib.ptr(tab[0]), _lib.ptr(tab[1]), _lib.ptr(tab[2]),
+                                             _lib.ptr(tab[3]), n, _lib.ptr(tab[4]), _lib.ptr(tab[5]), float(r2), _lib.ptr(cu),
+                                             _lib.ptr(cl), _lib.ptr(cs), stream), "alabi_ns_mlf_draw")
+        return self._draw_select(draw, logl_star, K, cand_id0, chunk)
+
+    def _draw_select(self, draw, logl_star, K, cand_id0, chunk):
+        """The chunk loop of ``unif`` and ``mlfriends``: ``draw(ns, cid, M, evaluate, cand_u, cand_logl, cand_status, stream)``
+        launches the candidates cid .. cid + M - 1; the host likelihood fills in between; ``ns_unif_select_kernel`` takes."""
+        ns, lib, dev, stream = self._ensure(), _lib.lib(), _dev(), _lib.current_stream()
+        K, d = int(K), self.ndim
         u_out = torch.empty((max(K, 1), d), dtype=torch.float64, device=dev)
         l_out = torch.empty(max(K, 1), dtype=torch.float64, device=dev)
         counts = torch.zeros(5, dtype=torch.int32, device=dev)
@@ -739,9 +838,7 @@ class GPUWalkBackend:
             cu = torch.empty((M, d), dtype=torch.float64, device=dev)
             cl = torch.empty(M, dtype=torch.float64, device=dev)
             cs = torch.empty(M, dtype=torch.int32, device=dev)
-            _lib.check(lib.alabi_ns_unif_draw(ns, int(call), cid, M, 0 if self.host_loglike is not None else 1, E, _lib.ptr(tab[0]),
-                                              _lib.ptr(tab[1]), _lib.ptr(tab[2]), _lib.ptr(tab[3]), _lib.ptr(cu), _lib.ptr(cl),
-                                              _lib.ptr(cs), stream), "alabi_ns_unif_draw")
+            draw(ns, cid, M, 0 if self.host_loglike is not None else 1, cu, cl, cs, stream)
             status = cs.cpu().numpy()
             ev = status == 2
             if self.host_loglike is not None and ev.any():

@@ -411,7 +411,24 @@ int alabi_ns_unif_draw(alabi_ns* ns, long long call, int cand_id0, int M, int ev
  * need = 0), and the evaluated / outside / thinned candidates among the consumed. */
 int alabi_ns_unif_select(alabi_ns* ns, int M, const double* cand_u, const double* cand_logl, const int* cand_status,
                          double logl_star, int need, double* u_out, double* logl_out, int* counts, void* stream);
-/* Path of the last alabi_ns_walk / alabi_ns_slice / alabi_ns_unif_draw (evaluate = 1): 1 training set resident in registers, 2
+/* The MLFriends region (UltraNest's bound, the replacement step of SurrogateModel.run_ultranest, alabi/core.py:3241-3690) over the
+ * ellipsoids above: a candidate counts only if it lies within r of one of n live points in a whitened metric.  w, device [n,d]: the
+ * whitened live points L^-1 p_i; metric_inv, device [d,d]: L^-1, row-major, lower triangle read (layout and draws in nested_mlf.hip).
+ * alabi_ns_mlf_radius runs B bootstrap rounds: round b draws n indices with replacement, keyed by (seed, call, b), and writes
+ * r2_out[b] = the largest squared distance from a point left out to the nearest point drawn (0 when none is left out); the caller
+ * takes the maximum.  n outside [1, ALABI_NS_MLF_MAX_POINTS], B < 1 or a NULL array: ALABI_BAD_ARGUMENT, nothing launched. */
+#define ALABI_NS_MLF_MAX_POINTS 16384
+int alabi_ns_mlf_radius(alabi_ns* ns, long long call, int n, const double* w /* device [n,d] */, int B,
+                        double* r2_out /* device [B] */, void* stream);
+/* alabi_ns_unif_draw with one more test: a candidate that would get status 2 keeps it iff some j < n has
+ * |metric_inv u - w_j|^2 <= r2, and gets status 1 otherwise, so that status 1 means "thinned, or no live point within r".
+ * r2 = +inf gives the bits of alabi_ns_unif_draw, r2 = 0 keeps exact hits only.  Every check of alabi_ns_unif_draw, and n outside
+ * [1, ALABI_NS_MLF_MAX_POINTS], a NaN or negative r2 or a NULL w / metric_inv: ALABI_BAD_ARGUMENT, nothing launched. */
+int alabi_ns_mlf_draw(alabi_ns* ns, long long call, int cand_id0, int M, int evaluate, int E, const double* centres,
+                      const double* axes, const double* inv_axes, const double* cum, int n, const double* w,
+                      const double* metric_inv /* device [d,d], lower triangle read */, double r2,
+                      double* cand_u, double* cand_logl, int* cand_status, void* stream);
+/* Path of the last alabi_ns_walk / alabi_ns_slice / alabi_ns_unif_draw / alabi_ns_mlf_draw (evaluate = 1): 1 training set resident in registers, 2
  * tiled (point pairs beyond the block re-read from L2 every step). */
 int alabi_ns_last_path(alabi_ns* ns, int* path /* host */);
 

@@ -15,6 +15,11 @@ reference-shaped CPU leg (one oracle predict per likelihood call, as dynesty cal
                                            # d = 2; wall time, ncall, evals_launched and evaluations per dead point of the tutorial
                                            # setting and of C3 size with sample="unif" beside sample="rwalk" on the same build.
                                            # Writes profiles/nested_unif.txt as well.
+    python tools/prof_nested.py --mlf      # the MLFriends region (run_ultranest's move): HIP-event time of ns_mlf_radius_kernel (30
+                                           # rounds) and of one ns_mlf_draw_kernel + select pair beside the ns_unif_draw_kernel +
+                                           # select pair, in turn on the same build, at (N, d) = (2000, 10) and (200, 2) with 400
+                                           # live points; run_ultranest beside run_pymultinest end to end on the 2-D Rosenbrock
+                                           # surrogate.  Writes profiles/nested_mlfriends.txt as well.
 """
 import json
 import math
@@ -360,6 +365,123 @@ def unif_end_to_end(name, d, ntrain, nlive, bounds, runs=2):
                  logzerr=float(r.logzerr[-1]), status=r.status)
 
 
+def mlf_kernels(N, d, nlive=400, B=30, rounds=3, reps=10):
+    """ns_mlf_radius_kernel, and the draw + select pair with and without the neighbour test, by HIP events, in turn.  Live points:
+    `nlive` of the prior draws above the median logL; r^2 the bootstrapped radius of those points, as the sampler would use."""
+    from alabi_amd import HipGP, _lib
+    from alabi_amd.nested import GPUWalkBackend, bounding_ellipsoids, mlfriends_metric
+    X, y, h = make_problem(N, d, 0)
+    g = HipGP(d, h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"])
+    g.compute(X)
+    box = np.array([[-3.0, 3.0]] * d)
+    be = GPUWalkBackend(g, y, box, seed=1, to_theta=lambda u: u)
+    u, l = be.prior(0, 4096)
+    lstar = float(np.quantile(l, 0.5))
+    live = u[l > lstar][:nlive]
+    ells = bounding_ellipsoids(live, "multi")
+    _, minv, w = mlfriends_metric(live, ells)
+    lib, ns, st = _lib.lib(), be._ensure(), _lib.current_stream()
+    tab = [torch.as_tensor(np.ascontiguousarray(a), device="cuda") for a in (ells.centres, ells.axes, ells.inv_axes, ells.cum, w, minv)]
+    r2d = torch.empty(B, dtype=torch.float64, device="cuda")
+
+    def radius(call):
+        _lib.check(lib.alabi_ns_mlf_radius(ns, call, len(w), _lib.ptr(tab[4]), B, _lib.ptr(r2d), st), "alabi_ns_mlf_radius")
+    radius(1)
+    radius(2)
+    torch.cuda.synchronize()
+    r2 = float(r2d.max().item())
+    for rnd in range(rounds):
+        ms = 0.0
+        for i in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            radius(100 + i)
+            b.record()
+            torch.cuda.synchronize()
+            ms += a.elapsed_time(b)
+        emit(what="ns_mlf_radius", N=N, d=d, nlive=len(w), B=B, round=rnd, us_per_launch=ms / reps * 1e3, r2=r2)
+    for M in (256, 1024, 4096):
+        need = M // 4
+        cu = torch.empty((M, d), dtype=torch.float64, device="cuda")
+        cl = torch.empty(M, dtype=torch.float64, device="cuda")
+        cs = torch.empty(M, dtype=torch.int32, device="cuda")
+        uo = torch.empty((need, d), dtype=torch.float64, device="cuda")
+        lo = torch.empty(need, dtype=torch.float64, device="cuda")
+        counts = torch.zeros(5, dtype=torch.int32, device="cuda")
+
+        def select():
+            _lib.check(lib.alabi_ns_unif_select(ns, M, _lib.ptr(cu), _lib.ptr(cl), _lib.ptr(cs), lstar, need, _lib.ptr(uo),
+                                                _lib.ptr(lo), _lib.ptr(counts), st), "alabi_ns_unif_select")
+
+        def unif_pair(call):
+            _lib.check(lib.alabi_ns_unif_draw(ns, call, 0, M, 1, len(ells), *[_lib.ptr(t) for t in tab[:4]], _lib.ptr(cu), _lib.ptr(cl),
+                                              _lib.ptr(cs), st), "alabi_ns_unif_draw")
+            select()
+
+        def mlf_pair(call):
+            _lib.check(lib.alabi_ns_mlf_draw(ns, call, 0, M, 1, len(ells), *[_lib.ptr(t) for t in tab[:4]], len(w), _lib.ptr(tab[4]),
+                                             _lib.ptr(tab[5]), r2, _lib.ptr(cu), _lib.ptr(cl), _lib.ptr(cs), st), "alabi_ns_mlf_draw")
+            select()
+        for fn in (unif_pair, mlf_pair):
+            fn(1)
+            fn(2)
+        torch.cuda.synchronize()
+        for rnd in range(rounds):
+            for name, fn in (("ns_unif_draw+select", unif_pair), ("ns_mlf_draw+select", mlf_pair)):
+                ms, ev = 0.0, 0
+                for i in range(reps):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    fn(100 + i)
+                    b.record()
+                    torch.cuda.synchronize()
+                    ms += a.elapsed_time(b)
+                    ev += int((cs == 2).sum().item())
+                emit(what=name, N=N, d=d, M=M, need=need, nlive=len(w), ellipsoids=len(ells), round=rnd, path=be.last_path(),
+                     us_per_pair=ms / reps * 1e3, evals_per_launch=ev / reps, last_counts=[int(v) for v in counts.cpu().numpy()])
+    be.close()
+
+
+def _rosenbrock(theta):
+    t = np.atleast_2d(theta)
+    out = -((1.0 - t[:, 0]) ** 2 + 100.0 * (t[:, 1] - t[:, 0] ** 2) ** 2) / 100.0
+    return out if np.ndim(theta) == 2 else float(out[0])
+
+
+def mlf_end_to_end(ntrain=200, nlive=400, runs=3):
+    """run_ultranest (static, sample="mlfriends") beside run_pymultinest (sample="unif") on the surrogate of the 2-D Rosenbrock
+    likelihood on [-5, 5]^2, same model, same build, alternating, both stopped at dlogz = log1p(0.01)."""
+    import tempfile
+
+    from alabi_amd import SurrogateModel
+    sm = SurrogateModel(lnlike_fn=_rosenbrock, bounds=[(-5.0, 5.0)] * 2, savedir=tempfile.mkdtemp(), verbose=False, random_state=0,
+                        cache=False)
+    sm.init_samples(ntrain=ntrain)
+    sm.init_gp(hyperopt_method="ml", gp_nopt=1)
+    for run in range(runs + 1):                                   # run 0: warm-up
+        t0 = time.perf_counter()
+        sm.run_ultranest(sampler_kwargs={"seed": 1 + run}, run_kwargs={"min_num_live_points": nlive, "max_num_improvement_loops": 0},
+                         min_ess=0)
+        wall = time.perf_counter() - t0
+        r, s = sm.ultranest_results, sm.ultranest_sampler
+        if run:
+            emit(what="run_ultranest", config="rosenbrock", sample="mlfriends", N=ntrain, nlive=nlive, run=run, wall_s=wall,
+                 niter=int(r.niter), ncall=int(r.ncall), evals_launched=int(s.backend.evals_launched),
+                 evals_per_dead_point=r.ncall / r.niter, launched_per_dead_point=s.backend.evals_launched / r.niter,
+                 iterations=len(s.radius2), max_ellipsoids=int(max(s.n_ellipsoids)), logz=float(r.logz[-1]),
+                 logzerr=float(r.logzerr[-1]), status=r.status)
+        t0 = time.perf_counter()
+        sm.run_pymultinest(sampler_kwargs={"n_live_points": nlive, "seed": 1 + run, "evidence_tolerance": math.log1p(0.01)}, min_ess=0)
+        wall = time.perf_counter() - t0
+        r, s = sm.pymultinest_results, sm.pymultinest_sampler
+        if run:
+            emit(what="run_pymultinest", config="rosenbrock", sample="unif", N=ntrain, nlive=nlive, run=run, wall_s=wall,
+                 niter=int(r.niter), ncall=int(r.ncall), evals_launched=int(s.backend.evals_launched),
+                 evals_per_dead_point=r.ncall / r.niter, launched_per_dead_point=s.backend.evals_launched / r.niter,
+                 iterations=len(s.n_ellipsoids), max_ellipsoids=int(max(s.n_ellipsoids)), logz=float(r.logz[-1]),
+                 logzerr=float(r.logzerr[-1]), status=r.status)
+
+
 def _gauss(d, seed):
     rng = np.random.RandomState(seed)
     A = rng.randn(d, d)
@@ -413,6 +535,15 @@ if __name__ == "__main__":
         unif_kernels(200, 2)
         unif_end_to_end("tutorial", 2, 200, 100, (-4.0, 4.0))
         unif_end_to_end("C3", 10, 2000, 500, (-2.0, 2.0))
+        _SINK.close()
+    if what in ("--mlf", "mlf"):
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        _SINK = open(os.path.join(ROOT, "profiles", "nested_mlfriends.txt"), "w")
+        _SINK.write("# python tools/prof_nested.py --mlf : one JSON line per measurement (times: HIP events for the launches, wall "
+                    "clock for the runs)\n")
+        mlf_kernels(2000, 10)
+        mlf_kernels(200, 2)
+        mlf_end_to_end()
         _SINK.close()
     if what in ("--normal", "normal"):
         normal_prior()
