@@ -74,6 +74,8 @@ SIGNATURES = {
     "alabi_ens_set_moves": (_i, [_vp, _i, _pi, _pd, _pd, _pd]),
     "alabi_ens_set_stream": (_i, [_vp, _i]),
     "alabi_ens_last_path": (_i, [_vp, _pi]),
+    "alabi_ens_stream_variant": (_i, [_vp, _pi]),
+    "alabi_ens_pair_stats": (_i, [_vp, _pll, _i]),
     "alabi_ens_group_plan": (_i, [_vp, _pi]),
     "alabi_ens_lnprob": (_i, [_vp, _vp, _vp, _vp]),
     "alabi_ens_run": (_i, [_vp, _vp, _vp, _ll, _ll, _i, _d, _vp, _vp, _vp, _vp]),

@@ -623,6 +623,7 @@ int alabi_ens_destroy(alabi_ens* e) {
     if (e->part) (void)hipFree(e->part);
     if (e->cand) (void)hipFree(e->cand);
     if (e->err) (void)hipFree(e->err);
+    ens_pair_release(e);
     delete e;
     return ALABI_OK;
 }
@@ -691,6 +692,24 @@ int alabi_ens_set_stream(alabi_ens* e, int enabled) {
     if (enabled && !(e->hist && e->err)) return ALABI_BAD_ARGUMENT;
     e->stream_ok = enabled ? 1 : 0;
     e->settings_gen++;
+    return ALABI_OK;
+}
+
+int alabi_ens_stream_variant(alabi_ens* e, int* variant) {
+    if (!e || !variant) return ALABI_BAD_ARGUMENT;
+    *variant = (e->last_path == 1) ? e->last_variant : 0;
+    return ALABI_OK;
+}
+
+int alabi_ens_pair_stats(alabi_ens* e, long long* out, int reset) {
+    if (!e || !out) return ALABI_BAD_ARGUMENT;
+    if (!e->pair_stats) {                              // counting starts with the next run
+        ALABI_HIP_CHECK(hipMalloc(&e->pair_stats, 9 * sizeof(unsigned long long)));
+        ALABI_HIP_CHECK(hipMemset(e->pair_stats, 0, 9 * sizeof(unsigned long long)));
+    }
+    ALABI_HIP_CHECK(hipDeviceSynchronize());
+    ALABI_HIP_CHECK(hipMemcpy(out, e->pair_stats, 9 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (reset) ALABI_HIP_CHECK(hipMemset(e->pair_stats, 0, 9 * sizeof(unsigned long long)));
     return ALABI_OK;
 }
 
@@ -819,6 +838,17 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
         const int need = (int)(nsteps < e->chunk_cap ? nsteps : e->chunk_cap);   // rows 1..need are polled by this call
         const int clean_rows = e->hist_clean;
         e->hist_clean = 0;
+        // Two workgroups per list position (ens_pair_kernel) where 2 ceil(W/2) E of them fit one per CU.  That leaves no spare CU, so
+        // a time-out of the pair variant is retried below on ens_stream_kernel, from the walkers saved here, before it is reported.
+        const bool use_pair = !use_group && can_stream && ens_pair_ready(e);
+        e->last_variant = use_pair ? 1 : 0;
+        const size_t WTs = (size_t)e->W * e->E;
+        if (use_pair) {
+            double* sv = e->pair_save;
+            ALABI_HIP_CHECK(hipMemcpyAsync(sv, coords, WTs * e->d * sizeof(double), hipMemcpyDeviceToDevice, s));
+            ALABI_HIP_CHECK(hipMemcpyAsync(sv + WTs * e->d, logp, WTs * sizeof(double), hipMemcpyDeviceToDevice, s));
+            if (n_accept) ALABI_HIP_CHECK(hipMemcpyAsync(sv + WTs * (e->d + 1), n_accept, WTs * sizeof(long long), hipMemcpyDeviceToDevice, s));
+        }
         if (use_group && (st = set_run_state(e, step0, 0, s)) != ALABI_OK) return st;
         ALABI_HIP_CHECK(hipMemsetAsync(e->err, 0, sizeof(int), s));
         long long remaining = nsteps;
@@ -842,7 +872,9 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
                 else if ((st = launch_ens_draw_at(e, cur, K, a, false, step0 + done, s)) != ALABI_OK) return st;
                 ahead_issued = false;
                 if (ahead) ALABI_HIP_CHECK(hipEventRecord(e->ev_free, s));   // everything that read the other buffer set is behind this point
-                if ((st = launch_ens_stream_kernel(e, cur, coords, logp, K, done == 0, (done == 0 && clean_rows < need) ? need : 0, s)) != ALABI_OK)
+                const int fill_rows = (done == 0 && clean_rows < need) ? need : 0;
+                if ((st = use_pair ? launch_ens_pair_kernel(e, cur, coords, logp, K, done == 0, fill_rows, s)
+                                   : launch_ens_stream_kernel(e, cur, coords, logp, K, done == 0, fill_rows, s)) != ALABI_OK)
                     return st;
                 if (ahead) {
                     const long long rem2 = remaining - K;
@@ -862,6 +894,16 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
         ALABI_HIP_CHECK(hipMemcpyAsync(&flag, e->err, sizeof(int), hipMemcpyDeviceToHost, s));
         ALABI_HIP_CHECK(hipStreamSynchronize(s));
         e->hist_clean = (!use_group && !flag) ? (clean_rows > need ? clean_rows : need) : 0;
+        if (flag && use_pair) {
+            // restore the walkers, turn the pair variant off for this handle and run the call again on ens_stream_kernel (the history
+            // is marked dirty above, the flag is cleared at the start of the call); a second time-out is reported as before
+            const double* sv = e->pair_save;
+            ALABI_HIP_CHECK(hipMemcpyAsync(coords, sv, WTs * e->d * sizeof(double), hipMemcpyDeviceToDevice, s));
+            ALABI_HIP_CHECK(hipMemcpyAsync(logp, sv + WTs * e->d, WTs * sizeof(double), hipMemcpyDeviceToDevice, s));
+            if (n_accept) ALABI_HIP_CHECK(hipMemcpyAsync(n_accept, sv + WTs * (e->d + 1), WTs * sizeof(long long), hipMemcpyDeviceToDevice, s));
+            e->pair_state = -1;
+            return alabi_ens_run(e, coords, logp, step0, nsteps, thin_by, a, chain, chain_logp, n_accept, stream);
+        }
         return flag ? ALABI_TIMEOUT : ALABI_OK;
     }
     if ((st = set_run_state(e, step0, 0, s)) != ALABI_OK) return st;

@@ -184,6 +184,12 @@ struct alabi_ens {
     int stream_grid = 0;                 // workgroups per ensemble of the persistent kernel
     int last_path = 0;                   // 1 persistent kernel (ens_stream_kernel), 3 group kernel (ens_group_kernel), 0 one launch per half step
     int stream_ok = 0;                   // eligible: training set fits the lanes' registers, one workgroup per CU
+    // pair variant of the persistent kernel (ens_pair_kernel)
+    unsigned long long* prop = nullptr;  // [(chunk_cap+1)][E*W][d+2] published proposals, allocated on first use
+    double* pair_save = nullptr;         // (coords, logp, n_accept) at the start of a pair call: a time-out is retried on ens_stream_kernel
+    unsigned long long* pair_stats = nullptr;   // [9] debug counters (alabi_ens_pair_stats), allocated on request
+    int pair_state = 0;                  // 0 undecided, 1 ready, -1 off (not eligible, ALABI_ENS_PAIR=0, or after a time-out of this handle)
+    int last_variant = 0;                // persistent kernel of the last stream call: 0 ens_stream_kernel, 1 ens_pair_kernel
     // group kernel (ens_group_kernel: training set partitioned over the members of a group, proposals streamed through)
     unsigned long long* part = nullptr;  // [2 chunk_cap][E][NG][G][16 Q] partial kernel sums (allocated on first use)
     size_t part_words = 0;
@@ -303,6 +309,13 @@ int alabi_ens_half_step_hist(alabi_ens* e, const double* coords, const double* l
                              const double* shist, double* out, hipStream_t s);
 bool ens_stream_fits(const alabi_ens* e);
 int launch_ens_stream_kernel(alabi_ens* e, const DrawBuffers& rec, double* coords, double* logp, int K, bool first, int fill_rows, hipStream_t s);
+int ens_stream_ppt_of(const alabi_ens* e);       // point pairs per compute lane of the persistent kernels (0: does not fit)
+int launch_ens_hist_fill(unsigned long long* rows, size_t words, hipStream_t s);
+int launch_ens_stream_prologue(alabi_ens* e, double* coords, double* logp, bool first, int fill_rows, hipStream_t s);
+// ens_pair.hip: the pair variant of the persistent kernel (two workgroups per list position, both outcomes of a pending update)
+bool ens_pair_ready(alabi_ens* e);
+void ens_pair_release(alabi_ens* e);
+int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, double* coords, double* logp, int K, bool first, int fill_rows, hipStream_t s);
 int launch_ens_stream_epilogue(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
                                long long* n_accept, long long step_next, long long done0, hipStream_t s);
 // ens_group.hip

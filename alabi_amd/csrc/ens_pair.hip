@@ -1,0 +1,485 @@
+// Persistent ensemble kernel, pair variant: both outcomes of a pending update on two CUs.
+//
+// ens_stream_kernel (ensemble.hip) runs one workgroup per list position on half of the CUs, and a half step is a hand-off hop
+// followed by a kernel sum, one after the other.  A proposal of half step h + 1 does not need the verdict of the half step-h
+// update it reads, only the state of that walker, and that state is one of two rows which are both known early: the walker's
+// previous row (in the history) and the proposal of half step h (known on its CU a whole kernel sum before its verdict).  Here
+// every list position has a PAIR of workgroups, 2b ("R") and 2b + 1 ("A"), and every proposal is published when it is known
+// to be the real one (`prop`, the same row layout and sentinel as `hist`).  For an input row produced in the immediately
+// preceding half step ("fresh") R assumes that update was rejected and reads the previous version's row, A assumes it was
+// accepted and reads the published proposal; both evaluate while the verdict is computed and travels, both poll the verdict
+// (the acceptance flag of the fresh row; A with a fresh own row takes the old log-probability from the same row), and the one
+// that assumed right does the accept test and the row store exactly as ens_stream_kernel does.  The other drops its sum.
+//
+// Freshness follows from the draws alone (class = number of fresh input rows):
+//   second half of a step   the partner row (version t + 1) is fresh, the own row is not                       -> class 1
+//   first half, t >= 1      a row is fresh iff its walker was in the second list of step t - 1 (pos_of >= n0)   -> class 0, 1, 2
+//   step 0 of a launch      row 0 is complete before the launch                                               -> class 0
+// class 0: R evaluates as ens_stream_kernel does, A skips the item.   class 1: as above.   class 2: no speculation (two of
+// four outcomes would buy nothing): R polls both rows as ens_stream_kernel does, A skips.
+// Exactly one workgroup of a pair writes prop and the history row of an item: R at formation for classes 0 and 2, the
+// workgroup whose assumption held on the verdict's arrival for class 1 -- always, for an out-of-bounds proposal too, so that
+// no reader waits for it.  Every dependency points to an earlier half step, so the oldest unfinished item can always run
+// while all 2 G E workgroups are resident (the host launches at most one per CU).
+// Arithmetic, lane -> point map, accumulation order, accept expression and row layout are those of ens_stream_kernel: the
+// surviving sum is that kernel's sum, so the chains agree bit for bit.
+#include <cstdlib>
+#include "ens_stream.hpp"
+
+namespace alabi {
+
+struct PairArgs {
+    StreamArgs s;
+    unsigned long long* prop;    // [(K+1)][E*W][d+2] published proposals (words [0, d) of a row are read); rows 1..K pre-filled with ALABI_HIST_EMPTY
+    unsigned long long* stats;   // nullptr, or [3 classes][3]: items, rows stored by R, rows stored by A (debug; accumulated outside the chain)
+};
+
+#ifdef ALABI_PAIR_PROF
+// hand-off wave of pair 3, [0..7] R, [8..15] A: [0] input poll, [1] rows detected -> barrier A, [2] A -> B (the verdict poll included),
+// [3] B -> row store issued, [4] items, [5] ticks of the launch, [6] verdict-poll ticks of the class-1 items, [7] class-1 items;
+// [16..19] R, [20..23] A: publish -> detect ticks of the prop rows read and their number, row store -> verdict detected and their number
+// (the publisher leaves its clock in g_pair_pub, by row index modulo its size: [0] at the prop store, [1] at the row store)
+__device__ long long g_pair_prof[24];
+#define ALABI_PAIR_PUB_MASK ((1 << 19) - 1)
+__device__ long long g_pair_pub[2][ALABI_PAIR_PUB_MASK + 1];
+__device__ inline void pair_pub_stamp(int which, size_t row_index) {
+    __hip_atomic_store(&g_pair_pub[which][row_index & ALABI_PAIR_PUB_MASK], wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ inline long long pair_pub_age(int which, size_t row_index, long long now) {
+    const long long dt = now - __hip_atomic_load(&g_pair_pub[which][row_index & ALABI_PAIR_PUB_MASK], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return (dt > 0 && dt < 100000) ? dt : -1;     // (a stamp of another launch, or one not yet visible: not counted)
+}
+#endif
+
+// blockDim.x = TMAX = 64 + compute threads + 64; roles, barriers and the compute waves' code as in ens_stream_kernel.
+template <int D, int PPT, int TMAX, bool GENERIC>
+__global__ void __launch_bounds__(TMAX)
+ens_pair_kernel(PairArgs pa) {
+    const StreamArgs& p = pa.s;
+    __shared__ __attribute__((aligned(16))) double scratch[2][16];   // wave partials, by proposal parity
+    __shared__ unsigned long long rec_s[4][6];                       // proposal-record ring: the packed record, own row fresh, partner row fresh
+    __shared__ __attribute__((aligned(16))) double qs_s[2][ALABI_MAX_DIM];   // scaled proposal [0, D) and its in-bounds flag [D], by proposal parity
+    __shared__ double consts_s[6][ALABI_MAX_DIM];
+    __shared__ int abort_s;
+    static_assert(D < ALABI_MAX_DIM && TMAX >= 192 && TMAX % 64 == 0, "ens_pair_kernel: shape");
+    constexpr int TC = TMAX - 128, nwc = TC >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool comm = wv == 0, service = wv == nwc + 1, compute = !comm && !service;
+    const int b = blockIdx.x >> 1, e = blockIdx.y, E = gridDim.y;
+    const int role_a = blockIdx.x & 1;                               // 1: this workgroup assumes "accepted"
+    const int WT = p.W * E, row = p.d + 2;
+#ifdef ALABI_PAIR_PROF
+    long long prof[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const long long prof_begin = wall_clock64();
+#endif
+    // training-set share of this lane, resident for the whole launch (same lane -> point map as ens_half_kernel)
+    const int half = p.Npad >> 1, ct = tid - 64;
+    f64x2 xa[PPT][D], aa[PPT];
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+        const int idx = ct + j * TC;
+        const bool v = compute && idx < half;
+#pragma unroll
+        for (int k = 0; k < D; ++k)
+            xa[j][k] = v ? reinterpret_cast<const f64x2*>(p.Xt + (size_t)k * p.Npad)[idx] : f64x2{0.0, 0.0};
+        aa[j] = v ? reinterpret_cast<const f64x2*>(p.alpha)[idx] : (GENERIC ? f64x2{0.0, 0.0} : f64x2{ALABI_SE_PAD, ALABI_SE_PAD});
+    }
+    if (tid < ALABI_MAX_DIM) {
+        consts_s[0][tid] = (tid < p.d) ? p.consts[tid] : 0.0;
+        consts_s[1][tid] = (tid < p.d) ? p.consts[ALABI_MAX_DIM + tid] : 0.0;
+        consts_s[2][tid] = (tid < p.d) ? p.consts[2 * ALABI_MAX_DIM + tid] : 0.0;
+        consts_s[3][tid] = (tid < p.d) ? p.consts[3 * ALABI_MAX_DIM + tid] : 0.0;
+        consts_s[4][tid] = (tid < p.d) ? p.consts[4 * ALABI_MAX_DIM + tid] : 0.0;
+        consts_s[5][tid] = (!GENERIC && tid < p.d) ? p.centre[tid] : 0.0;
+    }
+    if (tid < 32) scratch[tid >> 4][tid & 15] = 0.0;
+    if (tid == 0) abort_s = 0;
+
+    // The pair's proposals: list position b of every half step that has one (G = n0 pairs per ensemble, so at most one item
+    // per half step), in (step, split) order.
+    const int G = gridDim.x >> 1;
+    auto next_item = [&](int& t, int& split, int& bb) {
+        bb += G;
+        for (;;) {
+            if (t >= p.K) return;
+            if (bb < (split ? p.W - p.n0 : p.n0)) return;
+            bb = b;
+            if (split == 0) split = 1; else { split = 0; ++t; }
+        }
+    };
+    // Record wave: the packed record is fetched four items ahead (lane l < 4 loads word l); one item later, when its walker ids
+    // are in registers, lanes 4 and 5 fetch the list positions of the two walkers in step t - 1, which say whether the rows
+    // the proposal reads are fresh.  Both are in the ring two items before the hand-off wave decodes them.
+    const unsigned long long* packed = p.rec.packed;
+    const int* pos_of = p.rec.pos_of;
+    auto record_load = [&](int t, int split, int bb) -> unsigned long long {
+        if (t >= p.K || lane >= 4) return 0ull;
+        const size_t pos = ((size_t)t * E + e) * p.W + (split ? p.n0 : 0) + bb;
+        return packed[4 * pos + lane];
+    };
+    // lane 4: the own row is fresh, lane 5: the partner row is fresh (`rec`: the item's packed record, walker ids in lane 0)
+    auto fresh_load = [&](int t, int split, unsigned long long rec) -> unsigned long long {
+        const int w = __builtin_amdgcn_readlane((int)(unsigned)(rec & 0xffffffffull), 0);
+        const int cw = __builtin_amdgcn_readlane((int)(unsigned)(rec >> 32), 0);
+        if (t >= p.K || (lane != 4 && lane != 5)) return 0ull;
+        if (split) return lane == 5 ? 1ull : 0ull;
+        if (t == 0) return 0ull;
+        return pos_of[(size_t)(t - 1) * WT + (lane == 4 ? w : cw)] >= p.n0 ? 1ull : 0ull;
+    };
+    unsigned long long rec_a = 0, fresh_a = 0, rec_b = 0;   // record and freshness of item + 2, record of item + 3
+    int bt = 0, bsplit = 0;                                 // (step, split) of rec_b's item
+    int pt = 0, psplit = 0, pbb = b, pslot = 0;             // the item the next record load is for
+    if (service) {                                    // prologue: items 0 and 1 into the ring, item 2 in registers, item 3 in flight
+        for (int i = 0; i < 2; ++i) {
+            const unsigned long long r = record_load(pt, psplit, pbb);
+            const unsigned long long f = fresh_load(pt, psplit, r);
+            if (lane < 6) rec_s[pslot & 3][lane] = lane < 4 ? r : f;
+            next_item(pt, psplit, pbb); ++pslot;
+        }
+        rec_a = record_load(pt, psplit, pbb);
+        fresh_a = fresh_load(pt, psplit, rec_a);
+        next_item(pt, psplit, pbb);
+        bt = pt; bsplit = psplit;
+        rec_b = record_load(pt, psplit, pbb);
+        next_item(pt, psplit, pbb);
+    }
+    __syncthreads();
+    int t = 0, split = 0, bb = b, item = 0;           // b < G = n0: the first item is valid
+
+    if (comm) {
+        // ---- hand-off wave: poll -> proposal -> LDS -> A -> (prior term, next decode, VERDICT poll, candidate rows) -> B -> accept -> store
+        const int n0_lane = lane < p.d ? lane : p.d, n1_lane = lane < p.d ? lane : p.d - 1;
+        const int out_lane = lane <= p.d ? lane : p.d + 1, ver_lane = lane == p.d ? p.d : p.d + 1;
+        const long long prop_off = (long long)(pa.prop - p.hist);   // one base pointer: every address stays a global one
+        // the next item, decoded ahead
+        int n_mode = 0, n_own_a = 0;                  // mode 0 evaluate (the winner is known), 1 speculate, 2 skip; A reads a fresh own row
+        double n_zz = 0.0;
+        size_t n_out = 0;                             // this lane's word of the new row (in hist, and in prop)
+#ifdef ALABI_PAIR_PROF
+        size_t n_fidx = 0;                            // row index of the fresh input row
+#endif
+        int n_cls = 0;                                // class of the item, in a vector register (read by the debug counters only)
+        const unsigned long long *n_hw = p.hist, *n_hc = p.hist, *n_ver = p.hist;
+        auto decode_next = [&](int it, int tt, int sp) {
+            const unsigned long long* rs = rec_s[it & 3];
+            const unsigned long long ids = rs[0];
+            const int w = (int)(unsigned)(ids & 0xffffffffull);
+            const int cw = (int)(unsigned)(ids >> 32);
+            n_zz = __longlong_as_double((long long)rs[1]);
+            n_cls = (int)rs[4] + (int)rs[5];
+            const int fo = __builtin_amdgcn_readfirstlane((int)rs[4]), fp = __builtin_amdgcn_readfirstlane((int)rs[5]);
+            const int spec = (fo + fp) == 1;
+            n_mode = spec ? 1 : role_a ? 2 : 0;
+            n_own_a = spec & role_a & fo;
+            // own row at version t, partner row at version t (+1 when the partner's half went first).  R, class 1: the previous
+            // version of the fresh row.  A, class 1: the fresh row from prop (words [0, d) only).  A, skipped item: row 0 (complete).
+            const int vo = tt, vp = tt + sp;
+            const int rv_o = vo - (spec & !role_a & fo), rv_p = vp - (spec & !role_a & fp);
+            const size_t row_o = ((size_t)rv_o * WT + w) * row, row_p = ((size_t)rv_p * WT + cw) * row;
+            const bool prop_o = spec && role_a && fo, prop_p = spec && role_a && fp;
+            n_hw = p.hist + (row_o + (prop_o ? n1_lane : n0_lane)) + (prop_o ? prop_off : 0ll);
+            n_hc = p.hist + (row_p + n1_lane) + (prop_p ? prop_off : 0ll);
+            if (n_mode == 2) { n_hw = p.hist + n0_lane; n_hc = p.hist + n1_lane; }
+            n_ver = p.hist + ((size_t)(fo ? vo : vp) * WT + (fo ? w : cw)) * row + ver_lane;
+            n_out = ((size_t)(tt + 1) * WT + w) * row + out_lane;
+#ifdef ALABI_PAIR_PROF
+            n_fidx = (size_t)(fo ? vo : vp) * WT + (fo ? w : cw);
+#endif
+        };
+        const double il_r = consts_s[0][lane], lo_r = consts_s[1][lane], hi_r = consts_s[2][lane], c_r = consts_s[5][lane];
+        const bool needc = lane < p.d;
+        const unsigned long long coord_lanes = (1ull << p.d) - 1;
+        int st_items = 0, st_rows = 0;                // debug counters: lane c counts the items of class c
+        decode_next(0, 0, 0);
+        while (t < p.K) {
+            const int par = item & 1;
+#ifdef ALABI_PAIR_PROF
+            const long long c0 = wall_clock64();
+#endif
+            unsigned long long ws, wc;
+            int spins = 0;
+            bool pending;
+            for (;;) {
+                ws = ld_sc1(n_hw);
+                wc = ld_sc1(n_hc);
+                pending = __builtin_amdgcn_ballot_w64(ws == ALABI_HIST_EMPTY || wc == ALABI_HIST_EMPTY) != 0;
+                if (!pending) break;
+                if (__builtin_expect(++spins > p.spin_limit || ((spins & 63) == 0 && __builtin_amdgcn_readfirstlane(
+                        __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0), 0)) break;
+            }
+            // Bounded spin ran out: as in ens_stream_kernel the cold block rejoins the fast path -- a NaN stretch factor puts
+            // the proposal out of bounds, this is the last proposal, nothing of it is stored or published.
+            if (__builtin_expect(pending, 0)) {
+                n_zz = __builtin_nan("");
+                abort_s = 1;
+                __hip_atomic_store(p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+#ifdef ALABI_PAIR_PROF
+            const long long c1 = wall_clock64();
+            const size_t fidx = n_fidx;
+            if (n_mode == 1 && role_a && !pending) { const long long dt = pair_pub_age(0, fidx, c1); if (dt > 0) { prof[7] += dt; prof[8] += 1; } }
+#endif
+            const int mode = n_mode, own_a = n_own_a, cls = n_cls;
+            const size_t out_word = n_out;
+            const unsigned long long* ver = n_ver;
+            const double sv = __longlong_as_double((long long)ws), cv = __longlong_as_double((long long)wc);
+            const double qv = cv - (cv - sv) * n_zz;
+            const bool all_in = mode != 2 && (__builtin_amdgcn_ballot_w64(qv > lo_r) & __builtin_amdgcn_ballot_w64(qv < hi_r) & coord_lanes)
+                                                 == coord_lanes;
+            double qs = qv * il_r;
+            if (!GENERIC) qs -= c_r;
+            qs_s[par][lane] = needc ? qs : 0.0;
+            reinterpret_cast<int*>(&qs_s[par][D])[1] = all_in ? 0x3ff00000 : 0;
+            // classes 0 and 2: this workgroup (R) holds the real proposal -- published at formation (the lanes behind the
+            // coordinates write words d and d + 1 of the prop row, which nobody reads)
+#ifdef ALABI_PAIR_PROF
+            if (mode == 0 && !pending) pair_pub_stamp(0, out_word / row);
+#endif
+            if (mode == 0 && !pending) st_sc1(p.hist + (out_word + prop_off), (unsigned long long)__double_as_longlong(qv));
+            __syncthreads();                          // barrier A: the proposal is in LDS
+            __builtin_amdgcn_sched_barrier(0);
+#ifdef ALABI_PAIR_PROF
+            const long long c2 = wall_clock64();
+#endif
+            int t2 = t, s2 = split, b2 = bb;
+            next_item(t2, s2, b2);
+            if (pending) t2 = p.K;
+            double prior_q = 0.0;
+            if (p.has_prior) {
+                const double u = (qv - consts_s[3][lane]) * consts_s[4][lane];
+                prior_q = lane_bcast(wave_sum_dpp(needc ? -0.5 * u * u : 0.0), 63) + p.prior_const;
+            }
+            double lnfac = __longlong_as_double((long long)rec_s[item & 3][2]);
+            double lnu = __longlong_as_double((long long)rec_s[item & 3][3]);
+            double lp_old = lane_bcast(sv, p.d);      // lane d loaded logp (not so for A with a fresh own row: see below)
+            int part = par * (int)sizeof(scratch[0]);
+            if (t2 < p.K) decode_next(item + 1, t2, s2);
+            // The verdict of the fresh row: its acceptance flag (every lane but lane d) and its log-probability (lane d).  Polled
+            // here, in the window in which this wave is idle; the workgroup whose assumption holds publishes its proposal at once.
+            int win = mode == 0;
+#ifdef ALABI_PAIR_PROF
+            const long long c2v = wall_clock64();
+#endif
+            if (mode == 1 && !pending) {
+                unsigned long long vw;
+                bool vpend;
+                int vspins = 0;
+                for (;;) {
+                    vw = ld_sc1(ver);
+                    vpend = __builtin_amdgcn_ballot_w64(vw == ALABI_HIST_EMPTY) != 0;
+                    if (!vpend) break;
+                    if (__builtin_expect(++vspins > p.spin_limit || ((vspins & 63) == 0 && __builtin_amdgcn_readfirstlane(
+                            __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0), 0)) break;
+                }
+                if (__builtin_expect(vpend, 0)) {     // time-out: the last proposal, nothing stored
+                    abort_s = 1;
+                    __hip_atomic_store(p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    t2 = p.K;
+                }
+                const int flag = __builtin_amdgcn_readfirstlane((int)(unsigned)(vw & 0xffffffffull));   // lane 0 polls the flag word (d >= 1)
+                win = !vpend && flag == role_a;
+#ifdef ALABI_PAIR_PROF
+                if (win) pair_pub_stamp(0, out_word / row);
+#endif
+                if (win) st_sc1(p.hist + (out_word + prop_off), (unsigned long long)__double_as_longlong(qv));
+                if (own_a) lp_old = lane_bcast(__longlong_as_double((long long)vw), p.d);
+            }
+#ifdef ALABI_PAIR_PROF
+            const long long c2w = wall_clock64();
+            if (mode == 1 && !pending) { const long long dt = pair_pub_age(1, fidx, c2w); if (dt > 0) { prof[9] += dt; prof[10] += 1; } }
+#endif
+            // the new row as it is written if the proposal is rejected / accepted (ens_stream_kernel's w_rej, w_acc)
+            unsigned long long w_rej = needc ? ws : lane == p.d ? (unsigned long long)__double_as_longlong(lp_old) : 0ull;
+            unsigned long long w_acc = !all_in ? w_rej : needc ? (unsigned long long)__double_as_longlong(qv) : 1ull;
+            const bool takes_lp = all_in && lane == p.d;
+            if (pending) win = 0;
+            // debug counters, in registers; R sees every item
+            if (pa.stats) { st_items += (cls == lane); st_rows += (cls == lane && win); }
+            size_t ow = out_word;
+            asm volatile("" : "+v"(ow), "+v"(w_rej), "+v"(w_acc), "+v"(lp_old), "+v"(lnfac), "+v"(lnu), "+v"(prior_q), "+v"(part));
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();                          // barrier B: the wave partials are in LDS
+#ifdef ALABI_PAIR_PROF
+            const long long c3 = wall_clock64();
+#endif
+            const double* partials = reinterpret_cast<const double*>(reinterpret_cast<const char*>(&scratch[0][0]) + part);
+            const double lp_new = fma(p.amp, wave_partials_tree<nwc>(partials), p.mean) + prior_q;
+            const bool acc = lnfac + lp_new - lp_old > lnu;
+            if (takes_lp) w_acc = (unsigned long long)__double_as_longlong(lp_new);
+#ifdef ALABI_PAIR_PROF
+            if (win) pair_pub_stamp(1, ow / row);
+#endif
+            if (win) st_sc1(p.hist + ow, acc ? w_acc : w_rej);
+            t = t2; split = s2; bb = b2; ++item;
+#ifdef ALABI_PAIR_PROF
+            { const long long c4 = wall_clock64();
+              prof[0] += c1 - c0; prof[1] += c2 - c1; prof[2] += c3 - c2; prof[3] += c4 - c3; prof[4] += 1;
+              if (mode == 1) { prof[5] += c2w - c2v; prof[6] += 1; } }
+#endif
+        }
+        if (pa.stats && lane < 3) {
+            if (!role_a) atomicAdd(pa.stats + 3 * lane, (unsigned long long)st_items);
+            atomicAdd(pa.stats + 3 * lane + 1 + role_a, (unsigned long long)st_rows);
+        }
+#ifdef ALABI_PAIR_PROF
+        if (tid == 0 && b == 3 && blockIdx.y == 0) {
+            long long* g = g_pair_prof + 8 * role_a;
+            for (int i = 0; i < 5; ++i) g[i] = prof[i];
+            g[5] = wall_clock64() - prof_begin;
+            g[6] = prof[5]; g[7] = prof[6];
+            for (int i = 0; i < 4; ++i) g_pair_prof[16 + 4 * role_a + i] = prof[7 + i];
+        }
+#endif
+    } else if (compute) {
+        // ---- compute waves: A -> q -> sum -> DPP -> partial -> B (ens_stream_kernel's code)
+        while (t < p.K) {
+            next_item(t, split, bb);
+            const int par = item & 1;
+            __syncthreads();                          // barrier A
+            double q[D];
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                const double r = qs_s[par][k];
+                q[k] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(r)),
+                                        __builtin_amdgcn_readfirstlane(__double2loint(r)));
+            }
+            const int inb = __builtin_amdgcn_readfirstlane(__double2hiint(qs_s[par][D]));
+            __builtin_amdgcn_sched_group_barrier(0x100, D + 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x2, 2 * D + 1, 0);
+            if (inb != 0) {
+                double acc = 0.0;
+                if (!GENERIC) {
+                    const double nhq = se_neg_half_norm<D>(q);
+#pragma unroll
+                    for (int j = 0; j < PPT; ++j) {
+                        double fa, fb;
+                        se_pair_terms<D>(xa[j], aa[j], q, nhq, fa, fb);
+                        acc += fa; acc += fb;
+                        if ((j & 1) == 1) __builtin_amdgcn_sched_barrier(0);
+                    }
+                } else
+#pragma unroll
+                for (int j = 0; j < PPT; ++j) {
+                    double r2a = 0.0, r2b = 0.0;
+#pragma unroll
+                    for (int k = 0; k < D; ++k) {
+                        const double da = xa[j][k].x - q[k], db = xa[j][k].y - q[k];
+                        r2a = fma(da, da, r2a);
+                        r2b = fma(db, db, r2b);
+                    }
+                    acc = (j == 0) ? aa[j].x * radial<GENERIC>(r2a, p.kf) : fma(aa[j].x, radial<GENERIC>(r2a, p.kf), acc);
+                    acc = fma(aa[j].y, radial<GENERIC>(r2b, p.kf), acc);
+                    if ((j & 1) == 1) __builtin_amdgcn_sched_barrier(0);
+                }
+                const double wsum = wave_sum_dpp(acc);
+                if (lane == 63) scratch[par][wv - 1] = wsum;
+            }
+            __syncthreads();                          // barrier B
+            if (abort_s) return;
+            ++item;
+        }
+    } else {
+        // ---- record wave: ring slot item + 2 <- (record, freshness) in registers; freshness of item + 3; record of item + 4
+        while (t < p.K) {
+            next_item(t, split, bb);
+            __syncthreads();                          // barrier A
+            if (lane < 6) rec_s[pslot & 3][lane] = lane < 4 ? rec_a : fresh_a;
+            ++pslot;
+            rec_a = rec_b;
+            fresh_a = fresh_load(bt, bsplit, rec_a);
+            bt = pt; bsplit = psplit;
+            rec_b = record_load(pt, psplit, pbb);
+            next_item(pt, psplit, pbb);
+            __syncthreads();                          // barrier B
+            if (abort_s) return;
+        }
+    }
+}
+
+#ifdef ALABI_PAIR_PROF
+extern "C" int alabi_debug_pair_prof(long long* out) {
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pair_prof), sizeof(long long) * 24);
+}
+#endif
+
+#define ALABI_PAIR_DISPATCH_DIM(DB, ...)                              \
+    switch (DB) {                                                     \
+        case 1: { constexpr int D = 1; __VA_ARGS__; } break;          \
+        case 2: { constexpr int D = 2; __VA_ARGS__; } break;          \
+        case 3: { constexpr int D = 3; __VA_ARGS__; } break;          \
+        case 4: { constexpr int D = 4; __VA_ARGS__; } break;          \
+        case 5: { constexpr int D = 5; __VA_ARGS__; } break;          \
+        case 6: { constexpr int D = 6; __VA_ARGS__; } break;          \
+        case 8: { constexpr int D = 8; __VA_ARGS__; } break;          \
+        case 10: { constexpr int D = 10; __VA_ARGS__; } break;        \
+        case 12: { constexpr int D = 12; __VA_ARGS__; } break;        \
+        case 16: { constexpr int D = 16; __VA_ARGS__; } break;        \
+        default: return ALABI_BAD_ARGUMENT;                           \
+    }
+#define ALABI_PAIR_LAUNCH(PPT_, TMAX_)                                                                            \
+    ALABI_PAIR_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type,                                                \
+        hipLaunchKernelGGL((ens_pair_kernel<D, PPT_, TMAX_, GENERIC>), dim3(2 * n0, e->E), dim3(TMAX_), 0, s, a)))
+
+// The pair variant can run this handle: prop allocated (lazily, here), one workgroup per CU for 2 ceil(W/2) E workgroups, not
+// switched off by ALABI_ENS_PAIR=0 or by an earlier time-out of this handle.  The caller has checked ens_stream_fits and the moves.
+bool ens_pair_ready(alabi_ens* e) {
+    if (e->pair_state < 0) return false;
+    if (e->pair_state == 0) {
+        e->pair_state = -1;
+        const char* env = getenv("ALABI_ENS_PAIR");
+        if (env && env[0] == '0') return false;
+        int dev = 0, n_cu = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
+        const long long wgs = 2LL * ((e->W + 1) / 2) * e->E;
+        if (e->d < 1 || wgs > n_cu) return false;
+        const size_t WT = (size_t)e->W * e->E, row = e->d + 2;
+        const size_t words = ((size_t)e->chunk_cap + 1) * WT * row;
+        if (hipMalloc(&e->prop, words * sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); e->prop = nullptr; return false; }
+        if (hipMalloc(&e->pair_save, (WT * (e->d + 1)) * sizeof(double) + WT * sizeof(long long)) != hipSuccess) {
+            (void)hipGetLastError(); (void)hipFree(e->prop); e->prop = nullptr; e->pair_save = nullptr; return false;
+        }
+        e->pair_state = 1;
+    }
+    return true;
+}
+
+void ens_pair_release(alabi_ens* e) {
+    if (e->prop) (void)hipFree(e->prop);
+    if (e->pair_save) (void)hipFree(e->pair_save);
+    if (e->pair_stats) (void)hipFree(e->pair_stats);
+    e->prop = nullptr; e->pair_save = nullptr; e->pair_stats = nullptr;
+}
+
+// One chunk of K steps on the pair kernel; the arguments of launch_ens_stream_kernel.  Rows 1..K of prop are refilled with the
+// sentinel in front of every chunk (the epilogue restores the sentinel in hist only).
+int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, double* coords, double* logp, int K, bool first, int fill_rows,
+                           hipStream_t s) {
+    alabi_gp* gp = e->gp;
+    const int n0 = (e->W + 1) / 2;
+    const int WT = e->W * e->E, row = e->d + 2;
+    int st = launch_ens_stream_prologue(e, coords, logp, first, fill_rows, s);
+    if (st != ALABI_OK) return st;
+    if ((st = launch_ens_hist_fill(e->prop + (size_t)WT * row, (size_t)K * WT * row, s)) != ALABI_OK) return st;
+    PairArgs a{};
+    a.s = ens_stream_args(e, rec, K);
+    a.prop = e->prop; a.stats = e->pair_stats;
+    const int db = dim_bucket(e->d);
+    const int T = e->threads, ppt = ens_stream_ppt_of(e);
+    e->last_path = 1;
+    if (T == 256) {
+        if (ppt == 1) { ALABI_PAIR_LAUNCH(1, 384); }
+        else if (ppt == 2) { ALABI_PAIR_LAUNCH(2, 384); }
+        else if (ppt == 3) { ALABI_PAIR_LAUNCH(3, 384); }
+        else if (ppt == 4) { ALABI_PAIR_LAUNCH(4, 384); }
+        else return ALABI_BAD_ARGUMENT;
+    } else if (T == 512) {
+        if (ppt == 1) { ALABI_PAIR_LAUNCH(1, 640); }
+        else if (ppt == 2) { ALABI_PAIR_LAUNCH(2, 640); }
+        else return ALABI_BAD_ARGUMENT;
+    } else return ALABI_BAD_ARGUMENT;
+    ALABI_LAUNCH_CHECK();
+    return ALABI_OK;
+}
+
+}  // namespace alabi

@@ -37,7 +37,7 @@
 // 2000 kernel evaluations: latency bound, not HBM bound (X and alpha, 176 KB, stay in L2).
 #include <cstdlib>
 #include <vector>
-#include "ens_device.hpp"
+#include "ens_stream.hpp"
 
 namespace alabi {
 
@@ -714,45 +714,9 @@ __global__ void ens_advance_kernel(long long* run_state, long long n) {
 // Correctness never depends on placement or timing; every spin is bounded
 // (a timeout sets *err and every workgroup leaves, the host then falls back to the launch-per-half-step path).
 // All workgroups must be co-resident: the host launches at most one per CU.
-#define ALABI_HIST_EMPTY 0x7FF8A1AB1D15EA5Eull   // quiet NaN with a payload no computation produces
-
-struct StreamArgs {
-    unsigned long long* hist;    // [(K+1)][E*W][d+1] as raw 64-bit words; rows 1..K pre-filled with ALABI_HIST_EMPTY
-    int* err;                    // [1], zeroed before the launch
-    DrawBuffers rec;             // chunk base
-    const double* consts;
-    const double* Xt;            // squared exponential: gp->Xc (inputs relative to their mean) ...
-    const double* alpha;         // ... and gp->ens_h (se_pair_terms)
-    const double* centre;        // mean of the scaled training inputs (squared exponential)
-    int K, W, n0, d, Npad, spin_limit, has_prior;
-    double amp, mean, prior_const;
-    KernelFn kf;
-};
-
-__device__ inline unsigned long long ld_sc1(const unsigned long long* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ inline void st_sc1(unsigned long long* p, unsigned long long v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 #ifdef ALABI_STREAM_PROF
 __device__ long long g_stream_prof[16];
 #endif
-
-// Sum of the wave partials s[0..15] (zeros beyond the last compute wave) in exactly the order wave_sum_dpp adds
-// lanes 0..15 of a row -- a balanced binary tree -- so this path and ens_half_kernel agree bit for bit.  Only the pairs that
-// hold a partial are read; a pair beyond them is the +0.0 it holds, and the additions of such zeros that reach a live
-// value stay in the code: x + 0.0 is +0.0 for x = -0.0, so they are not the identity.
-template <int NW>
-__device__ inline double wave_partials_tree(const double* s) {
-    const f64x2* v = reinterpret_cast<const f64x2*>(s);
-    auto pair = [&](int i) { return 2 * i < NW ? v[i].y + v[i].x : 0.0; };
-    const double lo8 = (pair(3) + pair(2)) + (pair(1) + pair(0));
-    if (NW <= 8) return lo8;
-    const double hi8 = (pair(7) + pair(6)) + (pair(5) + pair(4));
-    return hi8 + lo8;
-}
 
 // blockDim.x = TMAX = 64 + compute threads (a multiple of 64) + 64.  Three roles, ONE LOOP EACH over the workgroup's proposals;
 // the loops meet only at the two barriers of a proposal (A: the proposal is in LDS, B: the wave partials are in LDS), so no role
@@ -1208,24 +1172,45 @@ int launch_ens_hist_epilogue(alabi_ens* e, double* coords, double* logp, int K, 
     return ALABI_OK;
 }
 
+int ens_stream_ppt_of(const alabi_ens* e) { return ens_stream_ppt(e); }
+
+int launch_ens_hist_fill(unsigned long long* rows, size_t words, hipStream_t s) {
+    hipLaunchKernelGGL(ens_hist_fill_kernel, dim3(1024), dim3(256), 0, s, rows, words);
+    ALABI_LAUNCH_CHECK();
+    return ALABI_OK;
+}
+
+// What stands in front of a persistent launch (ens_stream_kernel, ens_pair_kernel): the sentinel in rows that cannot be trusted, row 0
+int launch_ens_stream_prologue(alabi_ens* e, double* coords, double* logp, bool first, int fill_rows, hipStream_t s) {
+    const int WT = e->W * e->E, row = e->d + 2;
+    if (fill_rows > 0) hipLaunchKernelGGL(ens_hist_fill_kernel, dim3(1024), dim3(256), 0, s, e->hist + (size_t)WT * row, (size_t)fill_rows * WT * row);
+    if (first) hipLaunchKernelGGL(ens_hist_copy_kernel, dim3((WT * row + 255) / 256), dim3(256), 0, s, coords, logp, e->hist, WT, e->d, 1);
+    ALABI_LAUNCH_CHECK();
+    return ALABI_OK;
+}
+
+StreamArgs ens_stream_args(alabi_ens* e, const DrawBuffers& rec, int K) {
+    alabi_gp* gp = e->gp;
+    StreamArgs a{};
+    a.hist = e->hist; a.err = e->err; a.rec = rec; a.consts = e->consts;
+    const bool se = gp->kf.type == 0;                 // squared exponential: centred inputs and h (se_pair_terms), built by ens_se_prepare
+    a.Xt = se ? gp->Xc : gp->Xt; a.alpha = se ? gp->ens_h : gp->alpha; a.centre = gp->xa_centre;
+    a.K = K; a.W = e->W; a.n0 = (e->W + 1) / 2; a.d = e->d; a.Npad = gp->Npad; a.spin_limit = 1 << 20;
+    if (const char* env = getenv("ALABI_ENS_SPIN_LIMIT")) { const int v = atoi(env); if (v > 0) a.spin_limit = v; }   // tests: force a time-out
+    a.amp = e->lp_scale * exp(gp->log_amp); a.mean = fma(e->lp_scale, gp->mean, e->lp_shift); a.kf = gp->kf;
+    a.has_prior = e->has_prior; a.prior_const = e->prior_const;
+    return a;
+}
+
 // One chunk of K steps on the persistent kernel, proposal records from `rec`.  `first`: row 0 of the history is taken from
 // (coords, logp) (later chunks of a call find it there, left by the previous chunk's epilogue); fill_rows > 0: rows 1..fill_rows
 // cannot be trusted to hold the sentinel (first use of the handle, after a time-out or the group kernel) and are refilled.
 int launch_ens_stream_kernel(alabi_ens* e, const DrawBuffers& rec, double* coords, double* logp, int K, bool first, int fill_rows,
                              hipStream_t s) {
     alabi_gp* gp = e->gp;
-    const int n0 = (e->W + 1) / 2;
-    const int WT = e->W * e->E, row = e->d + 2;
-    if (fill_rows > 0) hipLaunchKernelGGL(ens_hist_fill_kernel, dim3(1024), dim3(256), 0, s, e->hist + (size_t)WT * row, (size_t)fill_rows * WT * row);
-    if (first) hipLaunchKernelGGL(ens_hist_copy_kernel, dim3((WT * row + 255) / 256), dim3(256), 0, s, coords, logp, e->hist, WT, e->d, 1);
-    StreamArgs a{};
-    a.hist = e->hist; a.err = e->err; a.rec = rec; a.consts = e->consts;
-    const bool se = gp->kf.type == 0;                 // squared exponential: centred inputs and h (se_pair_terms), built by ens_se_prepare
-    a.Xt = se ? gp->Xc : gp->Xt; a.alpha = se ? gp->ens_h : gp->alpha; a.centre = gp->xa_centre;
-    a.K = K; a.W = e->W; a.n0 = n0; a.d = e->d; a.Npad = gp->Npad; a.spin_limit = 1 << 20;
-    if (const char* env = getenv("ALABI_ENS_SPIN_LIMIT")) { const int v = atoi(env); if (v > 0) a.spin_limit = v; }   // tests: force a time-out
-    a.amp = e->lp_scale * exp(gp->log_amp); a.mean = fma(e->lp_scale, gp->mean, e->lp_shift); a.kf = gp->kf;
-    a.has_prior = e->has_prior; a.prior_const = e->prior_const;
+    int st = launch_ens_stream_prologue(e, coords, logp, first, fill_rows, s);
+    if (st != ALABI_OK) return st;
+    const StreamArgs a = ens_stream_args(e, rec, K);
     const int db = dim_bucket(e->d);
     // lanes x pairs-per-lane cover Npad/2 point pairs; the launch-per-half-step kernel's lane -> point map (and so its
     // summation order) is reproduced exactly because both run with e->threads compute lanes.

@@ -354,6 +354,9 @@ class EnsembleSampler:
         _lib.lib().alabi_ens_last_path(self._ens, C.byref(path))
         self.last_path = {1: "stream", 3: "group"}.get(path.value, "launch-per-half-step")
         self.last_stream_kernel = {1: "ens_stream_kernel", 3: "ens_group_kernel"}.get(path.value)
+        variant = C.c_int(0)                                  # path 1: one workgroup per list position, or a pair of them
+        _lib.lib().alabi_ens_stream_variant(self._ens, C.byref(variant))
+        self.last_stream_variant = {0: "single", 1: "pair"}[variant.value] if path.value == 1 else None
         self.group_plan = None
         if path.value == 3:                                   # which instantiation of ens_group_kernel ran (tests pin it)
             plan = (C.c_int * 8)()

@@ -237,6 +237,16 @@ int alabi_ens_set_stream(alabi_ens* ens, int enabled);
  * registers (ens_stream_kernel: N <= 2048, small d), 3 = persistent group kernel (ens_group_kernel: training set
  * partitioned over groups of workgroups, kernel sums on the matrix cores; d <= 30), 0 = one launch per half step. */
 int alabi_ens_last_path(alabi_ens* ens, int* path /* host */);
+/* Which persistent kernel the last alabi_ens_run of path 1 launched: 0 = ens_stream_kernel (one workgroup per list position),
+ * 1 = ens_pair_kernel (two per list position, which evaluate both outcomes of a pending update; chosen where 2 ceil(W/2) E
+ * workgroups fit one per CU and the moves are stretch moves; ALABI_ENS_PAIR=0 disables it; a time-out of it is retried inside
+ * the call on ens_stream_kernel and turns it off for the handle).  Both produce the same bits. */
+int alabi_ens_stream_variant(alabi_ens* ens, int* variant /* host */);
+/* Debug counters of ens_pair_kernel, by class (number of input rows of a proposal that the immediately preceding half step
+ * produced: 0, 1, 2): out[3 c] items, out[3 c + 1] rows stored by the workgroup that assumes "rejected", out[3 c + 2] by the one
+ * that assumes "accepted".  The first call switches counting on (from the next run on); reset != 0 zeroes the counters after
+ * reading.  Synchronises the device. */
+int alabi_ens_pair_stats(alabi_ens* ens, long long* out /* host [9] */, int reset);
 /* Blocking of the last group-kernel launch of alabi_ens_run (zeros before the first one), so a parity test can pin WHICH
  * instantiation of ens_group_kernel it compared with the oracle: out[0] Q (16-proposal tiles per group), [1] G (members per
  * group), [2] NG (groups per ensemble), [3] RT (point tiles per wave held in registers), [4] tpm (point tiles per member),

@@ -1,0 +1,34 @@
+"""Phase breakdown of the pair variant of the persistent ensemble kernel (ens_pair_kernel): real-time stamps of the hand-off waves of
+both workgroups of one pair, the verdict poll of the speculative items, and the publish -> detect times of the proposal array and
+of the verdict (needs a build with -DALABI_PAIR_PROF: see tools/README.md)."""
+import ctypes, sys, os, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np, torch
+from alabi_amd import EnsembleSampler, HipGP, _lib
+from alabi_amd.workloads import make_config
+cfg = make_config("C3", N=int(os.environ.get("PROF_N", "2000")))
+h = cfg["hyper"]
+gp = HipGP(cfg["d"], h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"]); gp.compute(cfg["X"])
+s = EnsembleSampler(cfg["W"], cfg["d"], gp, cfg["y"], cfg["bounds"], seed=1)
+s.run_mcmc(cfg["p0"], 1024); torch.cuda.synchronize()
+t0 = time.perf_counter(); s.run_mcmc(None, 1024); torch.cuda.synchronize(); dt = time.perf_counter() - t0
+out = (ctypes.c_longlong * 24)()
+L = _lib.lib()
+L.alabi_debug_pair_prof.argtypes = [ctypes.POINTER(ctypes.c_longlong)]
+print("rc", L.alabi_debug_pair_prof(out), "path", s.last_path, "variant", s.last_stream_variant, "wall us/half-step", 1e6 * dt / 2048)
+v = list(out)
+names = ["input poll wait (hand-off wave)", "rows detected -> barrier A", "barrier A -> barrier B (verdict poll included)",
+         "barrier B -> row store issued"]
+for role, base in (("R (assumes rejected)", 0), ("A (assumes accepted)", 8)):
+    r = v[base:base + 8]
+    n = max(r[4], 1)
+    tick_ns = 1e9 * dt / max(r[5], 1)                # calibrated against the call's wall time (nominal 10 ns)
+    tot = sum(r[:4])
+    print(role)
+    for nm, x in zip(names, r[:4]):
+        print(f"  {nm:46s} {x / n:9.2f} ticks/item {x / n * tick_ns:9.1f} ns  {100.0 * x / max(tot, 1):5.1f}%")
+    print(f"  verdict poll, per class-1 item {r[6] / max(r[7], 1) * tick_ns:9.1f} ns  ({r[7]} of {r[4]} items)")
+    q = v[16 + (4 if base else 0):][:4]
+    print(f"  prop publish -> detected by this reader    {q[0] / max(q[1], 1) * tick_ns:9.1f} ns  (n = {q[1]})")
+    print(f"  row store -> verdict detected by this reader {q[2] / max(q[3], 1) * tick_ns:9.1f} ns  (n = {q[3]})")
+    print("  items", r[4], "ticks total", r[5], "=> tick ns", tick_ns)
