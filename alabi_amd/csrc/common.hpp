@@ -100,7 +100,7 @@ struct alabi_gp {
     size_t mupart_bytes = 0;
     double* pgrad = nullptr;  // scratch of the query-gradient path (v, |v|^2 partials, z parts)
     size_t pgrad_bytes = 0;
-    // ensemble kernels, squared exponential (ensemble.hip: se_pair_terms): the scaled training inputs relative to their mean
+    // ensemble kernels, squared exponential (ens_device.hpp: se_pair_terms): the scaled training inputs relative to their mean
     // (xa_centre) and h_n = |x_n - c|^2 / 2 - ln|alpha_n| with sign(alpha_n) in the lowest mantissa bit, rebuilt whenever `gen` moves
     double* Xc = nullptr;     // [dim_bucket(d), Npad]
     double* ens_h = nullptr;  // [Npad]
@@ -307,23 +307,24 @@ int launch_ens_advance(alabi_ens* e, long long n, hipStream_t s);
 int ens_sync_consts(alabi_ens* e, hipStream_t s);   // (inv_len, bounds, prior) on the device match the GP's hyper-parameters
 int alabi_ens_half_step_hist(alabi_ens* e, const double* coords, const double* logp, int t, int split, int part_begin, int part_end,
                              const double* shist, double* out, hipStream_t s);
+// ens_stream.hip: the persistent kernel, the version history around a persistent launch (also the group kernel's)
 bool ens_stream_fits(const alabi_ens* e);
+int ens_stream_ppt(const alabi_ens* e);          // point pairs per compute lane of the persistent kernels (0: does not fit)
 int launch_ens_stream_kernel(alabi_ens* e, const DrawBuffers& rec, double* coords, double* logp, int K, bool first, int fill_rows, hipStream_t s);
-int ens_stream_ppt_of(const alabi_ens* e);       // point pairs per compute lane of the persistent kernels (0: does not fit)
 int launch_ens_hist_fill(unsigned long long* rows, size_t words, hipStream_t s);
 int launch_ens_stream_prologue(alabi_ens* e, double* coords, double* logp, bool first, int fill_rows, hipStream_t s);
+int launch_ens_stream_epilogue(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
+                               long long* n_accept, long long step_next, long long done0, hipStream_t s);
+int launch_ens_hist_prologue(alabi_ens* e, double* coords, double* logp, int K, bool fill, hipStream_t s);
+int launch_ens_hist_epilogue(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
+                             long long* n_accept, hipStream_t s);
 // ens_pair.hip: the pair variant of the persistent kernel (two workgroups per list position, both outcomes of a pending update)
 bool ens_pair_ready(alabi_ens* e);
 void ens_pair_release(alabi_ens* e);
 int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, double* coords, double* logp, int K, bool first, int fill_rows, hipStream_t s);
-int launch_ens_stream_epilogue(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
-                               long long* n_accept, long long step_next, long long done0, hipStream_t s);
 // ens_group.hip
 bool ens_group_fits(const alabi_ens* e);
 bool ens_group_buffers(alabi_ens* e, hipStream_t s);   // the group kernel's hand-off buffers exist (allocates on first use); false: take another path
 int launch_ens_group(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
                      long long* n_accept, hipStream_t s);
-int launch_ens_hist_prologue(alabi_ens* e, double* coords, double* logp, int K, bool fill, hipStream_t s);
-int launch_ens_hist_epilogue(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
-                             long long* n_accept, hipStream_t s);
 }  // namespace alabi

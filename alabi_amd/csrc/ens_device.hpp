@@ -1,4 +1,4 @@
-// Device helpers shared by the ensemble kernels (ensemble.hip) and the nested-sampling walk kernel (nested.hip):
+// Device helpers shared by the ensemble kernels (ensemble.hip, ens_stream.hpp) and the nested-sampling walk kernel (nested.hip):
 // the counter-based Philox4x32-10 generator, the inverse y-scaler map and the squared-exponential pair terms.
 #pragma once
 #include "gp_device.hpp"

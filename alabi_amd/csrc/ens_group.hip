@@ -36,13 +36,12 @@
 // instructions each) = 1.5 us of the fp64 pipe.
 #include <cstdlib>
 #include <vector>
-#include "gp_device.hpp"
+#include "ens_stream.hpp"
 
 namespace alabi {
 
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 
-#define ALABI_GRP_EMPTY 0x7FF8A1AB1D15EA5Eull   // the sentinel of the version history (ensemble.hip: ALABI_HIST_EMPTY)
 #define ALABI_GRP_NW 8                           // waves per workgroup (512 threads, two per SIMD)
 // (Round 4, measured and not kept -- tools/experiments/ens_group_exp_table_2048.patch: a 2048-entry exp table (16 KB of LDS) with a
 // degree-3 polynomial, one fused multiply-add fewer per kernel evaluation (9 instead of 10 fp64 instructions, 1.93 ulp): C4 4.85 vs
@@ -69,12 +68,6 @@ struct GroupArgs {
     KernelFn kf;
 };
 
-__device__ inline unsigned long long grp_ld(const unsigned long long* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ inline void grp_st(unsigned long long* p, unsigned long long v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ inline unsigned long long grp_bits(double v) { return (unsigned long long)__double_as_longlong(v); }
 __device__ inline double grp_dbl(unsigned long long v) { return __longlong_as_double((long long)v); }
 
@@ -361,8 +354,8 @@ ens_group_kernel(GroupArgs p) {
         for (int ps = 0; ps < NPM; ++ps) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                if (want_[ps] & (32u << i)) vc_[ps][i] = grp_ld(pc_[ps] + i);
-                if (want_[ps] & (1u << i)) va_[ps][i] = grp_ld(pa_[ps][i]);
+                if (want_[ps] & (32u << i)) vc_[ps][i] = ld_sc1(pc_[ps] + i);
+                if (want_[ps] & (1u << i)) va_[ps][i] = ld_sc1(pa_[ps][i]);
             }
         }
         // (b) ... and looks at the FRESH words, the partial sums of the half step just before.  A look costs a memory round
@@ -376,10 +369,10 @@ ens_group_kernel(GroupArgs p) {
             while (bmiss) {
                 unsigned long long tb[NPM];
 #pragma unroll
-                for (int ps = 0; ps < NPM; ++ps) { tb[ps] = ALABI_GRP_EMPTY; if (bmiss & (1u << ps)) tb[ps] = grp_ld(pb_[ps]); }
+                for (int ps = 0; ps < NPM; ++ps) { tb[ps] = ALABI_HIST_EMPTY; if (bmiss & (1u << ps)) tb[ps] = ld_sc1(pb_[ps]); }
 #pragma unroll
                 for (int ps = 0; ps < NPM; ++ps)
-                    if ((bmiss & (1u << ps)) && tb[ps] != ALABI_GRP_EMPTY) { vb_[ps] = tb[ps]; bmiss &= ~(1u << ps); }
+                    if ((bmiss & (1u << ps)) && tb[ps] != ALABI_HIST_EMPTY) { vb_[ps] = tb[ps]; bmiss &= ~(1u << ps); }
                 if (bmiss && (++spins > p.spin_limit ||
                               ((spins & 63) == 0 && __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0))) {
                     ok = 0;
@@ -394,16 +387,16 @@ ens_group_kernel(GroupArgs p) {
             for (int ps = 0; ps < NPM; ++ps)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    if ((want_[ps] & (32u << i)) && vc_[ps][i] == ALABI_GRP_EMPTY) all = false;
-                    if ((want_[ps] & (1u << i)) && va_[ps][i] == ALABI_GRP_EMPTY) all = false;
+                    if ((want_[ps] & (32u << i)) && vc_[ps][i] == ALABI_HIST_EMPTY) all = false;
+                    if ((want_[ps] & (1u << i)) && va_[ps][i] == ALABI_HIST_EMPTY) all = false;
                 }
             if (all) break;
 #pragma unroll
             for (int ps = 0; ps < NPM; ++ps)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    if ((want_[ps] & (32u << i)) && vc_[ps][i] == ALABI_GRP_EMPTY) vc_[ps][i] = grp_ld(pc_[ps] + i);
-                    if ((want_[ps] & (1u << i)) && va_[ps][i] == ALABI_GRP_EMPTY) va_[ps][i] = grp_ld(pa_[ps][i]);
+                    if ((want_[ps] & (32u << i)) && vc_[ps][i] == ALABI_HIST_EMPTY) vc_[ps][i] = ld_sc1(pc_[ps] + i);
+                    if ((want_[ps] & (1u << i)) && va_[ps][i] == ALABI_HIST_EMPTY) va_[ps][i] = ld_sc1(pa_[ps][i]);
                 }
             if (++spins > p.spin_limit ||
                 ((spins & 15) == 0 && __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
@@ -493,9 +486,9 @@ ens_group_kernel(GroupArgs p) {
             if (valid && mine_[ps]) {
                 // candidate of this proposal (everything the accept test needs but the kernel sum), for whoever reads the row later
                 unsigned long long* cn = cand_h + cand_off_[ps];
-                if (k < d) { grp_st(cn + k, grp_bits(qv)); grp_st(cn + d + k, grp_bits(sv)); }
-                else if (k == d) { grp_st(cn + 2 * d, grp_bits(sv)); grp_st(cn + 2 * d + 3, grp_bits(seg_out == 0ull ? pr + p.prior_const : -INFINITY)); }
-                else if (k == d + 1) { grp_st(cn + 2 * d + 1, rs[4 * pp + 2]); grp_st(cn + 2 * d + 2, rs[4 * pp + 3]); }
+                if (k < d) { st_sc1(cn + k, grp_bits(qv)); st_sc1(cn + d + k, grp_bits(sv)); }
+                else if (k == d) { st_sc1(cn + 2 * d, grp_bits(sv)); st_sc1(cn + 2 * d + 3, grp_bits(seg_out == 0ull ? pr + p.prior_const : -INFINITY)); }
+                else if (k == d + 1) { st_sc1(cn + 2 * d + 1, rs[4 * pp + 2]); st_sc1(cn + 2 * d + 2, rs[4 * pp + 3]); }
                 // the chain: version t of the own walker (t = 0 is already there)
                 if (t > 0 && k <= d + 1)
                     hist_t[(size_t)w * row + k] = (k <= d) ? grp_bits(sv) : (unsigned long long)acc_o;
@@ -580,7 +573,7 @@ ens_group_kernel(GroupArgs p) {
 #pragma unroll
                 for (int w = 0; w < NW; ++w) x[w] = wsum[w * QPAD + pp];
                 const double s = ((x[0] + x[1]) + (x[2] + x[3])) + ((x[4] + x[5]) + (x[6] + x[7]));
-                grp_st(part_h + (size_t)pp * G, grp_bits(s));
+                st_sc1(part_h + (size_t)pp * G, grp_bits(s));
             }
         }
 #ifdef ALABI_GROUP_PROF
@@ -689,7 +682,7 @@ bool ens_group_buffers(alabi_ens* e, hipStream_t s) {
 
 __global__ void __launch_bounds__(256)
 ens_group_fill_kernel(unsigned long long* __restrict__ h, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) h[i] = ALABI_GRP_EMPTY;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) h[i] = ALABI_HIST_EMPTY;
 }
 
 #define ALABI_GROUP_DISPATCH_Q(Q_, ...)                      \

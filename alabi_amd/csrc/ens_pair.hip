@@ -1,6 +1,6 @@
 // Persistent ensemble kernel, pair variant: both outcomes of a pending update on two CUs.
 //
-// ens_stream_kernel (ensemble.hip) runs one workgroup per list position on half of the CUs, and a half step is a hand-off hop
+// ens_stream_kernel (ens_stream.hip) runs one workgroup per list position on half of the CUs, and a half step is a hand-off hop
 // followed by a kernel sum, one after the other.  A proposal of half step h + 1 does not need the verdict of the half step-h
 // update it reads, only the state of that walker, and that state is one of two rows which are both known early: the walker's
 // previous row (in the history) and the proposal of half step h (known on its CU a whole kernel sum before its verdict).  Here
@@ -51,7 +51,8 @@ __device__ inline long long pair_pub_age(int which, size_t row_index, long long 
 }
 #endif
 
-// blockDim.x = TMAX = 64 + compute threads + 64; roles, barriers and the compute waves' code as in ens_stream_kernel.
+// blockDim.x = TMAX = 64 + compute threads + 64; roles and barriers as in ens_stream_kernel, the set-up, the item iterator, the
+// compute waves' loop and the bounded poll are that kernel's (ens_stream.hpp).
 template <int D, int PPT, int TMAX, bool GENERIC>
 __global__ void __launch_bounds__(TMAX)
 ens_pair_kernel(PairArgs pa) {
@@ -73,51 +74,16 @@ ens_pair_kernel(PairArgs pa) {
     long long prof[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const long long prof_begin = wall_clock64();
 #endif
-    // training-set share of this lane, resident for the whole launch (same lane -> point map as ens_half_kernel)
-    const int half = p.Npad >> 1, ct = tid - 64;
     f64x2 xa[PPT][D], aa[PPT];
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-        const int idx = ct + j * TC;
-        const bool v = compute && idx < half;
-#pragma unroll
-        for (int k = 0; k < D; ++k)
-            xa[j][k] = v ? reinterpret_cast<const f64x2*>(p.Xt + (size_t)k * p.Npad)[idx] : f64x2{0.0, 0.0};
-        aa[j] = v ? reinterpret_cast<const f64x2*>(p.alpha)[idx] : (GENERIC ? f64x2{0.0, 0.0} : f64x2{ALABI_SE_PAD, ALABI_SE_PAD});
-    }
-    if (tid < ALABI_MAX_DIM) {
-        consts_s[0][tid] = (tid < p.d) ? p.consts[tid] : 0.0;
-        consts_s[1][tid] = (tid < p.d) ? p.consts[ALABI_MAX_DIM + tid] : 0.0;
-        consts_s[2][tid] = (tid < p.d) ? p.consts[2 * ALABI_MAX_DIM + tid] : 0.0;
-        consts_s[3][tid] = (tid < p.d) ? p.consts[3 * ALABI_MAX_DIM + tid] : 0.0;
-        consts_s[4][tid] = (tid < p.d) ? p.consts[4 * ALABI_MAX_DIM + tid] : 0.0;
-        consts_s[5][tid] = (!GENERIC && tid < p.d) ? p.centre[tid] : 0.0;
-    }
-    if (tid < 32) scratch[tid >> 4][tid & 15] = 0.0;
-    if (tid == 0) abort_s = 0;
+    stream_setup<D, PPT, TC, GENERIC>(p, compute, xa, aa, consts_s, scratch, abort_s);
 
     // The pair's proposals: list position b of every half step that has one (G = n0 pairs per ensemble, so at most one item
     // per half step), in (step, split) order.
-    const int G = gridDim.x >> 1;
-    auto next_item = [&](int& t, int& split, int& bb) {
-        bb += G;
-        for (;;) {
-            if (t >= p.K) return;
-            if (bb < (split ? p.W - p.n0 : p.n0)) return;
-            bb = b;
-            if (split == 0) split = 1; else { split = 0; ++t; }
-        }
-    };
+    const StreamItems items{p, (int)(gridDim.x >> 1), b};
     // Record wave: the packed record is fetched four items ahead (lane l < 4 loads word l); one item later, when its walker ids
     // are in registers, lanes 4 and 5 fetch the list positions of the two walkers in step t - 1, which say whether the rows
     // the proposal reads are fresh.  Both are in the ring two items before the hand-off wave decodes them.
-    const unsigned long long* packed = p.rec.packed;
     const int* pos_of = p.rec.pos_of;
-    auto record_load = [&](int t, int split, int bb) -> unsigned long long {
-        if (t >= p.K || lane >= 4) return 0ull;
-        const size_t pos = ((size_t)t * E + e) * p.W + (split ? p.n0 : 0) + bb;
-        return packed[4 * pos + lane];
-    };
     // lane 4: the own row is fresh, lane 5: the partner row is fresh (`rec`: the item's packed record, walker ids in lane 0)
     auto fresh_load = [&](int t, int split, unsigned long long rec) -> unsigned long long {
         const int w = __builtin_amdgcn_readlane((int)(unsigned)(rec & 0xffffffffull), 0);
@@ -132,17 +98,17 @@ ens_pair_kernel(PairArgs pa) {
     int pt = 0, psplit = 0, pbb = b, pslot = 0;             // the item the next record load is for
     if (service) {                                    // prologue: items 0 and 1 into the ring, item 2 in registers, item 3 in flight
         for (int i = 0; i < 2; ++i) {
-            const unsigned long long r = record_load(pt, psplit, pbb);
+            const unsigned long long r = stream_record_load(p, E, e, lane, pt, psplit, pbb);
             const unsigned long long f = fresh_load(pt, psplit, r);
             if (lane < 6) rec_s[pslot & 3][lane] = lane < 4 ? r : f;
-            next_item(pt, psplit, pbb); ++pslot;
+            items.next(pt, psplit, pbb); ++pslot;
         }
-        rec_a = record_load(pt, psplit, pbb);
+        rec_a = stream_record_load(p, E, e, lane, pt, psplit, pbb);
         fresh_a = fresh_load(pt, psplit, rec_a);
-        next_item(pt, psplit, pbb);
+        items.next(pt, psplit, pbb);
         bt = pt; bsplit = psplit;
-        rec_b = record_load(pt, psplit, pbb);
-        next_item(pt, psplit, pbb);
+        rec_b = stream_record_load(p, E, e, lane, pt, psplit, pbb);
+        items.next(pt, psplit, pbb);
     }
     __syncthreads();
     int t = 0, split = 0, bb = b, item = 0;           // b < G = n0: the first item is valid
@@ -198,16 +164,11 @@ ens_pair_kernel(PairArgs pa) {
             const long long c0 = wall_clock64();
 #endif
             unsigned long long ws, wc;
-            int spins = 0;
-            bool pending;
-            for (;;) {
+            const bool pending = stream_poll(p, [&] {
                 ws = ld_sc1(n_hw);
                 wc = ld_sc1(n_hc);
-                pending = __builtin_amdgcn_ballot_w64(ws == ALABI_HIST_EMPTY || wc == ALABI_HIST_EMPTY) != 0;
-                if (!pending) break;
-                if (__builtin_expect(++spins > p.spin_limit || ((spins & 63) == 0 && __builtin_amdgcn_readfirstlane(
-                        __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0), 0)) break;
-            }
+                return __builtin_amdgcn_ballot_w64(ws == ALABI_HIST_EMPTY || wc == ALABI_HIST_EMPTY) != 0;
+            });
             // Bounded spin ran out: as in ens_stream_kernel the cold block rejoins the fast path -- a NaN stretch factor puts
             // the proposal out of bounds, this is the last proposal, nothing of it is stored or published.
             if (__builtin_expect(pending, 0)) {
@@ -243,7 +204,7 @@ ens_pair_kernel(PairArgs pa) {
             const long long c2 = wall_clock64();
 #endif
             int t2 = t, s2 = split, b2 = bb;
-            next_item(t2, s2, b2);
+            items.next(t2, s2, b2);
             if (pending) t2 = p.K;
             double prior_q = 0.0;
             if (p.has_prior) {
@@ -263,15 +224,10 @@ ens_pair_kernel(PairArgs pa) {
 #endif
             if (mode == 1 && !pending) {
                 unsigned long long vw;
-                bool vpend;
-                int vspins = 0;
-                for (;;) {
+                const bool vpend = stream_poll(p, [&] {
                     vw = ld_sc1(ver);
-                    vpend = __builtin_amdgcn_ballot_w64(vw == ALABI_HIST_EMPTY) != 0;
-                    if (!vpend) break;
-                    if (__builtin_expect(++vspins > p.spin_limit || ((vspins & 63) == 0 && __builtin_amdgcn_readfirstlane(
-                            __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0), 0)) break;
-                }
+                    return __builtin_amdgcn_ballot_w64(vw == ALABI_HIST_EMPTY) != 0;
+                });
                 if (__builtin_expect(vpend, 0)) {     // time-out: the last proposal, nothing stored
                     abort_s = 1;
                     __hip_atomic_store(p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -332,65 +288,19 @@ ens_pair_kernel(PairArgs pa) {
         }
 #endif
     } else if (compute) {
-        // ---- compute waves: A -> q -> sum -> DPP -> partial -> B (ens_stream_kernel's code)
-        while (t < p.K) {
-            next_item(t, split, bb);
-            const int par = item & 1;
-            __syncthreads();                          // barrier A
-            double q[D];
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-                const double r = qs_s[par][k];
-                q[k] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(r)),
-                                        __builtin_amdgcn_readfirstlane(__double2loint(r)));
-            }
-            const int inb = __builtin_amdgcn_readfirstlane(__double2hiint(qs_s[par][D]));
-            __builtin_amdgcn_sched_group_barrier(0x100, D + 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x2, 2 * D + 1, 0);
-            if (inb != 0) {
-                double acc = 0.0;
-                if (!GENERIC) {
-                    const double nhq = se_neg_half_norm<D>(q);
-#pragma unroll
-                    for (int j = 0; j < PPT; ++j) {
-                        double fa, fb;
-                        se_pair_terms<D>(xa[j], aa[j], q, nhq, fa, fb);
-                        acc += fa; acc += fb;
-                        if ((j & 1) == 1) __builtin_amdgcn_sched_barrier(0);
-                    }
-                } else
-#pragma unroll
-                for (int j = 0; j < PPT; ++j) {
-                    double r2a = 0.0, r2b = 0.0;
-#pragma unroll
-                    for (int k = 0; k < D; ++k) {
-                        const double da = xa[j][k].x - q[k], db = xa[j][k].y - q[k];
-                        r2a = fma(da, da, r2a);
-                        r2b = fma(db, db, r2b);
-                    }
-                    acc = (j == 0) ? aa[j].x * radial<GENERIC>(r2a, p.kf) : fma(aa[j].x, radial<GENERIC>(r2a, p.kf), acc);
-                    acc = fma(aa[j].y, radial<GENERIC>(r2b, p.kf), acc);
-                    if ((j & 1) == 1) __builtin_amdgcn_sched_barrier(0);
-                }
-                const double wsum = wave_sum_dpp(acc);
-                if (lane == 63) scratch[par][wv - 1] = wsum;
-            }
-            __syncthreads();                          // barrier B
-            if (abort_s) return;
-            ++item;
-        }
+        stream_compute_loop<D, PPT, GENERIC>(p, items, xa, aa, qs_s, scratch, abort_s, lane, wv);
     } else {
         // ---- record wave: ring slot item + 2 <- (record, freshness) in registers; freshness of item + 3; record of item + 4
         while (t < p.K) {
-            next_item(t, split, bb);
+            items.next(t, split, bb);
             __syncthreads();                          // barrier A
             if (lane < 6) rec_s[pslot & 3][lane] = lane < 4 ? rec_a : fresh_a;
             ++pslot;
             rec_a = rec_b;
             fresh_a = fresh_load(bt, bsplit, rec_a);
             bt = pt; bsplit = psplit;
-            rec_b = record_load(pt, psplit, pbb);
-            next_item(pt, psplit, pbb);
+            rec_b = stream_record_load(p, E, e, lane, pt, psplit, pbb);
+            items.next(pt, psplit, pbb);
             __syncthreads();                          // barrier B
             if (abort_s) return;
         }
@@ -402,24 +312,6 @@ extern "C" int alabi_debug_pair_prof(long long* out) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pair_prof), sizeof(long long) * 24);
 }
 #endif
-
-#define ALABI_PAIR_DISPATCH_DIM(DB, ...)                              \
-    switch (DB) {                                                     \
-        case 1: { constexpr int D = 1; __VA_ARGS__; } break;          \
-        case 2: { constexpr int D = 2; __VA_ARGS__; } break;          \
-        case 3: { constexpr int D = 3; __VA_ARGS__; } break;          \
-        case 4: { constexpr int D = 4; __VA_ARGS__; } break;          \
-        case 5: { constexpr int D = 5; __VA_ARGS__; } break;          \
-        case 6: { constexpr int D = 6; __VA_ARGS__; } break;          \
-        case 8: { constexpr int D = 8; __VA_ARGS__; } break;          \
-        case 10: { constexpr int D = 10; __VA_ARGS__; } break;        \
-        case 12: { constexpr int D = 12; __VA_ARGS__; } break;        \
-        case 16: { constexpr int D = 16; __VA_ARGS__; } break;        \
-        default: return ALABI_BAD_ARGUMENT;                           \
-    }
-#define ALABI_PAIR_LAUNCH(PPT_, TMAX_)                                                                            \
-    ALABI_PAIR_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type,                                                \
-        hipLaunchKernelGGL((ens_pair_kernel<D, PPT_, TMAX_, GENERIC>), dim3(2 * n0, e->E), dim3(TMAX_), 0, s, a)))
 
 // The pair variant can run this handle: prop allocated (lazily, here), one workgroup per CU for 2 ceil(W/2) E workgroups, not
 // switched off by ALABI_ENS_PAIR=0 or by an earlier time-out of this handle.  The caller has checked ens_stream_fits and the moves.
@@ -455,7 +347,6 @@ void ens_pair_release(alabi_ens* e) {
 // sentinel in front of every chunk (the epilogue restores the sentinel in hist only).
 int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, double* coords, double* logp, int K, bool first, int fill_rows,
                            hipStream_t s) {
-    alabi_gp* gp = e->gp;
     const int n0 = (e->W + 1) / 2;
     const int WT = e->W * e->E, row = e->d + 2;
     int st = launch_ens_stream_prologue(e, coords, logp, first, fill_rows, s);
@@ -464,20 +355,11 @@ int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, double* coords,
     PairArgs a{};
     a.s = ens_stream_args(e, rec, K);
     a.prop = e->prop; a.stats = e->pair_stats;
-    const int db = dim_bucket(e->d);
-    const int T = e->threads, ppt = ens_stream_ppt_of(e);
     e->last_path = 1;
-    if (T == 256) {
-        if (ppt == 1) { ALABI_PAIR_LAUNCH(1, 384); }
-        else if (ppt == 2) { ALABI_PAIR_LAUNCH(2, 384); }
-        else if (ppt == 3) { ALABI_PAIR_LAUNCH(3, 384); }
-        else if (ppt == 4) { ALABI_PAIR_LAUNCH(4, 384); }
-        else return ALABI_BAD_ARGUMENT;
-    } else if (T == 512) {
-        if (ppt == 1) { ALABI_PAIR_LAUNCH(1, 640); }
-        else if (ppt == 2) { ALABI_PAIR_LAUNCH(2, 640); }
-        else return ALABI_BAD_ARGUMENT;
-    } else return ALABI_BAD_ARGUMENT;
+    st = ens_stream_dispatch(e, [&](auto D, auto PPT, auto TMAX, auto GENERIC) {
+        hipLaunchKernelGGL((ens_pair_kernel<D(), PPT(), TMAX(), GENERIC()>), dim3(2 * n0, e->E), dim3(TMAX()), 0, s, a);
+    });
+    if (st != ALABI_OK) return st;
     ALABI_LAUNCH_CHECK();
     return ALABI_OK;
 }

@@ -13,8 +13,9 @@ __host__ __device__ inline int dim_bucket(int d) {
     return -1;
 }
 
-#define ALABI_DISPATCH_DIM(DB, ...)                                   \
-    switch (DB) {                                                     \
+// ALABI_DISPATCH_DIM16: the buckets up to 16 only, for kernels that keep whole proposals per lane in registers (the persistent
+// ensemble kernels, four proposals per workgroup in ens_half_multi_kernel); a larger bucket is ALABI_BAD_ARGUMENT.
+#define ALABI_DIM_CASES16(...)                                        \
         case 1: { constexpr int D = 1; __VA_ARGS__; } break;          \
         case 2: { constexpr int D = 2; __VA_ARGS__; } break;          \
         case 3: { constexpr int D = 3; __VA_ARGS__; } break;          \
@@ -24,7 +25,15 @@ __host__ __device__ inline int dim_bucket(int d) {
         case 8: { constexpr int D = 8; __VA_ARGS__; } break;          \
         case 10: { constexpr int D = 10; __VA_ARGS__; } break;        \
         case 12: { constexpr int D = 12; __VA_ARGS__; } break;        \
-        case 16: { constexpr int D = 16; __VA_ARGS__; } break;        \
+        case 16: { constexpr int D = 16; __VA_ARGS__; } break;
+#define ALABI_DISPATCH_DIM16(DB, ...)                                 \
+    switch (DB) {                                                     \
+        ALABI_DIM_CASES16(__VA_ARGS__)                                \
+        default: return ALABI_BAD_ARGUMENT;                           \
+    }
+#define ALABI_DISPATCH_DIM(DB, ...)                                   \
+    switch (DB) {                                                     \
+        ALABI_DIM_CASES16(__VA_ARGS__)                                \
         case 20: { constexpr int D = 20; __VA_ARGS__; } break;        \
         case 24: { constexpr int D = 24; __VA_ARGS__; } break;        \
         case 32: { constexpr int D = 32; __VA_ARGS__; } break;        \

@@ -107,6 +107,26 @@ def test_out_of_bounds_proposals(problems, monkeypatch):
     _compare(problems(10), monkeypatch, 16, 10, half_width=0.25, p0_width=0.25)
 
 
+# (compute lanes, training points) -> point pairs per lane = ceil(Npad / 2 / lanes), Npad = N rounded up to 64
+LADDER_ROWS = [(256, 150, 1), (256, 600, 2), (256, 1100, 3), (256, 1600, 4), (512, 150, 1), (512, 1100, 2)]
+
+
+@pytest.mark.parametrize("lanes,N,ppt", LADDER_ROWS)
+def test_every_row_of_the_launch_table(problems, monkeypatch, lanes, N, ppt):
+    """One configuration per (compute lanes, point pairs per lane) row of the persistent kernels' launch table: the pair kernel
+    and the single kernel of that row run, and their chains are those of one launch per half step with the same lanes."""
+    npad = -(-N // 64) * 64
+    assert -(-(npad // 2) // lanes) == ppt
+    W, d, nsteps = 8, 3, 4
+    monkeypatch.setenv("ALABI_ENS_THREADS", str(lanes))  # read, like ALABI_ENS_STREAM, when the sampler's handle is created
+    s = _compare(problems(d, N=N), monkeypatch, W, d, nsteps=nsteps)
+    monkeypatch.setenv("ALABI_ENS_PAIR", "0")
+    single = _sampler(problems(d, N=N), monkeypatch, "1", W, d)
+    single.run_mcmc(np.random.RandomState(W + d).uniform(-2.0, 2.0, (W, d)), nsteps)
+    assert single.last_path == "stream" and single.last_stream_variant == "single" and getattr(single, "stream_fallbacks", 0) == 0
+    _assert_same(_result(single), _result(s), (lanes, N, ppt))
+
+
 def _host_class_counts(s, W, nsteps):
     """Items per class from the exported draws (labels of consecutive steps): class = number of input rows of a proposal that
     the immediately preceding half step produced."""

@@ -1,6 +1,7 @@
 """Register budget of the pair variant of the persistent ensemble kernel (ens_pair_kernel), read off the gfx950 code object
-metadata (no GPU needed): the instantiations that the benchmark configurations C1, C2 and C3 launch spill no register and
-use no scratch memory."""
+metadata (no GPU needed): the instantiations that the benchmark configurations C1, C2 and C3 launch are there, and no
+instantiation that the library contains -- the launch table compiles exactly those that the fit rule (ens_stream_max_db) can
+select -- spills a register or uses scratch memory."""
 import os
 import re
 import shutil
@@ -53,3 +54,11 @@ def test_benchmark_instantiations_spill_nothing(metadata, d, ppt):
     assert m["sgpr_spill_count"] == 0
     assert m["vgpr_spill_count"] == 0
     assert m["private_segment_fixed_size"] == 0
+
+
+def test_no_instantiation_spills(metadata):
+    pair = {name: m for name, m in metadata.items() if "ens_pair_kernel" in name}
+    assert _pair_kernel(10, 4, 384, False) in pair
+    assert len(pair) == 102      # the rows of the launch table: 55 squared-exponential, 47 generic
+    for name, m in pair.items():
+        assert m == {"sgpr_spill_count": 0, "vgpr_spill_count": 0, "private_segment_fixed_size": 0}, (name, m)

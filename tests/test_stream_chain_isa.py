@@ -16,6 +16,9 @@ The same function on the listing of the commit before this file existed gave
   lgkm waits 2, round trips 2;  poll -> A 112 instructions, 30 of them control;  B -> store 56
 (in that listing the stretch from the poll to barrier A also holds, in layout order, the blocks of the time-out and of the
 exec-mask ladders around them; the fast path through it is about 70 instructions long).
+
+The code object's metadata is held to one more thing: every instantiation of the kernel that the library contains -- the launch
+table compiles exactly those that the fit rule (ens_stream_max_db) can select -- spills no register and uses no scratch memory.
 """
 import os
 import re
@@ -83,16 +86,21 @@ def chain_counts(body):
 
 
 @pytest.fixture(scope="module")
-def counts(tmp_path_factory):
+def listing(tmp_path_factory):
     hipcc = _hipcc()
     if hipcc is None:
         pytest.skip("hipcc is not installed")
-    out = tmp_path_factory.mktemp("isa") / "ensemble.s"
+    out = tmp_path_factory.mktemp("isa") / "ens_stream.s"
     cmd = [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--offload-device-only", "-S",
-           os.path.join(CSRC, "ensemble.hip"), "-o", str(out)]
+           os.path.join(CSRC, "ens_stream.hip"), "-o", str(out)]
     res = subprocess.run(cmd, capture_output=True, text=True)
     assert res.returncode == 0, res.stderr[-4000:]
-    c = chain_counts(kernel_body(out.read_text(), HEADLINE))
+    return out.read_text()
+
+
+@pytest.fixture(scope="module")
+def counts(listing):
+    c = chain_counts(kernel_body(listing, HEADLINE))
     print(c)
     return c
 
@@ -112,6 +120,19 @@ def test_poll_to_barrier_a_is_pinned(counts):
 
 def test_barrier_b_to_row_store_is_pinned(counts):
     assert counts["b_to_store"] == 22
+
+
+def test_no_instantiation_spills(listing):
+    kernels = {}
+    for block in listing.split("  - .agpr_count")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", block)
+        if name and "ens_stream_kernel" in name.group(1):
+            kernels[name.group(1)] = {k: int(v) for k, v in re.findall(
+                r"\.(sgpr_spill_count|vgpr_spill_count|private_segment_fixed_size):\s+(\d+)", block)}
+    assert HEADLINE in kernels
+    assert len(kernels) == 102      # the rows of the launch table: 55 squared-exponential, 47 generic
+    for name, m in kernels.items():
+        assert m == {"sgpr_spill_count": 0, "vgpr_spill_count": 0, "private_segment_fixed_size": 0}, (name, m)
 
 
 if __name__ == "__main__":

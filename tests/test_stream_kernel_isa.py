@@ -25,9 +25,9 @@ def metadata(tmp_path_factory):
     hipcc = _hipcc()
     if hipcc is None:
         pytest.skip("hipcc is not installed")
-    out = tmp_path_factory.mktemp("isa") / "ensemble.s"
+    out = tmp_path_factory.mktemp("isa") / "ens_stream.s"
     cmd = [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--offload-device-only", "-S",
-           os.path.join(CSRC, "ensemble.hip"), "-o", str(out)]
+           os.path.join(CSRC, "ens_stream.hip"), "-o", str(out)]
     res = subprocess.run(cmd, capture_output=True, text=True)
     assert res.returncode == 0, res.stderr[-4000:]
     text = out.read_text()
