@@ -1092,8 +1092,52 @@ class SurrogateModel(object):
                                                 f"Prior function: {getattr(prior_transform, '__name__', 'unrecorded')}")
         plan = post.plan_nested(self.like_fn, self.surrogate_log_likelihood, self.prior_transform, self.bounds,
                                 getattr(self, "theta_scaler", None), getattr(self, "y_scaler", None), getattr(self, "_y", None))
-        gp_obj, y_obj = self._handle_owner()
-        return plan, gp_obj, y_obj
+        return plan, *self._handle_owner()
+
+    def _nested_runs(self, name, label, setup, seed, make_sampler, run_args, min_ess, note, collect, t0, samples_file,
+                     file_fields=(), custom_is_surrogate=True, checkpoint=None):
+        """The runs and the tail of run_dynesty / run_pymultinest / run_ultranest, whose attributes start with ``name``.  Run k takes
+        the seed (``seed`` + 1000003 (k - 1), or the model's seed stream when None) + rank, builds a GPUWalkBackend from ``setup``
+        (the result of ``_nested_setup``) and ``make_sampler(backend, seed)`` on it, runs ``run_nested(**run_args)`` and resamples to
+        equal weights; ``collect(results, samples)`` keeps what the front end combines over its runs (it sets the log Z attributes
+        from the runs so far), ``checkpoint(sampler, k)`` makes run_dynesty's ``save_iter`` callable.  Runs repeat until ``min_ess``
+        samples exist.  Rank 0 then writes the samples with the ``name``_``file_fields`` attributes."""
+        from . import dist as adist
+        from .nested import GPUWalkBackend
+        rank, _ = adist.world_info()
+        plan, gp_obj, y_obj = setup
+        normal = {} if plan.normal_prior is None else {"normal_prior": plan.normal_prior}     # Gaussian prior coordinates
+
+        def run(run_number):
+            s = (self._seed() if seed is None else int(seed) + 1000003 * (run_number - 1)) + rank
+            backend = GPUWalkBackend(gp_obj, y_obj, plan.box, seed=s, to_theta=plan.to_theta, logp_affine=plan.logp_affine,
+                                     logp_map=plan.logp_map, host_loglike=plan.host_like, **normal)
+            sampler = make_sampler(backend, s)
+            setattr(self, f"{name}_sampler", sampler)
+            cp = checkpoint(sampler, run_number) if checkpoint is not None and rank == 0 else None
+            res = sampler.run_nested(**run_args, **({} if checkpoint is None else {"checkpoint": cp}))
+            if cp is not None:
+                cp.write(res)
+            backend.close()
+            setattr(self, f"{name}_results", res)
+            setattr(self, f"{name}_path", backend.path)
+            eq = res.samples_equal(np.random.default_rng(s))
+            collect(res, eq)
+            return eq
+
+        samples = post.run_until_min_ess(run, min_ess, note if self.verbose else None)
+        setattr(self, f"{name}_samples", samples)
+        if self.like_fn_name == "true":
+            setattr(self, f"{name}_samples_true", samples)
+        elif self.like_fn_name == "surrogate" or custom_is_surrogate:
+            setattr(self, f"{name}_samples_surrogate", samples)
+        setattr(self, f"{name}_run", True)
+        setattr(self, f"{name}_runtime", time.time() - t0)
+        if rank != 0:
+            return                                   # files are rank 0's
+        fname = self._write_samples(name, samples, samples_file, **{k: getattr(self, f"{name}_{k}") for k in file_fields})
+        if self.verbose:
+            print(f"Saved {label} samples to {fname}")
 
     def run_dynesty(self, like_fn=None, prior_transform=None, mode="dynamic", sampler_kwargs={}, run_kwargs={},
                     multi_proc=False, save_iter=None, prior_transform_comment=None, samples_file=None, min_ess=int(1e4)):
@@ -1118,9 +1162,7 @@ class SurrogateModel(object):
         ``maxiter`` (5e4), ``maxcall``, and for mode="dynamic" ``dlogz_init`` (0.5), ``nlive_init``, ``nlive_batch``,
         ``maxbatch`` (10), ``n_effective`` (1e4), ``wt_kwargs`` / ``stop_kwargs`` (pfrac = 1.0 only).  Under
         ``torch.distributed`` every rank runs its own sampler (seed + rank) and rank 0 writes the files."""
-        from . import dist as adist
-        from .nested import GPUWalkBackend, NestedSampler, PickleCheckpoint
-        rank, world = adist.world_info()
+        from .nested import NestedSampler, PickleCheckpoint
         dynesty_t0 = time.time()
         # ---- sampler / run settings (core.py:2603-2649)
         skw = dict(sampler_kwargs)
@@ -1151,45 +1193,26 @@ class SurrogateModel(object):
         if set(rkw) - allowed:
             raise TypeError(f"run_dynesty: unsupported run_kwargs {sorted(set(rkw) - allowed)}")
         # ---- likelihood, prior transform and the plan: fused walks, or the host evaluates like_fn(prior_transform(u))
-        plan, gp_obj, y_obj = self._nested_setup(like_fn, prior_transform, prior_transform_comment)
+        setup = self._nested_setup(like_fn, prior_transform, prior_transform_comment)
         if self.verbose:
-            print(f"Running nested sampling ({mode}, {'fused GPU walks' if plan.fused else 'host likelihood'}) with {nlive} live "
+            print(f"Running nested sampling ({mode}, {'fused GPU walks' if setup[0].fused else 'host likelihood'}) with {nlive} live "
                   "points...")
         all_logz = []
-        normal = {} if plan.normal_prior is None else {"normal_prior": plan.normal_prior}     # Gaussian prior coordinates
 
-        def run(run_number):
-            s = (self._seed() if seed is None else int(seed) + 1000003 * (run_number - 1)) + rank
-            backend = GPUWalkBackend(gp_obj, y_obj, plan.box, seed=s, to_theta=plan.to_theta, logp_affine=plan.logp_affine,
-                                     logp_map=plan.logp_map, host_loglike=plan.host_like, **normal)
-            self.dynesty_sampler = NestedSampler(backend, nlive, dynamic=(mode == "dynamic"), walks=walks, batch=batch, seed=s,
-                                                 **move)
-            checkpoint = None
-            if save_iter is not None and rank == 0:
-                pkl = os.path.join(self.savedir, f"dynesty_sampler_{self.like_fn_name}_run{run_number}.pkl")
-                checkpoint = PickleCheckpoint(self.dynesty_sampler, pkl, save_iter)
-            res = self.dynesty_sampler.run_nested(checkpoint=checkpoint, **rkw)
-            if checkpoint is not None:
-                checkpoint.write(res)
-            backend.close()
-            self.dynesty_results, self.dynesty_logz_err, self.dynesty_path = res, float(res.logzerr[-1]), backend.path
+        def collect(res, eq):                        # the reference keeps the largest log evidence of the runs
             all_logz.append(float(res.logz[-1]))
-            return res.samples_equal(np.random.default_rng(s))
+            self.dynesty_logz, self.dynesty_logz_err = max(all_logz), float(res.logzerr[-1])
 
-        note = (lambda total: f", logZ = {all_logz[-1]:.3f}") if self.verbose else None
-        self.dynesty_samples = post.run_until_min_ess(run, min_ess, note)
-        self.dynesty_logz = max(all_logz)            # the reference keeps the largest log evidence of the runs
-        if self.like_fn_name == "true":
-            self.dynesty_samples_true = self.dynesty_samples
-        elif self.like_fn_name == "surrogate":
-            self.dynesty_samples_surrogate = self.dynesty_samples
-        self.dynesty_run = True
-        self.dynesty_runtime = time.time() - dynesty_t0
-        if rank != 0:
-            return                                   # files are rank 0's
-        fname = self._write_samples("dynesty", self.dynesty_samples, samples_file)
-        if self.verbose:
-            print(f"Saved dynesty samples to {fname}")
+        def checkpoint(sampler, run_number):
+            if save_iter is not None:
+                pkl = os.path.join(self.savedir, f"dynesty_sampler_{self.like_fn_name}_run{run_number}.pkl")
+                return PickleCheckpoint(sampler, pkl, save_iter)
+
+        self._nested_runs("dynesty", "dynesty", setup, seed,
+                          lambda backend, s: NestedSampler(backend, nlive, dynamic=(mode == "dynamic"), walks=walks, batch=batch,
+                                                           seed=s, **move),
+                          rkw, min_ess, lambda total: f", logZ = {all_logz[-1]:.3f}", collect, dynesty_t0, samples_file,
+                          custom_is_surrogate=False, checkpoint=checkpoint)
 
     _PYMULTINEST_DEFAULTS = {"n_live_points": 1000, "evidence_tolerance": 0.5, "sampling_efficiency": 0.8,
                              "n_iter_before_update": 100, "null_log_evidence": -1e90, "max_modes": 100, "mode_tolerance": -1e90,
@@ -1217,9 +1240,7 @@ class SurrogateModel(object):
         (a ``UserWarning`` says so).  Runs repeat until ``min_ess`` samples exist (at most 10) and are combined as the reference
         does: log Z averaged with sample-count weights, its error the root of the weighted mean square.  Under
         ``torch.distributed`` every rank runs its own sampler (seed + rank) and rank 0 writes the file."""
-        from . import dist as adist
-        from .nested import GPUWalkBackend, NestedSampler
-        rank, world = adist.world_info()
+        from .nested import NestedSampler
         skw = dict(self._PYMULTINEST_DEFAULTS)
         unknown = set(sampler_kwargs) - set(skw)
         if unknown:
@@ -1238,45 +1259,26 @@ class SurrogateModel(object):
         seed = None if int(skw["seed"]) < 0 else int(skw["seed"])
         maxiter = None if int(skw["max_iter"]) <= 0 else int(skw["max_iter"])
         t0 = time.time()
-        plan, gp_obj, y_obj = self._nested_setup(like_fn, prior_transform, prior_transform_comment)
+        setup = self._nested_setup(like_fn, prior_transform, prior_transform_comment)
         if self.verbose:
-            print(f"Running ellipsoidal nested sampling ({'fused GPU draws' if plan.fused else 'host likelihood'}) with {nlive} "
+            print(f"Running ellipsoidal nested sampling ({'fused GPU draws' if setup[0].fused else 'host likelihood'}) with {nlive} "
                   "live points...")
-        normal = {} if plan.normal_prior is None else {"normal_prior": plan.normal_prior}
         logz, logz_err, counts = [], [], []
-
-        def run(run_number):
-            s = (self._seed() if seed is None else seed + 1000003 * (run_number - 1)) + rank
-            backend = GPUWalkBackend(gp_obj, y_obj, plan.box, seed=s, to_theta=plan.to_theta, logp_affine=plan.logp_affine,
-                                     logp_map=plan.logp_map, host_loglike=plan.host_like, **normal)
-            self.pymultinest_sampler = NestedSampler(backend, nlive, dynamic=False, batch=skw["batch"], seed=s, sample="unif",
-                                                     bound=bound, enlarge=1.0 / eff, max_ellipsoids=max_ell)
-            res = self.pymultinest_sampler.run_nested(dlogz=float(skw["evidence_tolerance"]), maxiter=maxiter)
-            backend.close()
-            self.pymultinest_results, self.pymultinest_path = res, backend.path
-            eq = res.samples_equal(np.random.default_rng(s))
-            logz.append(float(res.logz[-1])); logz_err.append(float(res.logzerr[-1])); counts.append(eq.shape[0])
-            return eq
-
-        note = (lambda total: f", logZ = {logz[-1]:.3f} +/- {logz_err[-1]:.3f}") if self.verbose else None
-        self.pymultinest_samples = post.run_until_min_ess(run, min_ess, note)
-        self.pymultinest_weights = np.ones(self.pymultinest_samples.shape[0])
-        w = np.asarray(counts, dtype=np.float64) / float(np.sum(counts))          # core.py:3175-3190
-        self.pymultinest_logz = float(np.average(logz, weights=w))
-        self.pymultinest_logz_err = float(np.sqrt(np.average(np.square(logz_err), weights=w)))
         self.pymultinest_analyzer = None
-        if self.like_fn_name == "true":
-            self.pymultinest_samples_true = self.pymultinest_samples
-        else:
-            self.pymultinest_samples_surrogate = self.pymultinest_samples
-        self.pymultinest_run = True
-        self.pymultinest_runtime = time.time() - t0
-        if rank != 0:
-            return                                   # files are rank 0's
-        fname = self._write_samples("pymultinest", self.pymultinest_samples, samples_file, weights=self.pymultinest_weights,
-                                    logz=self.pymultinest_logz, logz_err=self.pymultinest_logz_err)
-        if self.verbose:
-            print(f"Saved PyMultiNest samples to {fname}")
+
+        def collect(res, eq):                        # core.py:3175-3190: log Z averaged with sample-count weights
+            logz.append(float(res.logz[-1])); logz_err.append(float(res.logzerr[-1])); counts.append(eq.shape[0])
+            w = np.asarray(counts, dtype=np.float64) / float(np.sum(counts))
+            self.pymultinest_weights = np.ones(int(np.sum(counts)))
+            self.pymultinest_logz = float(np.average(logz, weights=w))
+            self.pymultinest_logz_err = float(np.sqrt(np.average(np.square(logz_err), weights=w)))
+
+        self._nested_runs("pymultinest", "PyMultiNest", setup, seed,
+                          lambda backend, s: NestedSampler(backend, nlive, dynamic=False, batch=skw["batch"], seed=s, sample="unif",
+                                                           bound=bound, enlarge=1.0 / eff, max_ellipsoids=max_ell),
+                          {"dlogz": float(skw["evidence_tolerance"]), "maxiter": maxiter}, min_ess,
+                          lambda total: f", logZ = {logz[-1]:.3f} +/- {logz_err[-1]:.3f}", collect, t0, samples_file,
+                          file_fields=("weights", "logz", "logz_err"))
 
     # the reference's defaults (core.py:3490-3522); the keys without an entry in the docstring are accepted and have no effect
     _ULTRANEST_SAMPLER_DEFAULTS = {"derived_param_names": [], "wrapped_params": None, "num_test_samples": 2, "draw_multiple": True,
@@ -1313,9 +1315,7 @@ class SurrogateModel(object):
         exist (at most 10) and are combined as the reference does: samples stacked, each run's weights 1 / (its sample count), log Z
         and its error those of the run with the largest log Z.  Under ``torch.distributed`` every rank runs its own sampler
         (seed + rank) and rank 0 writes the file."""
-        from . import dist as adist
-        from .nested import GPUWalkBackend, NestedSampler
-        rank, world = adist.world_info()
+        from .nested import NestedSampler
         skw, rkw = dict(self._ULTRANEST_SAMPLER_DEFAULTS), dict(self._ULTRANEST_RUN_DEFAULTS)
         for name, given, known in (("sampler_kwargs", sampler_kwargs, skw), ("run_kwargs", run_kwargs, rkw)):
             if set(given) - set(known):
@@ -1343,40 +1343,20 @@ class SurrogateModel(object):
         if dynamic:
             run_args.update(dlogz_init=dlogz, maxbatch=maxbatch, n_effective=rkw["min_ess"])
         t0 = time.time()
-        plan, gp_obj, y_obj = self._nested_setup(like_fn, prior_transform, prior_transform_comment)
+        setup = self._nested_setup(like_fn, prior_transform, prior_transform_comment)
         if self.verbose:
-            print(f"Running MLFriends nested sampling ({'fused GPU draws' if plan.fused else 'host likelihood'}) with {nlive} "
+            print(f"Running MLFriends nested sampling ({'fused GPU draws' if setup[0].fused else 'host likelihood'}) with {nlive} "
                   "live points...")
-        normal = {} if plan.normal_prior is None else {"normal_prior": plan.normal_prior}
         logz, logz_err, weights = [], [], []
 
-        def run(run_number):
-            s = (self._seed() if seed is None else seed + 1000003 * (run_number - 1)) + rank
-            backend = GPUWalkBackend(gp_obj, y_obj, plan.box, seed=s, to_theta=plan.to_theta, logp_affine=plan.logp_affine,
-                                     logp_map=plan.logp_map, host_loglike=plan.host_like, **normal)
-            self.ultranest_sampler = NestedSampler(backend, nlive, dynamic=dynamic, batch=skw["batch"], seed=s, **move)
-            res = self.ultranest_sampler.run_nested(**run_args)
-            backend.close()
-            self.ultranest_results, self.ultranest_path = res, backend.path
-            eq = res.samples_equal(np.random.default_rng(s))
+        def collect(res, eq):                        # core.py:3629-3642: the run with the highest log evidence
             logz.append(float(res.logz[-1])); logz_err.append(float(res.logzerr[-1]))
             weights.append(np.full(eq.shape[0], 1.0 / eq.shape[0]))
-            return eq
+            best = int(np.argmax(logz))
+            self.ultranest_weights = np.concatenate(weights)
+            self.ultranest_logz, self.ultranest_logz_err = logz[best], logz_err[best]
 
-        note = (lambda total: f", logZ = {logz[-1]:.3f} +/- {logz_err[-1]:.3f}") if self.verbose else None
-        self.ultranest_samples = post.run_until_min_ess(run, min_ess, note)
-        self.ultranest_weights = np.concatenate(weights)
-        best = int(np.argmax(logz))                  # core.py:3629-3642: the run with the highest log evidence
-        self.ultranest_logz, self.ultranest_logz_err = logz[best], logz_err[best]
-        if self.like_fn_name == "true":
-            self.ultranest_samples_true = self.ultranest_samples
-        else:
-            self.ultranest_samples_surrogate = self.ultranest_samples
-        self.ultranest_run = True
-        self.ultranest_runtime = time.time() - t0
-        if rank != 0:
-            return                                   # files are rank 0's
-        fname = self._write_samples("ultranest", self.ultranest_samples, samples_file, weights=self.ultranest_weights,
-                                    logz=self.ultranest_logz, logz_err=self.ultranest_logz_err)
-        if self.verbose:
-            print(f"Saved UltraNest samples to {fname}")
+        self._nested_runs("ultranest", "UltraNest", setup, seed,
+                          lambda backend, s: NestedSampler(backend, nlive, dynamic=dynamic, batch=skw["batch"], seed=s, **move),
+                          run_args, min_ess, lambda total: f", logZ = {logz[-1]:.3f} +/- {logz_err[-1]:.3f}", collect, t0,
+                          samples_file, file_fields=("weights", "logz", "logz_err"))

@@ -46,6 +46,8 @@
 //   ns_propose_kernel           the proposal of one step of every walk (host-callable likelihoods): the same draws and the same
 //                               arithmetic as the fused walk (shared functions below), so both paths move identically.
 //   ns_accept_kernel            the accept test of one step, given the host's logL of the proposals.
+// alabi_ns_walk and alabi_ns_slice check their own arguments and share ns_walk_launch (below); ns_dispatch, ns_point_args and the
+// ns_load_chol of the one-wave kernels are in ns_device.hpp.
 //
 // Draws.  Everything is keyed by (seed, call, global walk id, step): counter (c0, c1, c2, c3) = ((uint32) call, walk id, step,
 // j), key = (low, high 32 bits of seed).  Normals: pair j (coordinates 2j, 2j+1) from one Philox block r[0..3]:
@@ -239,10 +241,7 @@ ns_slice_step_kernel(unsigned long long seed, long long call, int walk_id0, int 
     char* base = state + (size_t)b * ns_slice_stride(d);
     NsSliceState* g = reinterpret_cast<NsSliceState*>(base);
     double* v = reinterpret_cast<double*>(base + sizeof(NsSliceState));
-    for (int i = tid; i < d * d; i += 64) {
-        const int r = i / d, c = i % d;
-        C_s[r * ALABI_MAX_DIM + c] = c <= r ? chol[i] : 0.0;
-    }
+    ns_load_chol(C_s, ALABI_MAX_DIM, chol, d);
     if (tid < d) { u_s[tid] = v[tid]; a_s[tid] = v[d + tid]; q_s[tid] = v[2 * d + tid]; }
     if (tid == 0) st_s = *g;
     __syncthreads();
@@ -367,10 +366,7 @@ ns_propose_kernel(unsigned long long seed, long long call, int walk_id0, int d, 
     __shared__ double C_s[ALABI_MAX_DIM * ALABI_MAX_DIM];
     __shared__ double z_s[ALABI_MAX_DIM];
     const int tid = threadIdx.x, b = blockIdx.x;
-    for (int i = tid; i < d * d; i += 64) {
-        const int r = i / d, c = i % d;
-        C_s[r * ALABI_MAX_DIM + c] = c <= r ? chol[i] : 0.0;
-    }
+    ns_load_chol(C_s, ALABI_MAX_DIM, chol, d);
     ns_draw_normals(seed, call, (uint32_t)(walk_id0 + b), (uint32_t)step, d, tid, z_s);
     __syncthreads();
     if (tid < d) u_prop[(size_t)b * d + tid] = ns_prop_coord(C_s, ALABI_MAX_DIM, z_s, tid, u_cur[(size_t)b * d + tid], scale);
@@ -399,6 +395,19 @@ ns_accept_kernel(int K, int d, const double* __restrict__ u_prop, const double* 
 
 using namespace alabi;
 
+// The launch of alabi_ns_walk and alabi_ns_slice after their argument checks: K workgroups of the kernel pick(inst).  walks: steps
+// or slices (NsArgs::walks and n_acc serve both kernels).
+template <class Pick>
+static int ns_walk_launch(alabi_ns* ns, long long call, int walk_id0, const double* u0, const double* logl0, int K, double logl_star,
+                          const double* chol, double scale, int walks, double* u_out, double* logl_out, int* n_acc, void* stream,
+                          Pick pick) {
+    const hipStream_t s = ns_stream(stream);
+    NsArgs a{};
+    { const int st = ns_point_args(ns, call, s, a); if (st != ALABI_OK) return st; }
+    a.u0 = u0; a.logl0 = logl0; a.chol = chol; a.u_out = u_out; a.logl_out = logl_out; a.n_acc = n_acc;
+    a.walk_id0 = walk_id0; a.K = K; a.walks = walks; a.logl_star = logl_star; a.scale = scale;
+    return ns_dispatch(ns, pick, K, s, a);
+}
 
 extern "C" {
 
@@ -470,26 +479,8 @@ int alabi_ns_walk(alabi_ns* ns, long long call, int walk_id0, const double* u0, 
     if ((long long)walk_id0 + K > 0xFFFFFFFFLL) return ALABI_BAD_ARGUMENT;
     if (K == 0) return ALABI_OK;
     if (!u0 || !u_out || !logl_out || (walks > 0 && (!chol || !(scale > 0.0) || !std::isfinite(scale)))) return ALABI_BAD_ARGUMENT;
-    alabi_gp* gp = ns->gp;
-    if (!gp->computed || !gp->has_alpha) return ALABI_NOT_COMPUTED;
-    const hipStream_t s = ns_stream(stream);
-    const bool se = gp->kf.type == 0;
-    if (se) { const int st = ens_se_prepare(gp, s); if (st != ALABI_OK) return st; }
-    NsArgs a{};
-    a.Xsrc = se ? gp->Xc : gp->Xt; a.Asrc = se ? gp->ens_h : gp->alpha; a.centre = gp->xa_centre;
-    a.Npad = gp->Npad; a.kf = gp->kf;
-    a.amp = ns->lp_scale * std::exp(gp->log_amp); a.mean = std::fma(ns->lp_scale, gp->mean, ns->lp_shift); a.ymap = ns->ymap;
-    a.lo = ns->lo; a.width = ns->width; a.inv_len = gp->inv_len; a.nmask = ns->nmask;
-    a.u0 = u0; a.logl0 = logl0; a.chol = chol; a.u_out = u_out; a.logl_out = logl_out; a.n_acc = n_accept;
-    a.seed = ns->seed; a.call = call; a.walk_id0 = walk_id0; a.K = K; a.d = ns->d; a.walks = walks;
-    a.logl_star = logl_star; a.scale = scale;
-    const int db = dim_bucket(ns->d), T = ns_threads(gp, db);
-    ns->last_path = (gp->Npad / 2 <= T) ? 1 : 2;
-    const bool tiled = ns->last_path == 2;
-    ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type, NS_DISPATCH_FLAGS(tiled, a.nmask != 0,
-        hipLaunchKernelGGL((ns_walk_kernel<D, GENERIC, ns_tmax(D), TILED, NORMAL>), dim3(K), dim3(T), 0, s, a))));
-    ALABI_LAUNCH_CHECK();
-    return ALABI_OK;
+    return ns_walk_launch(ns, call, walk_id0, u0, logl0, K, logl_star, chol, scale, walks, u_out, logl_out, n_accept, stream,
+                          [](auto inst) { return NS_KERNEL(ns_walk_kernel, inst); });
 }
 
 int alabi_ns_slice(alabi_ns* ns, long long call, int walk_id0, const double* u0, const double* logl0, int K, double logl_star,
@@ -498,26 +489,8 @@ int alabi_ns_slice(alabi_ns* ns, long long call, int walk_id0, const double* u0,
     if ((long long)walk_id0 + K > 0xFFFFFFFFLL) return ALABI_BAD_ARGUMENT;
     if (K == 0) return ALABI_OK;
     if (!u0 || !logl0 || !u_out || !logl_out || (slices > 0 && (!chol || !(scale > 0.0) || !std::isfinite(scale)))) return ALABI_BAD_ARGUMENT;
-    alabi_gp* gp = ns->gp;
-    if (!gp->computed || !gp->has_alpha) return ALABI_NOT_COMPUTED;
-    const hipStream_t s = ns_stream(stream);
-    const bool se = gp->kf.type == 0;
-    if (se) { const int st = ens_se_prepare(gp, s); if (st != ALABI_OK) return st; }
-    NsArgs a{};
-    a.Xsrc = se ? gp->Xc : gp->Xt; a.Asrc = se ? gp->ens_h : gp->alpha; a.centre = gp->xa_centre;
-    a.Npad = gp->Npad; a.kf = gp->kf;
-    a.amp = ns->lp_scale * std::exp(gp->log_amp); a.mean = std::fma(ns->lp_scale, gp->mean, ns->lp_shift); a.ymap = ns->ymap;
-    a.lo = ns->lo; a.width = ns->width; a.inv_len = gp->inv_len; a.nmask = ns->nmask;
-    a.u0 = u0; a.logl0 = logl0; a.chol = chol; a.u_out = u_out; a.logl_out = logl_out; a.n_acc = counts;
-    a.seed = ns->seed; a.call = call; a.walk_id0 = walk_id0; a.K = K; a.d = ns->d; a.walks = slices;
-    a.logl_star = logl_star; a.scale = scale;
-    const int db = dim_bucket(ns->d), T = ns_threads(gp, db);
-    ns->last_path = (gp->Npad / 2 <= T) ? 1 : 2;
-    const bool tiled = ns->last_path == 2;
-    ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type, NS_DISPATCH_FLAGS(tiled, a.nmask != 0,
-        hipLaunchKernelGGL((ns_slice_kernel<D, GENERIC, ns_tmax(D), TILED, NORMAL>), dim3(K), dim3(T), 0, s, a))));
-    ALABI_LAUNCH_CHECK();
-    return ALABI_OK;
+    return ns_walk_launch(ns, call, walk_id0, u0, logl0, K, logl_star, chol, scale, slices, u_out, logl_out, counts, stream,
+                          [](auto inst) { return NS_KERNEL(ns_slice_kernel, inst); });
 }
 
 int alabi_ns_slice_state_bytes(alabi_ns* ns, int K, long long* bytes) {

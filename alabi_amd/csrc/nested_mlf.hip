@@ -28,6 +28,7 @@
 //                               test costs n d fused multiply-adds per surviving candidate and saves the N d of a GP mean for each
 //                               one it rejects.
 //   ns_mlf_geom_kernel          the same up to the neighbour test for a host likelihood (evaluate = 0): 64 lanes, no training set.
+// alabi_ns_mlf_draw checks the region's arguments and then takes the launch path of alabi_ns_unif_draw (ns_draw_launch, ns_device.hpp).
 #include "ns_device.hpp"
 
 namespace alabi {
@@ -170,35 +171,12 @@ int alabi_ns_mlf_radius(alabi_ns* ns, long long call, int n, const double* w, in
 int alabi_ns_mlf_draw(alabi_ns* ns, long long call, int cand_id0, int M, int evaluate, int E, const double* centres,
                       const double* axes, const double* inv_axes, const double* cum, int n, const double* w,
                       const double* metric_inv, double r2, double* cand_u, double* cand_logl, int* cand_status, void* stream) {
-    if (!ns || M < 0 || cand_id0 < 0 || call < 0 || E < 1 || E > ALABI_NS_MAX_ELLIPSOIDS) return ALABI_BAD_ARGUMENT;
-    if ((long long)cand_id0 + M > 0xFFFFFFFFLL) return ALABI_BAD_ARGUMENT;
-    if (!centres || !axes || !inv_axes || !cum || !w || !metric_inv) return ALABI_BAD_ARGUMENT;
-    if (n < 1 || n > ALABI_NS_MLF_MAX_POINTS || !(r2 >= 0.0)) return ALABI_BAD_ARGUMENT;     // a NaN r2 fails the comparison
-    if (M == 0) return ALABI_OK;
-    if (!cand_u || !cand_logl || !cand_status) return ALABI_BAD_ARGUMENT;
-    const hipStream_t s = ns_stream(stream);
-    NsUnifArgs q{};
-    q.centres = centres; q.axes = axes; q.inv_axes = inv_axes; q.cum = cum;
-    q.cand_u = cand_u; q.cand_logl = cand_logl; q.cand_status = cand_status;
-    q.seed = ns->seed; q.call = call; q.E = E; q.M = M; q.cand_id0 = cand_id0; q.d = ns->d;
+    // like every other bad argument of the draw, before its M == 0 return; a NaN r2 fails the comparison
+    if (!w || !metric_inv || n < 1 || n > ALABI_NS_MLF_MAX_POINTS || !(r2 >= 0.0)) return ALABI_BAD_ARGUMENT;
     NsMlfArgs m{};
     m.w = w; m.metric_inv = metric_inv; m.r2 = r2; m.n = n;
-    if (!evaluate) {
-        hipLaunchKernelGGL(ns_mlf_geom_kernel, dim3(M < 65536 ? M : 65536), dim3(64), 0, s, q, m);
-        ALABI_LAUNCH_CHECK();
-        return ALABI_OK;
-    }
-    alabi_gp* gp = ns->gp;
-    NsArgs a{};
-    { const int st = ns_point_args(ns, call, s, a); if (st != ALABI_OK) return st; }
-    const int db = dim_bucket(ns->d), T = ns_threads(gp, db);
-    ns->last_path = (gp->Npad / 2 <= T) ? 1 : 2;
-    const bool tiled = ns->last_path == 2;
-    const int grid = M < 1024 ? M : 1024;                    // as ns_unif_draw_kernel: a workgroup keeps its training-set share
-    ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type, NS_DISPATCH_FLAGS(tiled, a.nmask != 0,
-        hipLaunchKernelGGL((ns_mlf_draw_kernel<D, GENERIC, ns_tmax(D), TILED, NORMAL>), dim3(grid), dim3(T), 0, s, a, q, m))));
-    ALABI_LAUNCH_CHECK();
-    return ALABI_OK;
+    return ns_draw_launch(ns, call, cand_id0, M, evaluate, E, centres, axes, inv_axes, cum, cand_u, cand_logl, cand_status, stream,
+                          ns_mlf_geom_kernel, [](auto inst) { return NS_KERNEL(ns_mlf_draw_kernel, inst); }, m);
 }
 
 }  // extern "C"

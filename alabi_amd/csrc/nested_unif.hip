@@ -35,6 +35,7 @@
 //                               order, to u_out / logl_out; counts[5] = taken, consumed (index after the last taken candidate when
 //                               `need` were found, else M), and the evaluated / outside / thinned candidates among the consumed.
 //                               Plain vector stores, no atomics: the order is the semantics.
+// alabi_ns_unif_draw is ns_draw_launch (ns_device.hpp), the launch path it shares with alabi_ns_mlf_draw.
 #include "ns_device.hpp"
 
 namespace alabi {
@@ -149,33 +150,8 @@ extern "C" {
 int alabi_ns_unif_draw(alabi_ns* ns, long long call, int cand_id0, int M, int evaluate, int E, const double* centres,
                        const double* axes, const double* inv_axes, const double* cum, double* cand_u, double* cand_logl,
                        int* cand_status, void* stream) {
-    if (!ns || M < 0 || cand_id0 < 0 || call < 0 || E < 1 || E > ALABI_NS_MAX_ELLIPSOIDS) return ALABI_BAD_ARGUMENT;
-    if ((long long)cand_id0 + M > 0xFFFFFFFFLL) return ALABI_BAD_ARGUMENT;
-    if (!centres || !axes || !inv_axes || !cum) return ALABI_BAD_ARGUMENT;
-    if (M == 0) return ALABI_OK;
-    if (!cand_u || !cand_logl || !cand_status) return ALABI_BAD_ARGUMENT;
-    const hipStream_t s = ns_stream(stream);
-    NsUnifArgs q{};
-    q.centres = centres; q.axes = axes; q.inv_axes = inv_axes; q.cum = cum;
-    q.cand_u = cand_u; q.cand_logl = cand_logl; q.cand_status = cand_status;
-    q.seed = ns->seed; q.call = call; q.E = E; q.M = M; q.cand_id0 = cand_id0; q.d = ns->d;
-    if (!evaluate) {
-        hipLaunchKernelGGL(ns_unif_geom_kernel, dim3(M < 65536 ? M : 65536), dim3(64), 0, s, q);
-        ALABI_LAUNCH_CHECK();
-        return ALABI_OK;
-    }
-    alabi_gp* gp = ns->gp;
-    NsArgs a{};
-    { const int st = ns_point_args(ns, call, s, a); if (st != ALABI_OK) return st; }
-    const int db = dim_bucket(ns->d), T = ns_threads(gp, db);
-    ns->last_path = (gp->Npad / 2 <= T) ? 1 : 2;
-    const bool tiled = ns->last_path == 2;
-    // a workgroup keeps its training-set share for all its candidates: no more workgroups than the device holds at once needs
-    const int grid = M < 1024 ? M : 1024;
-    ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type, NS_DISPATCH_FLAGS(tiled, a.nmask != 0,
-        hipLaunchKernelGGL((ns_unif_draw_kernel<D, GENERIC, ns_tmax(D), TILED, NORMAL>), dim3(grid), dim3(T), 0, s, a, q))));
-    ALABI_LAUNCH_CHECK();
-    return ALABI_OK;
+    return ns_draw_launch(ns, call, cand_id0, M, evaluate, E, centres, axes, inv_axes, cum, cand_u, cand_logl, cand_status, stream,
+                          ns_unif_geom_kernel, [](auto inst) { return NS_KERNEL(ns_unif_draw_kernel, inst); });
 }
 
 int alabi_ns_unif_select(alabi_ns* ns, int M, const double* cand_u, const double* cand_logl, const int* cand_status,

@@ -1,8 +1,10 @@
-// Device code shared by the nested-sampling kernels (nested.hip: the random walk and the slice move; nested_unif.hip: uniform draws
-// inside bounding ellipsoids; nested_mlf.hip: the MLFriends region over them): the sampler handle, the kernel arguments, the Philox
-// normals, the inverse normal CDF, the prior transform, the GP mean at one point (ns_logl) and the ellipsoid candidate
-// (ns_unif_candidate), plus the block-size rule and the flag dispatch of the templated kernels.
-// The draw layout (which Philox counter feeds which draw) is stated in nested.hip.
+// Code shared by the nested-sampling translation units (nested.hip: the random walk and the slice move; nested_unif.hip: uniform
+// draws inside bounding ellipsoids; nested_mlf.hip: the MLFriends region over them).  Device: the sampler handle, the kernel
+// arguments, the Philox normals, the Cholesky factor of the one-wave kernels (ns_load_chol), the inverse normal CDF, the prior
+// transform, the GP mean at one point (ns_logl) and the ellipsoid candidate (ns_unif_candidate).  Host: the block-size rule, the
+// dispatch of the four templated kernels (ns_dispatch), the GP part of NsArgs (ns_point_args) and the launch path of both draw
+// entries (ns_draw_launch).  The templated kernels keep their bodies, share load and D x D Cholesky load included, in their own
+// files: NOTES.md "Nested sampling".  The draw layout (which Philox counter feeds which draw) is stated in nested.hip.
 #pragma once
 #include <cmath>
 #include "ens_device.hpp"
@@ -73,6 +75,15 @@ __device__ inline double ns_prop_coord(const double* C, int ldc, const double* z
     double acc = 0.0;
     for (int i = 0; i <= k; ++i) acc = fma(C[(size_t)k * ldc + i], z[i], acc);
     return u + scale * acc;
+}
+
+// The 64 lanes of a one-wave workgroup: the lower triangle of the Cholesky factor chol [d, d] into C_s with row stride ldc, zero above
+// the diagonal (a barrier must follow).  Only the [d, d] block is written, which is all that ns_prop_coord and ns_slice_advance read.
+__device__ __forceinline__ void ns_load_chol(double* C_s, int ldc, const double* chol, int d) {
+    for (int i = threadIdx.x; i < d * d; i += 64) {
+        const int r = i / d, c = i % d;
+        C_s[r * ldc + c] = c <= r ? chol[i] : 0.0;
+    }
 }
 
 // AS 241 PPND16: numerator, denominator (constant term 1 first) for |p - 1/2| <= 0.425 in r = 0.180625 - (p - 1/2)^2; for
@@ -278,6 +289,27 @@ static inline int ns_threads(const alabi_gp* gp, int db) {
     return T < cap ? T : cap;
 }
 
+// The template arguments of one instantiation of the four templated kernels as a value that a generic lambda can take;
+// NS_KERNEL(kernel, inst) names that instantiation of `kernel`.
+template <int D_, bool GENERIC_, bool TILED_, bool NORMAL_>
+struct NsInst { static constexpr int D = D_; static constexpr bool GENERIC = GENERIC_, TILED = TILED_, NORMAL = NORMAL_; };
+#define NS_KERNEL(KERNEL, INST) \
+    KERNEL<decltype(INST)::D, decltype(INST)::GENERIC, ns_tmax(decltype(INST)::D), decltype(INST)::TILED, decltype(INST)::NORMAL>
+
+// Launches pick(inst)(args...) on `grid` workgroups: the instantiation and block size that fit this handle (dimension bucket, kernel
+// family, register-resident or tiled training set, normal-prior mask); records the path in last_path.
+template <class Pick, class... Args>
+static int ns_dispatch(alabi_ns* ns, Pick pick, int grid, hipStream_t s, const Args&... args) {
+    const alabi_gp* gp = ns->gp;
+    const int db = alabi::dim_bucket(ns->d), T = ns_threads(gp, db);
+    ns->last_path = (gp->Npad / 2 <= T) ? 1 : 2;
+    const bool tiled = ns->last_path == 2;
+    ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type, NS_DISPATCH_FLAGS(tiled, ns->nmask != 0,
+        hipLaunchKernelGGL(pick(NsInst<D, GENERIC, TILED, NORMAL>()), dim3(grid), dim3(T), 0, s, args...))));
+    ALABI_LAUNCH_CHECK();
+    return ALABI_OK;
+}
+
 // The NsArgs of a kernel that evaluates logL at single points (no walk): the GP's training set in the layout of its kernel family,
 // the affine map of the log-probability and the prior transform.  ALABI_NOT_COMPUTED without a factorised GP with alpha.
 static inline int ns_point_args(alabi_ns* ns, long long call, hipStream_t s, alabi::NsArgs& a) {
@@ -291,4 +323,32 @@ static inline int ns_point_args(alabi_ns* ns, long long call, hipStream_t s, ala
     a.lo = ns->lo; a.width = ns->width; a.inv_len = gp->inv_len; a.nmask = ns->nmask;
     a.seed = ns->seed; a.call = call; a.d = ns->d;
     return ALABI_OK;
+}
+
+// alabi_ns_unif_draw and, after its own checks of the region, alabi_ns_mlf_draw.  geom: the 64-lane kernel of a host likelihood
+// (evaluate = 0); pick(inst): the fused kernel; region: the move's further kernel arguments (none, or the NsMlfArgs).
+template <class Geom, class Pick, class... Region>
+static int ns_draw_launch(alabi_ns* ns, long long call, int cand_id0, int M, int evaluate, int E, const double* centres,
+                          const double* axes, const double* inv_axes, const double* cum, double* cand_u, double* cand_logl,
+                          int* cand_status, void* stream, Geom geom, Pick pick, const Region&... region) {
+    using namespace alabi;
+    if (!ns || M < 0 || cand_id0 < 0 || call < 0 || E < 1 || E > ALABI_NS_MAX_ELLIPSOIDS) return ALABI_BAD_ARGUMENT;
+    if ((long long)cand_id0 + M > 0xFFFFFFFFLL) return ALABI_BAD_ARGUMENT;
+    if (!centres || !axes || !inv_axes || !cum) return ALABI_BAD_ARGUMENT;
+    if (M == 0) return ALABI_OK;
+    if (!cand_u || !cand_logl || !cand_status) return ALABI_BAD_ARGUMENT;
+    const hipStream_t s = ns_stream(stream);
+    NsUnifArgs q{};
+    q.centres = centres; q.axes = axes; q.inv_axes = inv_axes; q.cum = cum;
+    q.cand_u = cand_u; q.cand_logl = cand_logl; q.cand_status = cand_status;
+    q.seed = ns->seed; q.call = call; q.E = E; q.M = M; q.cand_id0 = cand_id0; q.d = ns->d;
+    if (!evaluate) {
+        hipLaunchKernelGGL(geom, dim3(M < 65536 ? M : 65536), dim3(64), 0, s, q, region...);
+        ALABI_LAUNCH_CHECK();
+        return ALABI_OK;
+    }
+    NsArgs a{};
+    { const int st = ns_point_args(ns, call, s, a); if (st != ALABI_OK) return st; }
+    // a workgroup keeps its training-set share for all its candidates: no more workgroups than the device holds at once needs
+    return ns_dispatch(ns, pick, M < 1024 ? M : 1024, s, a, q, region...);
 }

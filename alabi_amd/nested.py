@@ -714,12 +714,14 @@ class GPUWalkBackend:
             lh = logl.cpu().numpy()
         return uh, lh
 
+    def _upload(self, u0, logl0, chol):
+        """Device copies (u, logl, chol, K) of K start points; the walk and the slice kernels update u and logl in place."""
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=_dev())  # noqa: E731
+        return up(u0).clone(), up(logl0).clone(), up(chol), int(np.asarray(u0).shape[0])
+
     def walk(self, call, u0, logl0, logl_star, chol, scale, walks, walk_id0=0):
         ns, lib, dev, stream = self._ensure(), _lib.lib(), _dev(), _lib.current_stream()
-        K = int(np.asarray(u0).shape[0])
-        u = torch.as_tensor(np.ascontiguousarray(u0, dtype=np.float64), device=dev).clone()
-        logl = torch.as_tensor(np.ascontiguousarray(logl0, dtype=np.float64), device=dev).clone()
-        ch = torch.as_tensor(np.ascontiguousarray(chol, dtype=np.float64), device=dev)
+        u, logl, ch, K = self._upload(u0, logl0, chol)
         nacc = torch.zeros(2 * K, dtype=torch.int32, device=dev)
         if self.host_loglike is None:
             _lib.check(lib.alabi_ns_walk(ns, int(call), int(walk_id0), _lib.ptr(u), _lib.ptr(logl), K, float(logl_star),
@@ -740,10 +742,7 @@ class GPUWalkBackend:
         """``slices`` random-direction slice updates of every walk: (u, logl, n_eval, n_expand, n_contract, n_capped), the
         last four per walk (in-cube likelihood evaluations, expansions, contractions, slices that hit the contraction cap)."""
         ns, lib, dev, stream = self._ensure(), _lib.lib(), _dev(), _lib.current_stream()
-        K = int(np.asarray(u0).shape[0])
-        u = torch.as_tensor(np.ascontiguousarray(u0, dtype=np.float64), device=dev).clone()
-        logl = torch.as_tensor(np.ascontiguousarray(logl0, dtype=np.float64), device=dev).clone()
-        ch = torch.as_tensor(np.ascontiguousarray(chol, dtype=np.float64), device=dev)
+        u, logl, ch, K = self._upload(u0, logl0, chol)
         counts = torch.zeros(4 * K, dtype=torch.int32, device=dev)
         if self.host_loglike is None:
             _lib.check(lib.alabi_ns_slice(ns, int(call), int(walk_id0), _lib.ptr(u), _lib.ptr(logl), K, float(logl_star),

@@ -140,6 +140,52 @@ def test_split_path_replays_the_fused_draws():
     be.close()
 
 
+def test_walk_and_slice_bad_arguments_launch_nothing():
+    import torch
+    from alabi_amd import HipGP, _lib
+    from alabi_amd.gp import _dev
+    from alabi_amd.nested import GPUWalkBackend
+    N, d, K, call = 400, 4, 8, 7
+    g, o, y = _setup(N, d)
+    box = np.array([[-3.0, 3.0]] * d)
+    be = GPUWalkBackend(g, y, box, seed=5, to_theta=lambda u: u)
+    ns, dev, lib, stream = be._ensure(), _dev(), _lib.lib(), _lib.current_stream()
+    u0 = torch.as_tensor(np.random.default_rng(1).random((K, d)), device=dev)
+    l0 = torch.zeros(K, dtype=torch.float64, device=dev)
+    ch = torch.eye(d, dtype=torch.float64, device=dev)
+    uo = torch.full((K, d), -7.0, dtype=torch.float64, device=dev)
+    lo = torch.full((K,), -7.0, dtype=torch.float64, device=dev)
+    cnt = torch.full((4 * K,), -7, dtype=torch.int32, device=dev)
+    good = dict(call=call, walk_id0=0, u0=_lib.ptr(u0), logl0=_lib.ptr(l0), K=K, logl_star=-1e300, chol=_lib.ptr(ch), scale=0.5,
+                walks=3, u_out=_lib.ptr(uo), logl_out=_lib.ptr(lo), counts=_lib.ptr(cnt))
+
+    def launch(fn, handle=ns, **kw):
+        a = dict(good, **kw)
+        return fn(handle, a["call"], a["walk_id0"], a["u0"], a["logl0"], a["K"], a["logl_star"], a["chol"], a["scale"], a["walks"],
+                  a["u_out"], a["logl_out"], a["counts"], stream)
+    # walk_id0 + K > 2^32 - 1 has no case: both are C ints, so the sum is at most 2^32 - 2 and that check cannot be reached
+    bad = [dict(K=-1), dict(walks=-1), dict(walk_id0=-1), dict(call=-1), dict(logl_star=float("nan")), dict(u0=None),
+           dict(u_out=None), dict(logl_out=None), dict(chol=None), dict(scale=0.0), dict(scale=float("inf"))]
+    for fn, extra in ((lib.alabi_ns_walk, []), (lib.alabi_ns_slice, [dict(logl0=None), dict(walks=0x7FFFFFFF)])):
+        for kw in bad + extra:
+            assert launch(fn, **kw) == _lib.BAD_ARG, (fn.__name__, kw)
+    torch.cuda.synchronize()
+    assert torch.all(uo == -7.0) and torch.all(lo == -7.0) and torch.all(cnt == -7)
+    none = dict(K=0, u0=None, logl0=None, chol=None, u_out=None, logl_out=None, counts=None)
+    for fn in (lib.alabi_ns_walk, lib.alabi_ns_slice):
+        assert launch(fn, **none) == _lib.OK
+    # a GP that was never factorised: reported after the argument checks, and not at all when there is nothing to do
+    bare = GPUWalkBackend(HipGP(d), None, box, seed=5, to_theta=lambda u: u, host_loglike=lambda u: np.zeros(len(u)))
+    nb = bare._ensure()
+    for fn in (lib.alabi_ns_walk, lib.alabi_ns_slice):
+        assert launch(fn, handle=nb) == _lib.NOT_COMPUTED
+        assert launch(fn, handle=nb, u0=None) == _lib.BAD_ARG
+        assert launch(fn, handle=nb, **none) == _lib.OK
+    torch.cuda.synchronize()
+    assert torch.all(uo == -7.0) and torch.all(lo == -7.0) and torch.all(cnt == -7)
+    be.close(); bare.close()
+
+
 # ------------------------------------------------------------------------ run_dynesty
 def _gauss2(theta):
     t = np.asarray(theta, dtype=float).reshape(-1, 2)
