@@ -701,15 +701,33 @@ int alabi_ens_stream_variant(alabi_ens* e, int* variant) {
     return ALABI_OK;
 }
 
+// The pair kernel's debug counters (alabi_ens::pair_stats); counting starts with the next run
+static int pair_stats_alloc(alabi_ens* e) {
+    if (e->pair_stats) return ALABI_OK;
+    ALABI_HIP_CHECK(hipMalloc(&e->pair_stats, ALABI_PAIR_STATS_WORDS * sizeof(unsigned long long)));
+    ALABI_HIP_CHECK(hipMemset(e->pair_stats, 0, ALABI_PAIR_STATS_WORDS * sizeof(unsigned long long)));
+    return ALABI_OK;
+}
+
 int alabi_ens_pair_stats(alabi_ens* e, long long* out, int reset) {
     if (!e || !out) return ALABI_BAD_ARGUMENT;
-    if (!e->pair_stats) {                              // counting starts with the next run
-        ALABI_HIP_CHECK(hipMalloc(&e->pair_stats, 9 * sizeof(unsigned long long)));
-        ALABI_HIP_CHECK(hipMemset(e->pair_stats, 0, 9 * sizeof(unsigned long long)));
-    }
+    int st;
+    if ((st = pair_stats_alloc(e)) != ALABI_OK) return st;
     ALABI_HIP_CHECK(hipDeviceSynchronize());
     ALABI_HIP_CHECK(hipMemcpy(out, e->pair_stats, 9 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (reset) ALABI_HIP_CHECK(hipMemset(e->pair_stats, 0, 9 * sizeof(unsigned long long)));
+    return ALABI_OK;
+}
+
+int alabi_ens_pair_stats2(alabi_ens* e, long long* out, int enable) {
+    if (!e || !out) return ALABI_BAD_ARGUMENT;
+    int st;
+    if (enable && (st = pair_stats_alloc(e)) != ALABI_OK) return st;
+    for (int i = 0; i < 6; ++i) out[i] = 0;
+    if (!e->pair_stats) return ALABI_OK;
+    ALABI_HIP_CHECK(hipDeviceSynchronize());
+    ALABI_HIP_CHECK(hipMemcpy(out, e->pair_stats + 9, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    ALABI_HIP_CHECK(hipMemset(e->pair_stats + 9, 0, 6 * sizeof(unsigned long long)));
     return ALABI_OK;
 }
 

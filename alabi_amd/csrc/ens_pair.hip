@@ -23,6 +23,11 @@
 // while all 2 G E workgroups are resident (the host launches at most one per CU).
 // Arithmetic, lane -> point map, accumulation order, accept expression and row layout are those of ens_stream_kernel: the
 // surviving sum is that kernel's sum, so the chains agree bit for bit.
+// Fetch-ahead: between barrier A and barrier B of an item the hand-off wave has decoded the next item, so it loads that
+// item's input words there (with every look of the verdict poll, or once) and keeps them in registers; the next item starts
+// with a test of those registers and polls only if a lane still holds the sentinel.  R's rows are at least one verdict old, so
+// the round trip of its first load no longer stands in front of every item.  A word goes from the sentinel to its value
+// once per launch, so a fetched value is final; the last item of a launch fetches row 0.
 #include <cstdlib>
 #include "ens_stream.hpp"
 
@@ -31,15 +36,18 @@ namespace alabi {
 struct PairArgs {
     StreamArgs s;
     unsigned long long* prop;    // [(K+1)][E*W][d+2] published proposals (words [0, d) of a row are read); rows 1..K pre-filled with ALABI_HIST_EMPTY
-    unsigned long long* stats;   // nullptr, or [3 classes][3]: items, rows stored by R, rows stored by A (debug; accumulated outside the chain)
+    unsigned long long* stats;   // nullptr, or [3 classes][3]: items, rows stored by R, rows stored by A, then [2 roles][2]: items, items
+                                 // whose inputs the fetch-ahead had complete, then 2 words kept for the slot counters of alabi_ens_pair_stats2
+                                 // (debug; accumulated outside the chain)
 };
 
 #ifdef ALABI_PAIR_PROF
 // hand-off wave of pair 3, [0..7] R, [8..15] A: [0] input poll, [1] rows detected -> barrier A, [2] A -> B (the verdict poll included),
 // [3] B -> row store issued, [4] items, [5] ticks of the launch, [6] verdict-poll ticks of the class-1 items, [7] class-1 items;
 // [16..19] R, [20..23] A: publish -> detect ticks of the prop rows read and their number, row store -> verdict detected and their number
-// (the publisher leaves its clock in g_pair_pub, by row index modulo its size: [0] at the prop store, [1] at the row store)
-__device__ long long g_pair_prof[24];
+// (the publisher leaves its clock in g_pair_pub, by row index modulo its size: [0] at the prop store, [1] at the row store);
+// [24] R, [25] A: items whose inputs were complete at the first look (the fetch-ahead of the previous item)
+__device__ long long g_pair_prof[26];
 #define ALABI_PAIR_PUB_MASK ((1 << 19) - 1)
 __device__ long long g_pair_pub[2][ALABI_PAIR_PUB_MASK + 1];
 __device__ inline void pair_pub_stamp(int which, size_t row_index) {
@@ -71,7 +79,7 @@ ens_pair_kernel(PairArgs pa) {
     const int role_a = blockIdx.x & 1;                               // 1: this workgroup assumes "accepted"
     const int WT = p.W * E, row = p.d + 2;
 #ifdef ALABI_PAIR_PROF
-    long long prof[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    long long prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const long long prof_begin = wall_clock64();
 #endif
     f64x2 xa[PPT][D], aa[PPT];
@@ -114,7 +122,7 @@ ens_pair_kernel(PairArgs pa) {
     int t = 0, split = 0, bb = b, item = 0;           // b < G = n0: the first item is valid
 
     if (comm) {
-        // ---- hand-off wave: poll -> proposal -> LDS -> A -> (prior term, next decode, VERDICT poll, candidate rows) -> B -> accept -> store
+        // ---- hand-off wave: poll -> proposal -> LDS -> A -> (prior term, next decode, VERDICT poll + next inputs, candidate rows) -> B -> accept -> store
         const int n0_lane = lane < p.d ? lane : p.d, n1_lane = lane < p.d ? lane : p.d - 1;
         const int out_lane = lane <= p.d ? lane : p.d + 1, ver_lane = lane == p.d ? p.d : p.d + 1;
         const long long prop_off = (long long)(pa.prop - p.hist);   // one base pointer: every address stays a global one
@@ -157,18 +165,31 @@ ens_pair_kernel(PairArgs pa) {
         const bool needc = lane < p.d;
         const unsigned long long coord_lanes = (1ull << p.d) - 1;
         int st_items = 0, st_rows = 0;                // debug counters: lane c counts the items of class c
+        int st_all = 0, st_ahead = 0;                 // ... every lane: items, items whose inputs the fetch-ahead had complete
+        // The next item's input words, fetched ahead in this item's idle window (item 0: nothing fetched, the sentinel).  Every
+        // word of hist and prop goes from the sentinel to its value once per launch, so a fetched word that is not the sentinel
+        // is final; a lane that still holds the sentinel sends the wave to the poll below.
+        unsigned long long a_ws = ALABI_HIST_EMPTY, a_wc = ALABI_HIST_EMPTY;
         decode_next(0, 0, 0);
         while (t < p.K) {
             const int par = item & 1;
 #ifdef ALABI_PAIR_PROF
             const long long c0 = wall_clock64();
 #endif
-            unsigned long long ws, wc;
-            const bool pending = stream_poll(p, [&] {
+            unsigned long long ws = a_ws, wc = a_wc;
+            int loads = 0;
+            const bool pending = stream_poll_ahead(p, loads, [&] {
+                return __builtin_amdgcn_ballot_w64(ws == ALABI_HIST_EMPTY || wc == ALABI_HIST_EMPTY) != 0;
+            }, [&] {
                 ws = ld_sc1(n_hw);
                 wc = ld_sc1(n_hc);
-                return __builtin_amdgcn_ballot_w64(ws == ALABI_HIST_EMPTY || wc == ALABI_HIST_EMPTY) != 0;
+                asm volatile("" : "+v"(ws), "+v"(wc));   // waited for here, not in front of the first test
             });
+            // debug counters, in registers (here: the count does not stay live in a scalar register)
+            if (pa.stats) { st_all += 1; st_ahead += (loads == 0); }
+#ifdef ALABI_PAIR_PROF
+            prof[11] += (loads == 0);
+#endif
             // Bounded spin ran out: as in ens_stream_kernel the cold block rejoins the fast path -- a NaN stretch factor puts
             // the proposal out of bounds, this is the last proposal, nothing of it is stored or published.
             if (__builtin_expect(pending, 0)) {
@@ -216,8 +237,11 @@ ens_pair_kernel(PairArgs pa) {
             double lp_old = lane_bcast(sv, p.d);      // lane d loaded logp (not so for A with a fresh own row: see below)
             int part = par * (int)sizeof(scratch[0]);
             if (t2 < p.K) decode_next(item + 1, t2, s2);
+            else { n_hw = p.hist + n0_lane; n_hc = p.hist + n1_lane; }   // no next item: the fetch-ahead reads row 0
             // The verdict of the fresh row: its acceptance flag (every lane but lane d) and its log-probability (lane d).  Polled
             // here, in the window in which this wave is idle; the workgroup whose assumption holds publishes its proposal at once.
+            // The next item's input words (decoded above) are fetched in the same window: with every look of the verdict poll,
+            // else once -- a round trip that would otherwise stand in front of the next item although its rows are long there.
             int win = mode == 0;
 #ifdef ALABI_PAIR_PROF
             const long long c2v = wall_clock64();
@@ -226,6 +250,8 @@ ens_pair_kernel(PairArgs pa) {
                 unsigned long long vw;
                 const bool vpend = stream_poll(p, [&] {
                     vw = ld_sc1(ver);
+                    a_ws = ld_sc1(n_hw);
+                    a_wc = ld_sc1(n_hc);
                     return __builtin_amdgcn_ballot_w64(vw == ALABI_HIST_EMPTY) != 0;
                 });
                 if (__builtin_expect(vpend, 0)) {     // time-out: the last proposal, nothing stored
@@ -233,6 +259,9 @@ ens_pair_kernel(PairArgs pa) {
                     __hip_atomic_store(p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     t2 = p.K;
                 }
+                // the fetched words arrive right behind the verdict (one vmcnt, in issue order).  They are waited for HERE: a wait
+                // behind the prop store below would wait for that store's acknowledgement as well, in front of barrier B
+                asm volatile("" : "+v"(a_ws), "+v"(a_wc));
                 const int flag = __builtin_amdgcn_readfirstlane((int)(unsigned)(vw & 0xffffffffull));   // lane 0 polls the flag word (d >= 1)
                 win = !vpend && flag == role_a;
 #ifdef ALABI_PAIR_PROF
@@ -240,6 +269,10 @@ ens_pair_kernel(PairArgs pa) {
 #endif
                 if (win) st_sc1(p.hist + (out_word + prop_off), (unsigned long long)__double_as_longlong(qv));
                 if (own_a) lp_old = lane_bcast(__longlong_as_double((long long)vw), p.d);
+            } else {
+                a_ws = ld_sc1(n_hw);
+                a_wc = ld_sc1(n_hc);
+                asm volatile("" : "+v"(a_ws), "+v"(a_wc));   // waited for in front of barrier B, in this branch
             }
 #ifdef ALABI_PAIR_PROF
             const long long c2w = wall_clock64();
@@ -277,6 +310,7 @@ ens_pair_kernel(PairArgs pa) {
         if (pa.stats && lane < 3) {
             if (!role_a) atomicAdd(pa.stats + 3 * lane, (unsigned long long)st_items);
             atomicAdd(pa.stats + 3 * lane + 1 + role_a, (unsigned long long)st_rows);
+            if (lane < 2) atomicAdd(pa.stats + 9 + 2 * role_a + lane, (unsigned long long)(lane ? st_ahead : st_all));
         }
 #ifdef ALABI_PAIR_PROF
         if (tid == 0 && b == 3 && blockIdx.y == 0) {
@@ -285,6 +319,7 @@ ens_pair_kernel(PairArgs pa) {
             g[5] = wall_clock64() - prof_begin;
             g[6] = prof[5]; g[7] = prof[6];
             for (int i = 0; i < 4; ++i) g_pair_prof[16 + 4 * role_a + i] = prof[7 + i];
+            g_pair_prof[24 + role_a] = prof[11];
         }
 #endif
     } else if (compute) {
@@ -309,7 +344,7 @@ ens_pair_kernel(PairArgs pa) {
 
 #ifdef ALABI_PAIR_PROF
 extern "C" int alabi_debug_pair_prof(long long* out) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pair_prof), sizeof(long long) * 24);
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pair_prof), sizeof(long long) * 26);
 }
 #endif
 

@@ -119,6 +119,24 @@ __device__ __forceinline__ bool stream_poll(const StreamArgs& p, Look&& look) {
     return pending;
 }
 
+// The same poll for words that were fetched ahead and are in registers: `test` says whether any lane's word is still the
+// sentinel, `load` loads the words again AND waits for them (a pin on the loaded registers).  The first test is of the
+// registers, so a complete fetch costs no load -- and no wait: were the loop's loads waited for at their first use, the wait
+// would stand in the loop's header, in front of the first test too, and there it would (one vmcnt) wait for the row store the
+// wave has just issued.  `loads` counts the repeats.  Spin limit and abort look as in stream_poll.
+template <class Test, class Load>
+__device__ __forceinline__ bool stream_poll_ahead(const StreamArgs& p, int& loads, Test&& test, Load&& load) {
+    bool pending;
+    for (;;) {
+        pending = test();
+        if (!pending) break;
+        if (__builtin_expect(++loads > p.spin_limit || ((loads & 63) == 0 && __builtin_amdgcn_readfirstlane(
+                __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0), 0)) break;
+        load();
+    }
+    return pending;
+}
+
 // Compute waves 1..nwc, from barrier A to barrier B of every proposal: A -> q -> sum -> DPP -> partial -> B.  They look at the
 // abort word after barrier B, where they delay nobody.
 template <int D, int PPT, bool GENERIC>

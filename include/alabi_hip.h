@@ -247,6 +247,14 @@ int alabi_ens_stream_variant(alabi_ens* ens, int* variant /* host */);
  * that assumes "accepted".  The first call switches counting on (from the next run on); reset != 0 zeroes the counters after
  * reading.  Synchronises the device. */
 int alabi_ens_pair_stats(alabi_ens* ens, long long* out /* host [9] */, int reset);
+/* Fetch-ahead counters of ens_pair_kernel (its hand-off wave loads the next item's input words in the idle window of the current
+ * item and skips the poll when none of them is the sentinel): out[0] items of the workgroups that assume "rejected", out[1] those
+ * of them whose inputs the fetch-ahead had complete, out[2], out[3] the same for the workgroups that assume "accepted" (both
+ * step through every item; a skipped item reads row 0 and counts as complete); out[4], out[5] are kept for the class-1 items
+ * whose fresh input row the "accepted" workgroup takes from slot R and from slot A of a two-slot proposal array, and are 0
+ * while the proposal array has one slot.  enable != 0 switches counting on if it is not
+ * (from the next run on); the counters are zeroed after reading.  Synchronises the device. */
+int alabi_ens_pair_stats2(alabi_ens* ens, long long* out /* host [6] */, int enable);
 /* Blocking of the last group-kernel launch of alabi_ens_run (zeros before the first one), so a parity test can pin WHICH
  * instantiation of ens_group_kernel it compared with the oracle: out[0] Q (16-proposal tiles per group), [1] G (members per
  * group), [2] NG (groups per ensemble), [3] RT (point tiles per wave held in registers), [4] tpm (point tiles per member),

@@ -1,6 +1,8 @@
 """Phase breakdown of the pair variant of the persistent ensemble kernel (ens_pair_kernel): real-time stamps of the hand-off waves of
-both workgroups of one pair, the verdict poll of the speculative items, and the publish -> detect times of the proposal array and
-of the verdict (needs a build with -DALABI_PAIR_PROF: see tools/README.md)."""
+both workgroups of one pair, the verdict poll of the speculative items, the publish -> detect times of the proposal array and
+of the verdict, and the items whose inputs the fetch-ahead of the previous item had complete, so that the input poll was skipped
+(needs a build with -DALABI_PAIR_PROF: see tools/README.md).  "detected" is the stamp behind the input poll: for an item whose
+inputs were fetched ahead it is the top of the item, not the arrival of the words."""
 import ctypes, sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -12,7 +14,7 @@ gp = HipGP(cfg["d"], h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"]);
 s = EnsembleSampler(cfg["W"], cfg["d"], gp, cfg["y"], cfg["bounds"], seed=1)
 s.run_mcmc(cfg["p0"], 1024); torch.cuda.synchronize()
 t0 = time.perf_counter(); s.run_mcmc(None, 1024); torch.cuda.synchronize(); dt = time.perf_counter() - t0
-out = (ctypes.c_longlong * 24)()
+out = (ctypes.c_longlong * 26)()
 L = _lib.lib()
 L.alabi_debug_pair_prof.argtypes = [ctypes.POINTER(ctypes.c_longlong)]
 print("rc", L.alabi_debug_pair_prof(out), "path", s.last_path, "variant", s.last_stream_variant, "wall us/half-step", 1e6 * dt / 2048)
@@ -31,4 +33,5 @@ for role, base in (("R (assumes rejected)", 0), ("A (assumes accepted)", 8)):
     q = v[16 + (4 if base else 0):][:4]
     print(f"  prop publish -> detected by this reader    {q[0] / max(q[1], 1) * tick_ns:9.1f} ns  (n = {q[1]})")
     print(f"  row store -> verdict detected by this reader {q[2] / max(q[3], 1) * tick_ns:9.1f} ns  (n = {q[3]})")
+    print(f"  inputs complete at first look (fetched ahead)  {v[24 + (1 if base else 0)]} of {r[4]} items")
     print("  items", r[4], "ticks total", r[5], "=> tick ns", tick_ns)
