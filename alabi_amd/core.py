@@ -952,10 +952,12 @@ class SurrogateModel(object):
         ``opt_init=True`` starts the walkers around ``find_map()``.
 
         ``sampler_kwargs["moves"]`` (the reference's "Custom proposal moves", core.py:2144): None for the stretch move, or
-        ``alabi_amd.moves.StretchMove`` / ``DEMove`` objects (emcee's own are recognised), a list of them, or a list of
-        (move, weight) pairs -- one move is chosen per step.  Multimodal posteriors want
-        ``[(DEMove(), 0.9), (DEMove(gamma0=1.0), 0.1)]``: the stretch move alone does not cross between separated modes.
-        Any other emcee move raises ``NotImplementedError``; a ``DEMove`` cannot be combined with ``"shard": True``.
+        ``alabi_amd.moves.StretchMove`` / ``DEMove`` objects (emcee's own are recognised) or ``alabi_amd.moves.SnookerMove``
+        (the snooker update of ter Braak & Vrugt 2008; ``nwalkers >= 6``), a list of them, or a list of (move, weight) pairs --
+        one move is chosen per step.  Multimodal posteriors want ``[(DEMove(), 0.9), (DEMove(gamma0=1.0), 0.1)]``: the stretch
+        move alone does not cross between separated modes; the usual companion of DE is ``[(DEMove(), 0.8), (SnookerMove(),
+        0.2)]``.  Any other emcee move raises ``NotImplementedError`` -- emcee's ``DESnookerMove`` among them, whose arithmetic
+        is not the published rule; a ``DEMove`` or ``SnookerMove`` cannot be combined with ``"shard": True``.
 
         Several GPUs (the reference's parallel axis is a process pool handed to emcee, core.py:2300, :2322, built at :349-369;
         ``ncore`` / ``pool_method`` have no meaning here): run one process per GPU under ``torch.distributed`` (e.g.
@@ -971,9 +973,9 @@ class SurrogateModel(object):
         rank, world = adist.world_info()
         kw = dict(sampler_kwargs)
         move_set = parse_moves(kw.get("moves"), self.ndim)       # unsupported moves fail here, before anything runs
-        if kw.get("shard", False) and move_set is not None and move_set.has_de:
-            raise ValueError('sampler_kwargs={"shard": True} cannot run a DEMove: the sharded ensemble links one partner row per '
-                             'proposal')
+        if kw.get("shard", False) and move_set is not None and move_set.multi_partner:
+            raise ValueError('sampler_kwargs={"shard": True} cannot run a DEMove or a SnookerMove: the sharded ensemble links one '
+                             'partner row per proposal')
         shard = bool(kw.pop("shard", False)) and bool(multi_proc) and world > 1
         replicas = bool(multi_proc) and world > 1 and not shard
         # ---- likelihood

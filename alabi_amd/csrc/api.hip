@@ -530,16 +530,25 @@ static void free_move_buffers(MoveBuffers& m) {
     if (m.cw2) (void)hipFree(m.cw2);
     if (m.partner2) (void)hipFree(m.partner2);
     if (m.move) (void)hipFree(m.move);
+    if (m.cw3) (void)hipFree(m.cw3);
+    if (m.partner3) (void)hipFree(m.partner3);
     m = MoveBuffers{};
 }
 
-// The second-partner arrays of the records (first buffer set), allocated when a move set is first given or a DE step is injected.
-static int ensure_move_buffers(alabi_ens* e) {
-    if (e->mv.cw2) return ALABI_OK;
+// The second-partner arrays of the records (first buffer set), allocated when a move set is first given or a DE step is injected;
+// the third-partner arrays when the set holds a snooker move or a snooker step is injected.
+static int ensure_move_buffers(alabi_ens* e, bool third = false) {
     const size_t n = (size_t)e->chunk_cap * e->W * e->E;
-    hipError_t err = hipMalloc(&e->mv.cw2, n * sizeof(int));
-    if (err == hipSuccess) err = hipMalloc(&e->mv.partner2, n * sizeof(int));
-    if (err == hipSuccess) err = hipMalloc(&e->mv.move, (size_t)e->chunk_cap * e->E * sizeof(int));
+    hipError_t err = hipSuccess;
+    if (!e->mv.cw2) {
+        err = hipMalloc(&e->mv.cw2, n * sizeof(int));
+        if (err == hipSuccess) err = hipMalloc(&e->mv.partner2, n * sizeof(int));
+        if (err == hipSuccess) err = hipMalloc(&e->mv.move, (size_t)e->chunk_cap * e->E * sizeof(int));
+    }
+    if (third && !e->mv.cw3 && err == hipSuccess) {
+        err = hipMalloc(&e->mv.cw3, n * sizeof(int));
+        if (err == hipSuccess) err = hipMalloc(&e->mv.partner3, n * sizeof(int));
+    }
     if (err != hipSuccess) { free_move_buffers(e->mv); return hip_fail(err, "hipMalloc(move buffers)", __FILE__, __LINE__); }
     return ALABI_OK;
 }
@@ -665,22 +674,25 @@ int alabi_ens_set_logp_map(alabi_ens* e, int kind) {
 int alabi_ens_set_moves(alabi_ens* e, int n, const int* kind, const double* cum, const double* p0, const double* p1) {
     if (!e || n < 0 || n > ALABI_MAX_MOVES || (n > 0 && (!kind || !cum || !p0 || !p1))) return ALABI_BAD_ARGUMENT;
     MoveTable mt{};
-    bool de = false;
+    bool de = false, snooker = false;
     double prev = 0.0;
     for (int k = 0; k < n; ++k) {
         if (!(cum[k] >= prev) || !std::isfinite(cum[k])) return ALABI_BAD_ARGUMENT;   // cumulative weights do not decrease
         prev = cum[k];
         if (kind[k] == 0) { if (!(p0[k] > 1.0) || !std::isfinite(p0[k])) return ALABI_BAD_ARGUMENT; }          // stretch: a > 1
         else if (kind[k] == 1) { if (!std::isfinite(p0[k]) || !std::isfinite(p1[k])) return ALABI_BAD_ARGUMENT; de = true; }
+        else if (kind[k] == 2) { if (!std::isfinite(p0[k])) return ALABI_BAD_ARGUMENT; snooker = true; }                // snooker: gammas
         else return ALABI_BAD_ARGUMENT;
         mt.kind[k] = kind[k]; mt.cum[k] = cum[k]; mt.p0[k] = p0[k]; mt.p1[k] = p1[k];
     }
     if (n > 0 && !(prev > 0.0)) return ALABI_BAD_ARGUMENT;
     if (de && e->W < 4) return ALABI_BAD_ARGUMENT;       // two distinct partners in a complementary list of W / 2 walkers
-    if (n > 0) { const int st = ensure_move_buffers(e); if (st != ALABI_OK) return st; }
+    if (snooker && e->W < 6) return ALABI_BAD_ARGUMENT;  // three distinct partners
+    if (n > 0) { const int st = ensure_move_buffers(e, snooker); if (st != ALABI_OK) return st; }
     mt.n = n;
     e->moves = mt;
-    e->has_de = de;
+    e->has_de = de || snooker;                           // more than one partner row: one launch per half step
+    e->has_snooker = snooker;
     e->drawn_n = 0;                                      // records drawn under the old move set are not the new set's
     e->settings_gen++;
     if (e->graph_exec) { (void)hipGraphExecDestroy(e->graph_exec); e->graph_exec = nullptr; }   // captured draw launches carry the old table
@@ -815,6 +827,7 @@ static int enqueue_chunk(alabi_ens* e, HalfArgs h, int n, double a, hipStream_t 
     for (int t = 0; t < n; ++t) {
         h.rec = offset_draws(e->draws, (size_t)t * WT);
         h.cw2 = e->has_de ? e->mv.cw2 + (size_t)t * WT : nullptr;
+        h.cw3 = e->has_snooker ? e->mv.cw3 + (size_t)t * WT : nullptr;
         h.local_t = t; h.part_begin = 0;
         h.split = 0;
         if ((st = launch_ens_half_args(e, h, n0, s)) != ALABI_OK) return st;
@@ -846,8 +859,8 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
     const bool crowded = can_stream && e->stream_grid > 0 && ((e->W + 1) / 2 + e->stream_grid - 1) / e->stream_grid >= 4;
     const bool use_group = !e->has_de && e->stream_ok && s != nullptr && !group_off && (group_pref || !can_stream || crowded) && ens_group_fits(e) &&
                            ens_group_buffers(e, s);
-    // A differential-evolution record reads two partner rows: the persistent kernels hand one over, so such a move set runs
-    // with one launch per half step (and its graph replay).  Stretch-only sets differ in the draw kernel alone.
+    // A differential-evolution record reads two partner rows, a snooker record three: the persistent kernels hand one over, so
+    // such a move set (has_de) runs with one launch per half step (and its graph replay).  Stretch-only sets differ in the draw kernel alone.
     if (!e->has_de && e->stream_ok && s != nullptr && (can_stream || use_group)) {
         e->last_path = use_group ? 3 : 1;
         // ens_stream_kernel's chunks take the step counters by value and their epilogue leaves run_state as the other paths
@@ -987,6 +1000,7 @@ int alabi_ens_half_step(alabi_ens* e, double* coords, double* logp, int t, int s
     if (part_begin < 0 || part_end > nS || part_begin > part_end) return ALABI_BAD_ARGUMENT;
     h.rec = offset_draws(e->draws, (size_t)t * e->W);
     h.cw2 = e->has_de ? e->mv.cw2 + (size_t)t * e->W : nullptr;
+    h.cw3 = e->has_snooker ? e->mv.cw3 + (size_t)t * e->W : nullptr;
     h.local_t = t; h.split = split; h.part_begin = part_begin; h.n_accept = n_accept;
     return launch_ens_half_args(e, h, part_end - part_begin, as_stream(stream));
 }
@@ -1018,6 +1032,7 @@ int alabi_ens_propose(alabi_ens* e, const double* coords, int t, int split, int 
     const int nS = split == 0 ? h.n0 : e->W - h.n0;
     h.rec = offset_draws(e->draws, (size_t)t * e->W);
     h.cw2 = e->has_de ? e->mv.cw2 + (size_t)t * e->W : nullptr;
+    h.cw3 = e->has_snooker ? e->mv.cw3 + (size_t)t * e->W : nullptr;
     h.local_t = t; h.split = split; h.part_begin = 0;
     return launch_ens_propose(e, h, nS, gate_box, q, like, as_stream(stream));
 }
@@ -1077,6 +1092,40 @@ int alabi_ens_step_with_randoms_de(alabi_ens* e, double* coords, double* logp, c
     if ((st = launch_ens_half_args(e, h, n0, s)) != ALABI_OK) return st;
     h.split = 1;
     return launch_ens_half_args(e, h, e->W - n0, s);
+}
+
+int alabi_ens_step_with_randoms_snooker(alabi_ens* e, double* coords, double* logp, const int* order, int n0, const int* j1,
+                                        const int* j2, const int* j3, double gamma, const double* u_acc, long long* n_accept,
+                                        void* stream) {
+    if (!e || !coords || !logp || !order || !j1 || !j2 || !j3 || !u_acc || !std::isfinite(gamma) || n0 < 0 || n0 > e->W || e->E != 1)
+        return ALABI_BAD_ARGUMENT;
+    if (!e->gp->computed || !e->gp->has_alpha) return ALABI_NOT_COMPUTED;
+    hipStream_t s = as_stream(stream);
+    int st;
+    if ((st = sync_consts(e, s)) != ALABI_OK) return st;
+    if ((st = ensure_move_buffers(e, true)) != ALABI_OK) return st;
+    if ((st = launch_ens_prep_snooker(e, order, n0, j1, j2, j3, gamma, u_acc, s)) != ALABI_OK) return st;
+    e->drawn_n = 0;  // row 0 of the draw buffers now holds caller data
+    HalfArgs h = base_args(e, coords, logp);
+    h.rec = e->draws; h.cw2 = e->mv.cw2; h.cw3 = e->mv.cw3; h.n0 = n0; h.n_accept = n_accept; h.local_t = 0; h.part_begin = 0;
+    h.split = 0;
+    if ((st = launch_ens_half_args(e, h, n0, s)) != ALABI_OK) return st;
+    h.split = 1;
+    return launch_ens_half_args(e, h, e->W - n0, s);
+}
+
+int alabi_ens_export_snooker_draws(alabi_ens* e, int* j3, void* stream) {
+    if (!e || !j3 || e->drawn_n < 1 || !e->mv.cw3) return ALABI_BAD_ARGUMENT;
+    ALABI_HIP_CHECK(hipMemcpyAsync(j3, e->mv.partner3, (size_t)e->W * e->E * sizeof(int), hipMemcpyDeviceToDevice, as_stream(stream)));
+    return ALABI_OK;
+}
+
+int alabi_ens_export_partner_ids(alabi_ens* e, int* cw2, int* cw3, void* stream) {
+    if (!e || e->drawn_n < 1 || (cw2 && !e->mv.cw2) || (cw3 && !e->mv.cw3)) return ALABI_BAD_ARGUMENT;
+    const size_t bytes = (size_t)e->W * e->E * sizeof(int);
+    if (cw2) ALABI_HIP_CHECK(hipMemcpyAsync(cw2, e->mv.cw2, bytes, hipMemcpyDeviceToDevice, as_stream(stream)));
+    if (cw3) ALABI_HIP_CHECK(hipMemcpyAsync(cw3, e->mv.cw3, bytes, hipMemcpyDeviceToDevice, as_stream(stream)));
+    return ALABI_OK;
 }
 
 int alabi_ens_export_move_draws(alabi_ens* e, int* move, int* j2, double* gamma, void* stream) {

@@ -126,6 +126,7 @@ struct DrawBuffers {
 
 // Proposal moves (emcee's `moves=`): one move per step and ensemble, chosen by ens_draw_kernel from cumulative weights.
 //   kind 0 StretchMove: p0 = a.   kind 1 DEMove: p0 = gamma0 (mean step), p1 = sigma (its relative scatter).
+//   kind 2 SnookerMove: p0 = gammas (the fixed step along the line), p1 = 0.
 // n = 0 stands for the default, one stretch move with the `a` of the call.
 #define ALABI_MAX_MOVES 8
 struct MoveTable {
@@ -137,10 +138,15 @@ struct MoveTable {
 // What a differential-evolution record carries beyond DrawBuffers (kept apart from it: the persistent kernels take DrawBuffers by
 // value and know one partner only).  A DE record reuses the stretch record's slots -- cw = C[j1], zz = gamma, lnfac = 0 -- and adds
 // the second partner.  Allocated when a move set is given (alabi_ens_set_moves); null pointers are not written.
+// A snooker record (ter Braak & Vrugt 2008) names three walkers of the complementary set: cw = z = C[j1], cw2 = z1 = C[j2] and the
+// third partner z2 = C[j3]; zz = gammas, and lnfac is a placeholder (0): the factor depends on the rows and is formed by the kernel
+// that forms the proposal.  The third-partner arrays exist only on a handle that was given a snooker move.
 struct MoveBuffers {
     int* cw2;        // [chunk_cap, E, W] global id of the second partner C[j2] by list position; -1: a stretch record
     int* partner2;   // [chunk_cap, E, W] raw j2 into the complementary list (-1: stretch), for export / tests
     int* move;       // [chunk_cap, E] index of the step's move
+    int* cw3;        // [chunk_cap, E, W] global id of the third partner C[j3]; -1: a stretch or differential-evolution record
+    int* partner3;   // [chunk_cap, E, W] raw j3 into the complementary list (-1: stretch, DE), for export / tests
 };
 }  // namespace alabi
 
@@ -199,10 +205,11 @@ struct alabi_ens {
     long long settings_gen = 0;          // bumped by every setter that changes what captured launches carry (graph keys)
     long long serial = 0;                // unique per handle for the life of the process (a new handle at an old address is not the old one)
     int group_plan[8] = {0};  // blocking of the last group-kernel launch: Q, G, NG, RT, tpm, ltw, KS, LDS bytes (alabi_ens_group_plan)
-    // proposal moves (alabi_ens_set_moves): the table the draw kernel chooses from, whether it holds a DE move (then every run
-    // takes the launch-per-half-step path, whose kernels read the second partner row), and the records' second-partner arrays
+    // proposal moves (alabi_ens_set_moves): the table the draw kernel chooses from, whether it holds a move that reads more than
+    // one partner row -- has_de: a DE or a snooker move (then every run takes the launch-per-half-step path, whose kernels read the
+    // second partner row), has_snooker: a snooker move (the three-partner instantiations) -- and the records' further-partner arrays
     alabi::MoveTable moves{};
-    bool has_de = false;
+    bool has_de = false, has_snooker = false;
     alabi::MoveBuffers mv{};
 };
 
@@ -291,6 +298,8 @@ struct HalfArgs {
     double* sout = nullptr;
     // differential-evolution records (MoveBuffers::cw2 offset to the step): set -> the kernels' two-partner instantiations run
     const int* cw2 = nullptr;
+    // snooker records (MoveBuffers::cw3 offset to the step; cw2 is set as well): set -> the three-partner instantiations run
+    const int* cw3 = nullptr;
 };
 int launch_ens_draw(alabi_ens* e, int nsteps, double a, hipStream_t s);
 int launch_ens_draw_at(alabi_ens* e, const DrawBuffers& into, int nsteps, double a, bool from_state, long long step0, hipStream_t s);   // first step: run_state[0], or step0 by value
@@ -298,6 +307,8 @@ int launch_ens_prep(alabi_ens* e, const int* order, int n0, const double* u_z, c
                     const double* u_acc, double a, hipStream_t s);
 int launch_ens_prep_de(alabi_ens* e, const int* order, int n0, const int* j1, const int* j2, const double* gamma,
                        const double* u_acc, hipStream_t s);
+int launch_ens_prep_snooker(alabi_ens* e, const int* order, int n0, const int* j1, const int* j2, const int* j3, double gamma,
+                            const double* u_acc, hipStream_t s);
 int launch_ens_half_args(alabi_ens* e, const HalfArgs& args, int nblocks, hipStream_t s);
 int launch_ens_lnprob(alabi_ens* e, const double* coords, int nwalkers, double* logp, int gate_box, hipStream_t s);
 int launch_ens_propose(alabi_ens* e, const HalfArgs& args, int nblocks, int gate_box, double* q, double* like, hipStream_t s);

@@ -13,6 +13,12 @@
 // evolution moves (emcee 3 moves/de.py: q = S_k + gamma (C[j2] - C[j1]), j1 != j2, gamma = gamma0 (1 + sigma n), log factor 0).
 // A DE record uses the stretch record's slots plus one second-partner id (write_de_record); the half-step, multi-proposal and
 // propose kernels have a second instantiation that reads it (tests/de_move_numpy.py is the CPU statement).
+// The snooker update (ter Braak & Vrugt 2008, eq. 4; tests/snooker_numpy.py is the CPU statement) moves S_k along the line through
+// itself and z = C[j1] by gammas times the difference of the projections of z1 = C[j2] and z2 = C[j3] on that line (snooker_coord);
+// its log factor (d - 1) (ln|q - z| - ln|S_k - z|) depends on the rows, so it is formed where the proposal is: the half-step and
+// the propose kernel have a third instantiation that reads the third partner (write_snooker_record) and still takes stretch and
+// DE records, since the step's move is chosen on the device.  The multi-proposal kernel has no such instantiation: a set with a
+// snooker move runs one proposal per workgroup.
 //
 // E independent ensembles of W walkers ("independent chains") can share every launch: walker
 // ids are global (e*W + i), lists are per-ensemble segments, blockIdx.y is the ensemble.
@@ -73,6 +79,15 @@ __device__ inline void write_de_record(const DrawBuffers& b, const MoveBuffers& 
                                        double gamma, double u_acc) {
     store_record(b, pos, wid, cw, gamma, 0.0, log(u_acc));
     if (mv.cw2) { mv.cw2[pos] = cw2; mv.partner2[pos] = j2; }
+}
+
+// Snooker record: cw = z = C[j1], cw2 = z1 = C[j2], third partner z2 = C[j3], zz = gammas; lnfac is a placeholder, the kernel
+// that forms the proposal computes the factor from the rows.  Stretch and DE records carry -1 in the third-partner slots.
+__device__ inline void write_snooker_record(const DrawBuffers& b, const MoveBuffers& mv, size_t pos, int wid, int cw, int cw2, int j2,
+                                            int cw3, int j3, double gammas, double u_acc) {
+    store_record(b, pos, wid, cw, gammas, 0.0, log(u_acc));
+    if (mv.cw2) { mv.cw2[pos] = cw2; mv.partner2[pos] = j2; }
+    if (mv.cw3) { mv.cw3[pos] = cw3; mv.partner3[pos] = j3; }
 }
 
 // grid = (steps of the chunk, ensembles); dynamic LDS = Wp * 12 + 1024 bytes, Wp = W rounded up to a power of two.
@@ -189,18 +204,32 @@ ens_draw_kernel(unsigned long long seed, const long long* __restrict__ run_state
         if (kind == 0) {
             write_record(b, base + pos, (int)g0 + i, (int)g0 + cw, uz, ua, mp0, d);
             if (mv.cw2) { mv.cw2[base + pos] = -1; mv.partner2[base + pos] = -1; }
+            if (mv.cw3) { mv.cw3[base + pos] = -1; mv.partner3[base + pos] = -1; }
         } else {
             // j1 = pr and j2 != j1 from the fourth word: uniform over the nc (nc - 1) ordered pairs (emcee's _get_nondiagonal_pairs);
             // nc >= 2 is checked where the moves are set
             const int j2p = (int)(((uint64_t)r3 * (nc - 1)) >> 32);
             const int j2 = j2p + (j2p >= pr ? 1 : 0);
             const int cw2 = olist[(li ? 0 : n0) + j2];
+            if (kind == 2) {
+                // snooker: a third walker from stream 5, bumped past the smaller and then the larger of j1, j2 -- uniform over the
+                // nc (nc - 1) (nc - 2) ordered triples; nc >= 3 is checked where the moves are set
+                philox4x32_10(s_lo, s_hi, g0 + (uint32_t)i, 5u, k0, k1, r);
+                const int jlo = pr < j2 ? pr : j2, jhi = pr < j2 ? j2 : pr;
+                int j3 = (int)(((uint64_t)r[0] * (nc - 2)) >> 32);
+                j3 += (j3 >= jlo ? 1 : 0);
+                j3 += (j3 >= jhi ? 1 : 0);
+                const int cw3 = olist[(li ? 0 : n0) + j3];
+                write_snooker_record(b, mv, base + pos, (int)g0 + i, (int)g0 + cw, (int)g0 + cw2, j2, (int)g0 + cw3, j3, mp0, ua);
+                continue;
+            }
             // gamma = g0 (1 + sigma n), n standard normal by Box-Muller from stream 4
             philox4x32_10(s_lo, s_hi, g0 + (uint32_t)i, 4u, k0, k1, r);
             const double u1 = u53(r[0], r[1]), u2 = u53(r[2], r[3]);
             const double nrm = sqrt(-2.0 * log(1.0 - u1)) * cos(6.283185307179586 * u2);
             const double gamma = mp0 * (1.0 + mp1 * nrm);
             write_de_record(b, mv, base + pos, (int)g0 + i, (int)g0 + cw, (int)g0 + cw2, j2, gamma, ua);
+            if (mv.cw3) { mv.cw3[base + pos] = -1; mv.partner3[base + pos] = -1; }
         }
     }
 }
@@ -250,6 +279,30 @@ ens_prep_de_kernel(const int* __restrict__ order, int n0, int W, const int* __re
     write_de_record(b, mv, pos, wid, cw, cw2, jj, g, ua);
 }
 
+// The same for snooker records: j1 / j2 / j3 index the complementary list, pairwise distinct; gamma is the fixed step gammas.
+__global__ void __launch_bounds__(256)
+ens_prep_snooker_kernel(const int* __restrict__ order, int n0, int W, const int* __restrict__ j1, const int* __restrict__ j2,
+                        const int* __restrict__ j3, double gamma, const double* __restrict__ u_acc, DrawBuffers b, MoveBuffers mv) {
+    const int pos = blockIdx.x * 256 + threadIdx.x;
+    if (pos >= W) return;
+    const int w = order[pos];
+    const int li = pos >= n0;
+    const int nC = li ? n0 : W - n0;
+    int wid = -1, cw = -1, cw2 = -1, cw3 = -1, jj2 = -1, jj3 = -1;
+    double ua = 0.5;
+    if ((unsigned)w < (unsigned)W) {
+        const int a1 = j1[w], a2 = j2[w], a3 = j3[w];
+        if ((unsigned)a1 < (unsigned)nC && (unsigned)a2 < (unsigned)nC && (unsigned)a3 < (unsigned)nC && a1 != a2 && a1 != a3 && a2 != a3) {
+            const int off = li ? 0 : n0;
+            const int c1 = order[off + a1], c2 = order[off + a2], c3 = order[off + a3];
+            if ((unsigned)c1 < (unsigned)W && (unsigned)c2 < (unsigned)W && (unsigned)c3 < (unsigned)W) {
+                wid = w; cw = c1; cw2 = c2; cw3 = c3; jj2 = a2; jj3 = a3; ua = u_acc[w];
+            }
+        }
+    }
+    write_snooker_record(b, mv, pos, wid, cw, cw2, jj2, cw3, jj3, gamma, ua);
+}
+
 // Normal-prior term of coordinate `lane` (< d) of a proposal, summed over the wave: lanes >= d contribute 0.
 // consts rows 3 / 4: prior mean, 1 / std (0 where there is no normal prior).  Result valid in every lane.
 // h and the centred inputs of the squared-exponential half-step kernels (alabi_gp::Xc, ::ens_h)
@@ -290,10 +343,47 @@ __device__ inline double propose_coord(bool de, double sv, double cv, double c2v
     return de ? sv + zz * (c2v - cv) : cv - (cv - sv) * zz;
 }
 
+// Sum over k = 0 .. d-1 of the value lane k of the wave holds, accumulated in that order from 0 (what tests/snooker_numpy.py
+// states as _seq_sum); every lane returns it.  readlane takes the value whether or not the caller's branch has the lane active.
+template <int D>
+__device__ __forceinline__ double lane_seq_sum(double v, int d) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        const double t = lane_bcast(v, k);
+        if (k < d) s += t;
+    }
+    return s;
+}
+
+// Snooker proposal (ter Braak & Vrugt 2008, eq. 4), coordinate `lane` of it.  Called by lanes 0 .. D-1 of wave 0 together; lanes
+// >= d pass zeros and their result means nothing.  sv, zv, z1v, z2v: the coordinate of s, z = C[j1], z1 = C[j2], z2 = C[j3].
+//   delta = s - z, n = |delta|, e = delta / n, p = e.z1 - e.z2, q = s + (gamma p) e, lnfac = (d - 1) (ln|q - z| - ln n)
+// in the operation order of tests/snooker_numpy.py (products rounded, then added in coordinate order: no contraction); sqrt and /
+// are correctly rounded, so q has the model's bits.  n == 0 makes q NaN (out of the box), |q - z| == 0 makes lnfac -inf or, for
+// d == 1, NaN: the accept test is false in each case.
+template <int D>
+__device__ __forceinline__ double snooker_coord(int d, double sv, double zv, double z1v, double z2v, double gamma, double& lnfac) {
+    const double delta = sv - zv;
+    const double n = sqrt(lane_seq_sum<D>(delta * delta, d));
+    const double ev = delta / n;
+    const double pz1 = lane_seq_sum<D>(ev * z1v, d);
+    const double pz2 = lane_seq_sum<D>(ev * z2v, d);
+    const double gp = gamma * (pz1 - pz2);
+    const double qv = sv + gp * ev;
+    const double dq = qv - zv;
+    const double nq = sqrt(lane_seq_sum<D>(dq * dq, d));
+    lnfac = ((double)d - 1.0) * (log(nq) - log(n));
+    return qv;
+}
+
 // DE: the instantiation that reads the records' second partner (HalfArgs::cw2) and branches, workgroup-uniformly, on the
-// record's kind; without it the code is the stretch move's alone.
-template <int D, bool GENERIC, bool DE>
+// record's kind; without it the code is the stretch move's alone.  SNK (with DE): the one that reads the third partner as well
+// (HalfArgs::cw3) and forms a snooker record's proposal and log factor; stretch and DE records take the branches they take in the
+// DE instantiation.
+template <int D, bool GENERIC, bool DE, bool SNK = false>
 __device__ __forceinline__ void ens_half_body(const HalfArgs& p) {
+    static_assert(DE || !SNK, "the three-partner instantiation reads the second partner too");
     __shared__ double q_s[ALABI_MAX_DIM], qs_s[ALABI_MAX_DIM], old_s[ALABI_MAX_DIM];
     __shared__ double scratch[16];
     const int tid = threadIdx.x, T = blockDim.x;
@@ -318,12 +408,14 @@ __device__ __forceinline__ void ens_half_body(const HalfArgs& p) {
     const int cw = p.rec.cw[pos];
     const double zz = p.rec.zz[pos];
     const int cw2 = DE ? p.cw2[pos] : -1;         // second partner of a differential-evolution record, -1: a stretch record
-    const bool de = DE && cw2 >= 0;
+    const int cw3 = SNK ? p.cw3[pos] : -1;        // third partner of a snooker record, -1: a stretch or DE record
+    const bool snk = SNK && cw3 >= 0;
+    const bool de = DE && cw2 >= 0 && !snk;
     // where the two rows live: in place (coords / logp), or -- sharded ensemble -- in the history of published rows
     const double* own_c = p.coords + (size_t)w * p.d;
     const double* own_lp = p.logp + w;
     const double* par_c = p.coords + (size_t)cw * p.d;
-    const double* par2_c = p.coords + (size_t)(de ? cw2 : cw) * p.d;
+    const double* par2_c = p.coords + (size_t)(de || snk ? cw2 : cw) * p.d;
     if (p.shist) {
         const unsigned long long lw = p.rec.link[2 * pos];
         const int so = (int)(unsigned)(lw & 0xffffffffull), sp = (int)(unsigned)(lw >> 32);
@@ -338,7 +430,21 @@ __device__ __forceinline__ void ens_half_body(const HalfArgs& p) {
     int ok = 1;
     if (tid < D) {
         double qv = 0.0;
-        if (tid < p.d) {
+        if (SNK && snk) {                                  // workgroup-uniform; lanes d .. D-1 take part in the sums with zeros
+            const bool in = tid < p.d;
+            const double* par3_c = p.coords + (size_t)cw3 * p.d;
+            const double sv = in ? own_c[tid] : 0.0, zv = in ? par_c[tid] : 0.0;
+            const double z1v = in ? par2_c[tid] : 0.0, z2v = in ? par3_c[tid] : 0.0;
+            double lf;
+            const double qc = snooker_coord<D>(p.d, sv, zv, z1v, z2v, zz, lf);
+            if (in) {
+                lnfac = lf;                                // in the lanes that use the accept flag: 0 .. d-1
+                ok = (qc > lo[tid]) && (qc < hi[tid]);
+                q_s[tid] = qc; old_s[tid] = sv;
+                qv = qc * inv_len[tid];
+                if (!GENERIC) qv -= p.centre[tid];
+            }
+        } else if (tid < p.d) {
             const double cv = par_c[tid];
             const double sv = own_c[tid];
             qv = DE ? propose_coord(de, sv, cv, par2_c[tid], zz) : cv - (cv - sv) * zz;
@@ -443,6 +549,10 @@ ens_half_kernel(HalfArgs p) { ens_half_body<D, GENERIC, false>(p); }
 template <int D, bool GENERIC>
 __global__ void __launch_bounds__(1024)
 ens_half_de_kernel(HalfArgs p) { ens_half_body<D, GENERIC, true>(p); }
+
+template <int D, bool GENERIC>
+__global__ void __launch_bounds__(1024)
+ens_half_snooker_kernel(HalfArgs p) { ens_half_body<D, GENERIC, true, true>(p); }
 
 // NP proposals of the same half step per workgroup: the training set is streamed ONCE per workgroup and used for all of them.
 // With more proposals than CUs (W/2 > 256, or E ensembles) ens_half_kernel is bound by L2 -> CU bandwidth: every workgroup
@@ -634,7 +744,7 @@ ens_lnprob_kernel(const double* __restrict__ coords, int d, const double* __rest
 //   (host)              lp_new = like + prior_fn(q)   [or like_fn(q) + prior_fn(q)]
 //   ens_accept_kernel   one thread per proposal: accept test with the record's (d-1) ln z and ln u', state update.
 // The ensemble, the draws and the accept decisions stay on the device; only the proposals of a half step travel.
-template <int D, bool GENERIC, bool DE>
+template <int D, bool GENERIC, bool DE, bool SNK = false>
 __device__ __forceinline__ void ens_propose_body(const HalfArgs& p, int gate_box, double* __restrict__ q_out, double* __restrict__ like_out) {
     __shared__ double qs_s[ALABI_MAX_DIM];
     __shared__ double scratch[16];
@@ -649,11 +759,25 @@ __device__ __forceinline__ void ens_propose_body(const HalfArgs& p, int gate_box
     const int cw = p.rec.cw[pos];
     const double zz = p.rec.zz[pos];
     const int cw2 = DE ? p.cw2[pos] : -1;
-    const bool de = DE && cw2 >= 0;
+    const int cw3 = SNK ? p.cw3[pos] : -1;
+    const bool snk = SNK && cw3 >= 0;
+    const bool de = DE && cw2 >= 0 && !snk;
     int ok = 1;
     if (tid < D) {
         double qv = 0.0;
-        if (tid < p.d) {
+        if (SNK && snk) {                                  // as in ens_half_body; the log factor goes where ens_accept_kernel reads it
+            const bool in = tid < p.d;
+            const double sv = in ? p.coords[(size_t)w * p.d + tid] : 0.0, zv = in ? p.coords[(size_t)cw * p.d + tid] : 0.0;
+            const double z1v = in ? p.coords[(size_t)cw2 * p.d + tid] : 0.0, z2v = in ? p.coords[(size_t)cw3 * p.d + tid] : 0.0;
+            double lf;
+            const double qc = snooker_coord<D>(p.d, sv, zv, z1v, z2v, zz, lf);
+            if (tid == 0) p.rec.lnfac[pos] = lf;
+            if (in) {
+                ok = (qc > p.consts[ALABI_MAX_DIM + tid]) && (qc < p.consts[2 * ALABI_MAX_DIM + tid]);
+                q_out[(size_t)blockIdx.x * p.d + tid] = qc;
+                qv = qc * p.consts[tid];
+            }
+        } else if (tid < p.d) {
             const double cv = p.coords[(size_t)cw * p.d + tid];
             const double sv = p.coords[(size_t)w * p.d + tid];
             qv = DE ? propose_coord(de, sv, cv, p.coords[(size_t)(de ? cw2 : cw) * p.d + tid], zz) : cv - (cv - sv) * zz;
@@ -680,6 +804,12 @@ template <int D, bool GENERIC>
 __global__ void __launch_bounds__(1024)
 ens_propose_de_kernel(HalfArgs p, int gate_box, double* __restrict__ q_out, double* __restrict__ like_out) {
     ens_propose_body<D, GENERIC, true>(p, gate_box, q_out, like_out);
+}
+
+template <int D, bool GENERIC>
+__global__ void __launch_bounds__(1024)
+ens_propose_snooker_kernel(HalfArgs p, int gate_box, double* __restrict__ q_out, double* __restrict__ like_out) {
+    ens_propose_body<D, GENERIC, true, true>(p, gate_box, q_out, like_out);
 }
 
 __global__ void __launch_bounds__(256)
@@ -753,6 +883,14 @@ int launch_ens_prep_de(alabi_ens* e, const int* order, int n0, const int* j1, co
     return ALABI_OK;
 }
 
+int launch_ens_prep_snooker(alabi_ens* e, const int* order, int n0, const int* j1, const int* j2, const int* j3, double gamma,
+                            const double* u_acc, hipStream_t s) {
+    hipLaunchKernelGGL(ens_prep_snooker_kernel, dim3((e->W + 255) / 256), dim3(256), 0, s, order, n0, e->W, j1, j2, j3, gamma, u_acc,
+                       e->draws, e->mv);
+    ALABI_LAUNCH_CHECK();
+    return ALABI_OK;
+}
+
 int launch_ens_half_args(alabi_ens* e, const HalfArgs& args_in, int nblocks, hipStream_t s) {
     if (nblocks <= 0) return ALABI_OK;
     const int db = dim_bucket(e->d);
@@ -775,7 +913,10 @@ int launch_ens_half_args(alabi_ens* e, const HalfArgs& args_in, int nblocks, hip
         if (env && env[0] == '2') np = 2;
         if (env && env[0] == '1') np = 1;
     }
-    if (args.cw2) {                                   // records with a second partner: the two-partner instantiations
+    if (args.cw3) {                                   // records with a third partner: one proposal per workgroup
+        if (args.shist || !args.cw2) return ALABI_BAD_ARGUMENT;
+        ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(e->gp->kf.type, hipLaunchKernelGGL((ens_half_snooker_kernel<D, GENERIC>), dim3(nblocks, e->E), dim3(threads), 0, s, args)));
+    } else if (args.cw2) {                            // records with a second partner: the two-partner instantiations
         if (args.shist) return ALABI_BAD_ARGUMENT;    // the sharded history links one partner row
         if (np == 4) {
             ALABI_DISPATCH_DIM16(db, ALABI_DISPATCH_KERNEL(e->gp->kf.type, hipLaunchKernelGGL((ens_half_multi_de_kernel<D, GENERIC, 4>),
@@ -813,7 +954,11 @@ int launch_ens_lnprob(alabi_ens* e, const double* coords, int nwalkers, double* 
 int launch_ens_propose(alabi_ens* e, const HalfArgs& args, int nblocks, int gate_box, double* q, double* like, hipStream_t s) {
     if (nblocks <= 0) return ALABI_OK;
     const int db = dim_bucket(e->d);
-    if (args.cw2) {
+    if (args.cw3) {
+        if (!args.cw2) return ALABI_BAD_ARGUMENT;
+        ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(e->gp->kf.type, hipLaunchKernelGGL((ens_propose_snooker_kernel<D, GENERIC>), dim3(nblocks),
+                                                                                        dim3(e->threads), 0, s, args, gate_box, q, like)));
+    } else if (args.cw2) {
         ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(e->gp->kf.type, hipLaunchKernelGGL((ens_propose_de_kernel<D, GENERIC>), dim3(nblocks),
                                                                                         dim3(e->threads), 0, s, args, gate_box, q, like)));
     } else {

@@ -54,10 +54,12 @@ class EnsembleSampler:
         (alabi_ens_propose / alabi_ens_accept): the ensemble, the draws and the accept test stay on the device.  With
         ``like_fn=None`` the surrogate part is evaluated by the propose kernel; ``gate_box`` says whether that value is
         -inf outside ``bounds`` (True when the prior is the box itself, False when ``prior_fn`` is the whole prior).
-        ``moves``: emcee's proposal moves (alabi_amd.moves) -- None (the stretch move with ``a``), a ``StretchMove`` or
-        ``DEMove``, a list of them, or a list of (move, weight) pairs from which one move is chosen per step; emcee's own move
-        objects of these two classes are recognised.  Works with ``n_ensembles`` > 1 and with host callables; a set holding a
-        ``DEMove`` needs ``nwalkers >= 4``, runs with one launch per half step, and cannot be sharded.
+        ``moves``: emcee's proposal moves (alabi_amd.moves) -- None (the stretch move with ``a``), a ``StretchMove``,
+        ``DEMove`` or ``SnookerMove`` (the snooker update of ter Braak & Vrugt 2008), a list of them, or a list of (move, weight)
+        pairs from which one move is chosen per step; emcee's own ``StretchMove`` / ``DEMove`` objects are recognised, its
+        ``DESnookerMove`` is refused (different arithmetic).  Works with ``n_ensembles`` > 1 and with host callables; a set holding a
+        ``DEMove`` needs ``nwalkers >= 4``, one holding a ``SnookerMove`` ``nwalkers >= 6``; either runs with one launch per half
+        step and cannot be sharded.
         ``shard=True`` under an initialised ``torch.distributed`` group of more than one rank (``group``: default WORLD): ONE
         ensemble whose active half is partitioned over the ranks, an all-gather of the new rows per half step
         (alabi_amd.dist.ShardedRun -> alabi_ens_run_sharded); every rank must construct the sampler with the same arguments and
@@ -97,11 +99,14 @@ class EnsembleSampler:
         if self.shard and (self.generic or self.n_ensembles != 1):
             raise ValueError("shard=True needs the fused log-probability (no host callables) and n_ensembles == 1")
         self._move_set = parse_moves(moves, self.ndim)
-        if self._move_set is not None and self._move_set.has_de:
-            if self.nwalkers < 4:
+        if self._move_set is not None and self._move_set.multi_partner:
+            if self._move_set.has_de and self.nwalkers < 4:
                 raise ValueError("DEMove draws two distinct walkers from the complementary half: nwalkers >= 4")
+            if self._move_set.has_snooker and self.nwalkers < 6:
+                raise ValueError("SnookerMove draws three distinct walkers from the complementary half: nwalkers >= 6")
             if self.shard:
-                raise ValueError("shard=True cannot run a DEMove: the sharded history links one partner row per proposal")
+                raise ValueError("shard=True cannot run a DEMove or a SnookerMove: the sharded history links one partner row per "
+                                 "proposal")
         if seed is None:
             seed = int(np.random.SeedSequence().generate_state(2, dtype=np.uint32).view(np.uint64)[0])
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF

@@ -223,11 +223,16 @@ int alabi_ens_set_logp_map(alabi_ens* ens, int kind);
  * moves", alabi/core.py:2144, and handed to emcee.EnsembleSampler at alabi/core.py:2319).  A table of n <= 8 moves, all HOST
  * arrays: kind 0 = StretchMove with p0 = a (> 1); kind 1 = DEMove (emcee 3 moves/de.py) with p0 = gamma0 and p1 = sigma,
  * proposal q = s + gamma0 (1 + sigma n) (C[j2] - C[j1]), n standard normal, j1 != j2 drawn from the complementary set, log
- * factor 0.  cum = np.cumsum(w / w.sum()) in fp64: ONE move is chosen per step and ensemble, index = #{k: cum[k] <= u}
+ * factor 0; kind 2 = SnookerMove, the snooker update of ter Braak & Vrugt (2008, eq. 4) on the sampler's two-way split, with
+ * p0 = gammas (finite) and p1 = 0: three distinct walkers z = C[j1], z1 = C[j2], z2 = C[j3] of the complementary set, e the unit
+ * vector from z to s, q = s + gammas (e.z1 - e.z2) e, log factor (d - 1) (ln|q - z| - ln|s - z|) formed by the kernel that forms
+ * q (j3 from Philox stream 5, word 0, at the walker).  This is the published rule, not emcee 3's DESnookerMove, whose factor is
+ * half of it.  cum = np.cumsum(w / w.sum()) in fp64: ONE move is chosen per step and ensemble, index = #{k: cum[k] <= u}
  * (clipped to n - 1) with u from Philox stream 3 at the ensemble's walker 0.  n = 0 restores the default (one stretch move with
  * the `a` of each call); with n > 0 the `a` arguments of run / draw / export_draws are not used.  Streams 0-2 (labels, u_z and
- * partner, u') do not depend on the moves.  A set holding a DE move needs W >= 4, runs alabi_ens_run with one launch per half
- * step, and is refused by the sharded run.  Takes effect from the next call on. */
+ * partner, u') do not depend on the moves, streams 3-4 not on a snooker move.  A set holding a DE move needs W >= 4, one holding a
+ * snooker move W >= 6; either runs alabi_ens_run with one launch per half step (a snooker set: one proposal per workgroup) and
+ * is refused by the sharded run.  Takes effect from the next call on. */
 int alabi_ens_set_moves(alabi_ens* ens, int n, const int* kind, const double* cum, const double* p0, const double* p1);
 
 /* Enable / disable the persistent dataflow kernel for alabi_ens_run on this handle (default: enabled when the
@@ -353,6 +358,21 @@ int alabi_ens_export_move_draws(alabi_ens* ens, int* move, int* j2, double* gamm
 int alabi_ens_step_with_randoms_de(alabi_ens* ens, double* coords, double* logp, const int* order, int n0,
                                    const int* j1, const int* j2, const double* gamma, const double* u_acc,
                                    long long* n_accept, void* stream);
+
+/* Test entries of the snooker move (kind 2 of alabi_ens_set_moves), siblings of the two above.
+ * alabi_ens_export_snooker_draws: for the step last drawn by alabi_ens_export_draws on a handle whose move set holds a snooker
+ * move -- in LIST order j3 [E*W], the third partner's index into the complementary list (-1 at a stretch or DE step); j1 is
+ * export_draws' `partner`, j2 comes from alabi_ens_export_move_draws.
+ * alabi_ens_export_partner_ids: for the same step, in LIST order, the global walker ids of the second (cw2 [E*W]) and the third
+ * partner (cw3 [E*W]); -1 where the record has none; either pointer may be NULL.
+ * alabi_ens_step_with_randoms_snooker (n_ensembles == 1): one full snooker step from caller-supplied draws keyed by WALKER id:
+ * j1[W] / j2[W] / j3[W] int32 index the complementary list (pairwise distinct), gamma is gammas, u_acc[W] the accept uniform.
+ * Out-of-range or non-distinct indices make that proposal a no-op.  All arrays on the device. */
+int alabi_ens_export_snooker_draws(alabi_ens* ens, int* j3, void* stream);
+int alabi_ens_export_partner_ids(alabi_ens* ens, int* cw2, int* cw3, void* stream);
+int alabi_ens_step_with_randoms_snooker(alabi_ens* ens, double* coords, double* logp, const int* order, int n0,
+                                        const int* j1, const int* j2, const int* j3, double gamma, const double* u_acc,
+                                        long long* n_accept, void* stream);
 
 /* Nested sampling (dynesty's NestedSampler / DynamicNestedSampler with sample="rwalk" as driven by
  * SurrogateModel.run_dynesty, alabi/core.py:2417-2787, likelihood = surrogate_log_likelihood core.py:1446-1508, prior =

@@ -1,8 +1,9 @@
-"""Launch-per-half-step cost of the DE move against the stretch move at C3 (N = 2000, d = 10, W = 256).
+"""Launch-per-half-step cost of the DE and snooker moves against the stretch move at C3 (N = 2000, d = 10, W = 256).
 
-A move set holding a DEMove runs alabi_ens_run with one launch per half step (the two-partner instantiations of
-ens_half_kernel); the stretch move is measured on the same path (ALABI_ENS_STREAM=0), so the two differ in the proposal's
-construction alone.  Prints the median of --runs timed runs of --steps steps each, in us per half step, as one JSON line.
+A move set holding a DEMove or a SnookerMove runs alabi_ens_run with one launch per half step (the two- and three-partner
+instantiations of ens_half_kernel); the stretch move is measured on the same path (ALABI_ENS_STREAM=0), so the sets differ in
+the proposal's construction alone.  Prints the median of --runs timed runs of --steps steps each, in us per half step, as one
+JSON line.
 
     python tools/prof_moves.py                      # this checkout
     python tools/prof_moves.py --root ../parent     # another checkout (one without alabi_amd.moves measures the stretch run only)
@@ -59,4 +60,11 @@ except ImportError:
 else:
     out["de"] = measure(moves=DEMove())
     out["de_stretch_mix"] = measure(moves=[(DEMove(), 0.5), (StretchMove(), 0.5)])
+    try:
+        from alabi_amd.moves import SnookerMove
+    except ImportError:
+        out["snooker"] = None                       # a checkout without the snooker move
+    else:
+        out["snooker"] = measure(moves=SnookerMove())
+        out["de_snooker_mix"] = measure(moves=[(DEMove(), 0.8), (SnookerMove(), 0.2)])
 print(json.dumps(out))
