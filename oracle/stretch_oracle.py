@@ -116,12 +116,15 @@ def box_lnprior_batch(theta, bounds):
     return np.where(inside, 0.0, -np.inf)
 
 
-def stretch_step_arrays(coords, logp, order, n0, u_z, partner, u_acc, lnprob_batch, a=2.0):
+def stretch_step_arrays(coords, logp, order, n0, u_z, partner, u_acc, lnprob_batch, a=2.0, margin_out=None):
     """One full red-blue step from pre-drawn arrays keyed by walker id.
 
     Follows RedBlueMove.propose / StretchMove.get_proposal:
         zz = ((a-1) u + 1)^2 / a ; factors = (ndim-1) log zz ; q = c[r] - (c[r]-s) zz
         accept iff factors + logp(q) - logp(s) > log(u')
+
+    ``margin_out`` (a list): every half step appends the array factors + logp(q) - logp(s) - log(u') of its proposals, in
+    the order of the active list -- how far each accept test is from a tie (-inf for a proposal outside the box).
     """
     coords = np.array(coords, dtype=np.float64, copy=True)
     logp = np.array(logp, dtype=np.float64, copy=True)
@@ -142,6 +145,8 @@ def stretch_step_arrays(coords, logp, order, n0, u_z, partner, u_acc, lnprob_bat
         with np.errstate(divide="ignore", invalid="ignore"):
             lnpdiff = factors + new_logp - logp[S]
             acc = lnpdiff > np.log(u_acc[S])
+            if margin_out is not None:
+                margin_out.append(lnpdiff - np.log(u_acc[S]))
         coords[S[acc]] = q[acc]
         logp[S[acc]] = new_logp[acc]
         accepted[S[acc]] = True
@@ -208,10 +213,11 @@ def literal_draws_to_arrays(record):
     return order, n0, u_z, partner, u_acc
 
 
-def run_ensemble(p0, nsteps, lnprob_batch, seed, a=2.0, thin_by=1, step0=0, logp0=None, id0=0):
+def run_ensemble(p0, nsteps, lnprob_batch, seed, a=2.0, thin_by=1, step0=0, logp0=None, id0=0, margin_out=None):
     """Array-driven ensemble run with the counter-based draws (device production contract).
 
-    Returns chain[nsteps//thin_by, W, d], chain_logp[.., W], n_accept[W], coords, logp.
+    Returns chain[nsteps//thin_by, W, d], chain_logp[.., W], n_accept[W], coords, logp.  ``margin_out``: see
+    ``stretch_step_arrays``; two arrays per step.
     """
     coords = np.array(p0, dtype=np.float64, copy=True)
     W, d = coords.shape
@@ -222,7 +228,8 @@ def run_ensemble(p0, nsteps, lnprob_batch, seed, a=2.0, thin_by=1, step0=0, logp
     nacc = np.zeros(W, dtype=np.int64)
     for t in range(nsteps):
         order, n0, u_z, partner, u_acc = draw_step_randoms(seed, step0 + t, W, id0)
-        coords, logp, acc = stretch_step_arrays(coords, logp, order, n0, u_z, partner, u_acc, lnprob_batch, a)
+        coords, logp, acc = stretch_step_arrays(coords, logp, order, n0, u_z, partner, u_acc, lnprob_batch, a,
+                                                margin_out=margin_out)
         nacc += acc
         if (t + 1) % thin_by == 0:
             chain[(t + 1) // thin_by - 1] = coords

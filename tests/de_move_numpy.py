@@ -66,9 +66,10 @@ def draw_move_randoms(seed, step, W, cum, g0=1.0, sigma=0.0, id0=0):
     return move, j1, j2, n, gamma
 
 
-def de_step_arrays(coords, logp, order, n0, j1, j2, gamma, u_acc, lnprob_batch):
+def de_step_arrays(coords, logp, order, n0, j1, j2, gamma, u_acc, lnprob_batch, margin_out=None):
     """One full red-blue DE step from pre-drawn arrays keyed by walker id (the contract of alabi_ens_step_with_randoms_de):
-    q = s + gamma (C[j2] - C[j1]); accept iff logp(q) - logp(s) > log(u')."""
+    q = s + gamma (C[j2] - C[j1]); accept iff logp(q) - logp(s) > log(u').  ``margin_out`` (a list): every half step appends
+    logp(q) - logp(s) - log(u') of its proposals, as stretch_step_arrays does."""
     coords = np.array(coords, dtype=np.float64, copy=True)
     logp = np.array(logp, dtype=np.float64, copy=True)
     W = coords.shape[0]
@@ -87,6 +88,8 @@ def de_step_arrays(coords, logp, order, n0, j1, j2, gamma, u_acc, lnprob_batch):
         with np.errstate(divide="ignore", invalid="ignore"):
             lnpdiff = 0.0 + new_logp - logp[S]
             acc = lnpdiff > np.log(u_acc[S])
+            if margin_out is not None:
+                margin_out.append(lnpdiff - np.log(u_acc[S]))
         coords[S[acc]] = q[acc]
         logp[S[acc]] = new_logp[acc]
         accepted[S[acc]] = True
@@ -207,9 +210,11 @@ def draw_steps_batched(seed, step0, nsteps, W, cum, id0=0):
     return dict(order=order, n0=n0, u_z=u_z, partner=j1, u_acc=u_acc, j2=j2, n=n, move=move)
 
 
-def run_ensemble_moves(p0, nsteps, lnprob_batch, seed, moves, thin_by=1, step0=0, logp0=None, id0=0, count_moves=None):
+def run_ensemble_moves(p0, nsteps, lnprob_batch, seed, moves, thin_by=1, step0=0, logp0=None, id0=0, count_moves=None,
+                       margin_out=None):
     """Array-driven run of a move mixture with the counter-based draws, step for step (device production contract).
-    ``moves``: see ``move_table``.  Returns chain, chain_logp, n_accept[W], coords, logp as stretch_oracle.run_ensemble."""
+    ``moves``: see ``move_table``.  Returns chain, chain_logp, n_accept[W], coords, logp as stretch_oracle.run_ensemble.
+    ``margin_out``: see ``de_step_arrays``; two arrays per step."""
     coords = np.array(p0, dtype=np.float64, copy=True)
     W, d = coords.shape
     kinds, cum, tp0, tp1 = move_table(moves, d)
@@ -229,10 +234,11 @@ def run_ensemble_moves(p0, nsteps, lnprob_batch, seed, moves, thin_by=1, step0=0
         order, n0, u_acc = dr["order"][k], dr["n0"], dr["u_acc"][k]
         if kinds[mi] == 0:
             coords, logp, acc = stretch_step_arrays(coords, logp, order, n0, dr["u_z"][k], dr["partner"][k], u_acc, lnprob_batch,
-                                                    tp0[mi])
+                                                    tp0[mi], margin_out=margin_out)
         else:
             gamma = tp0[mi] * (1.0 + tp1[mi] * dr["n"][k])
-            coords, logp, acc = de_step_arrays(coords, logp, order, n0, dr["partner"][k], dr["j2"][k], gamma, u_acc, lnprob_batch)
+            coords, logp, acc = de_step_arrays(coords, logp, order, n0, dr["partner"][k], dr["j2"][k], gamma, u_acc, lnprob_batch,
+                                               margin_out=margin_out)
         nacc += acc
         if (t + 1) % thin_by == 0:
             chain[(t + 1) // thin_by - 1] = coords

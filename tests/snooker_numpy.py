@@ -111,10 +111,12 @@ def snooker_proposal(s, z, z1, z2, gamma):
     return q, n, nq
 
 
-def snooker_step_arrays(coords, logp, order, n0, j1, j2, j3, gamma, u_acc, lnprob_batch, jac=None):
+def snooker_step_arrays(coords, logp, order, n0, j1, j2, j3, gamma, u_acc, lnprob_batch, jac=None, margin_out=None):
     """One full red-blue snooker step from pre-drawn arrays keyed by walker id (the contract of
     alabi_ens_step_with_randoms_snooker).  ``jac``: the multiplier of (ln|q - z| - ln n); None is the move's d - 1, anything else
-    exists for the negative controls of the invariance test only.  Returns coords, logp, accepted and the proposals' lnfac."""
+    exists for the negative controls of the invariance test only.  ``margin_out`` (a list): every half step appends
+    lnfac + lnp(q) - lnp(s) - ln u' of its proposals, as stretch_step_arrays does (NaN for a degenerate proposal).  Returns coords,
+    logp, accepted and the proposals' lnfac."""
     coords = np.array(coords, dtype=np.float64, copy=True)
     logp = np.array(logp, dtype=np.float64, copy=True)
     W, d = coords.shape
@@ -133,6 +135,8 @@ def snooker_step_arrays(coords, logp, order, n0, j1, j2, j3, gamma, u_acc, lnpro
             f = mult * (np.log(nq) - np.log(n))
             lnpdiff = f + new_logp - logp[S]
             acc = lnpdiff > np.log(u_acc[S])                  # false for NaN and for -inf: degenerate proposals are rejected
+            if margin_out is not None:
+                margin_out.append(lnpdiff - np.log(u_acc[S]))
         lnfac[S] = f
         coords[S[acc]] = q[acc]
         logp[S[acc]] = new_logp[acc]
@@ -140,10 +144,11 @@ def snooker_step_arrays(coords, logp, order, n0, j1, j2, j3, gamma, u_acc, lnpro
     return coords, logp, accepted, lnfac
 
 
-def run_ensemble_moves(p0, nsteps, lnprob_batch, seed, moves, thin_by=1, step0=0, logp0=None, id0=0, count_moves=None, jac=None):
+def run_ensemble_moves(p0, nsteps, lnprob_batch, seed, moves, thin_by=1, step0=0, logp0=None, id0=0, count_moves=None, jac=None,
+                       margin_out=None):
     """de_move_numpy.run_ensemble_moves for the three kinds of move (``moves``: see ``move_table``): the array-driven run with
     the counter-based draws, step for step -- the device's production contract.  Returns chain, chain_logp, n_accept[W],
-    coords, logp."""
+    coords, logp.  ``margin_out``: see ``snooker_step_arrays``; two arrays per step."""
     coords = np.array(p0, dtype=np.float64, copy=True)
     W, d = coords.shape
     kinds, cum, tp0, tp1 = move_table(moves, d)
@@ -163,13 +168,14 @@ def run_ensemble_moves(p0, nsteps, lnprob_batch, seed, moves, thin_by=1, step0=0
         order, n0, u_acc = dr["order"][k], dr["n0"], dr["u_acc"][k]
         if kinds[mi] == 0:
             coords, logp, acc = stretch_step_arrays(coords, logp, order, n0, dr["u_z"][k], dr["partner"][k], u_acc, lnprob_batch,
-                                                    tp0[mi])
+                                                    tp0[mi], margin_out=margin_out)
         elif kinds[mi] == 1:
             gamma = tp0[mi] * (1.0 + tp1[mi] * dr["n"][k])
-            coords, logp, acc = dm.de_step_arrays(coords, logp, order, n0, dr["partner"][k], dr["j2"][k], gamma, u_acc, lnprob_batch)
+            coords, logp, acc = dm.de_step_arrays(coords, logp, order, n0, dr["partner"][k], dr["j2"][k], gamma, u_acc, lnprob_batch,
+                                                  margin_out=margin_out)
         else:
             coords, logp, acc, _ = snooker_step_arrays(coords, logp, order, n0, dr["partner"][k], dr["j2"][k], dr["j3"][k], tp0[mi],
-                                                       u_acc, lnprob_batch, jac=jac)
+                                                       u_acc, lnprob_batch, jac=jac, margin_out=margin_out)
         nacc += acc
         if (t + 1) % thin_by == 0:
             chain[(t + 1) // thin_by - 1] = coords
