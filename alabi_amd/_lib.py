@@ -80,6 +80,9 @@ SIGNATURES = {
     "alabi_ens_group_plan": (_i, [_vp, _pi]),
     "alabi_ens_lnprob": (_i, [_vp, _vp, _vp, _vp]),
     "alabi_ens_run": (_i, [_vp, _vp, _vp, _ll, _ll, _i, _d, _vp, _vp, _vp, _vp]),
+    "alabi_ens_last_state": (_i, [_vp, _vp, _vp]),
+    "alabi_ens_restore": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "alabi_ens_boundary_stats": (_i, [_vp, _pll]),
     "alabi_chain_autocorr": (_i, [_vp, _ll, _i, _i, _vp, _vp]),
     "alabi_ens_draw": (_i, [_vp, _ll, _i, _d, _vp]),
     "alabi_ens_half_step": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),

@@ -2,6 +2,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -604,8 +605,13 @@ int alabi_ens_create(alabi_gp* gp, int W, int d, int n_ensembles, const double* 
             if (G > (W + 1) / 2) G = (W + 1) / 2;
             e->stream_grid = G;
             const size_t hist_words = ((size_t)e->chunk_cap + 1) * WT * (d + 2);   // row = coords, logp, accepted
+            const size_t state_words = 1 + (size_t)WT * (d + 1);                   // err | coords | logp
             if (err == hipSuccess) err = hipMalloc(&e->hist, hist_words * sizeof(unsigned long long));
-            if (err == hipSuccess) err = hipMalloc(&e->err, sizeof(int));
+            if (err == hipSuccess) err = hipMalloc(&e->state_dev, state_words * sizeof(unsigned long long));
+            if (err == hipSuccess) err = hipMemset(e->state_dev, 0, state_words * sizeof(unsigned long long));
+            if (err == hipSuccess) err = hipHostMalloc(reinterpret_cast<void**>(&e->state_host), state_words * sizeof(unsigned long long), hipHostMallocDefault);
+            if (err == hipSuccess) err = hipMalloc(&e->save, (size_t)WT * (d + 1) * sizeof(double) + (size_t)WT * sizeof(long long));
+            if (err == hipSuccess) e->err = reinterpret_cast<int*>(e->state_dev);
             e->stream_ok = (err == hipSuccess) ? 1 : 0;
         }
     }
@@ -620,6 +626,7 @@ int alabi_ens_create(alabi_gp* gp, int W, int d, int n_ensembles, const double* 
 int alabi_ens_destroy(alabi_ens* e) {
     if (!e) return ALABI_OK;
     if (e->graph_exec) (void)hipGraphExecDestroy(e->graph_exec);
+    if (e->side_stream) (void)hipStreamSynchronize(e->side_stream);   // draws made ahead for a call that never came
     free_draws(e->draws);
     free_draws(e->draws2);
     free_move_buffers(e->mv);
@@ -631,7 +638,9 @@ int alabi_ens_destroy(alabi_ens* e) {
     if (e->hist) (void)hipFree(e->hist);
     if (e->part) (void)hipFree(e->part);
     if (e->cand) (void)hipFree(e->cand);
-    if (e->err) (void)hipFree(e->err);
+    if (e->state_dev) (void)hipFree(e->state_dev);       // e->err is its first word
+    if (e->state_host) (void)hipHostFree(e->state_host);
+    if (e->save) (void)hipFree(e->save);
     ens_pair_release(e);
     delete e;
     return ALABI_OK;
@@ -694,6 +703,8 @@ int alabi_ens_set_moves(alabi_ens* e, int n, const int* kind, const double* cum,
     e->has_de = de || snooker;                           // more than one partner row: one launch per half step
     e->has_snooker = snooker;
     e->drawn_n = 0;                                      // records drawn under the old move set are not the new set's
+    e->ahead_valid = false;                              // nor are those made ahead for the next stream call
+    e->moves_gen++;
     e->settings_gen++;
     if (e->graph_exec) { (void)hipGraphExecDestroy(e->graph_exec); e->graph_exec = nullptr; }   // captured draw launches carry the old table
     return ALABI_OK;
@@ -837,6 +848,38 @@ static int enqueue_chunk(alabi_ens* e, HalfArgs h, int n, double a, hipStream_t 
     return launch_ens_advance(e, n, s);
 }
 
+// (coords, logp, n_accept) <- what ens_call_prologue_kernel saved at the start of the last persistent call
+static int ens_restore(alabi_ens* e, double* coords, double* logp, long long* n_accept, hipStream_t s) {
+    if (!e->save || !e->save_valid) return ALABI_NOT_COMPUTED;
+    const size_t WT = (size_t)e->W * e->E;
+    const double* sv = e->save;
+    ALABI_HIP_CHECK(hipMemcpyAsync(coords, sv, WT * e->d * sizeof(double), hipMemcpyDeviceToDevice, s));
+    ALABI_HIP_CHECK(hipMemcpyAsync(logp, sv + WT * e->d, WT * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (n_accept && e->save_accept)
+        ALABI_HIP_CHECK(hipMemcpyAsync(n_accept, sv + WT * (e->d + 1), WT * sizeof(long long), hipMemcpyDeviceToDevice, s));
+    return ALABI_OK;
+}
+
+int alabi_ens_restore(alabi_ens* e, double* coords, double* logp, long long* n_accept, void* stream) {
+    if (!e || !coords || !logp) return ALABI_BAD_ARGUMENT;
+    return ens_restore(e, coords, logp, n_accept, as_stream(stream));
+}
+
+int alabi_ens_last_state(alabi_ens* e, double* coords_out, double* logp_out) {
+    if (!e || !coords_out || !logp_out) return ALABI_BAD_ARGUMENT;
+    if (!e->last_state_ok || !e->state_host) return ALABI_NOT_COMPUTED;
+    const size_t WT = (size_t)e->W * e->E;
+    memcpy(coords_out, e->state_host + 1, WT * e->d * sizeof(double));
+    memcpy(logp_out, e->state_host + 1 + WT * e->d, WT * sizeof(double));
+    return ALABI_OK;
+}
+
+int alabi_ens_boundary_stats(alabi_ens* e, long long* out) {
+    if (!e || !out) return ALABI_BAD_ARGUMENT;
+    for (int i = 0; i < 4; ++i) out[i] = e->boundary_stats[i];
+    return ALABI_OK;
+}
+
 int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, long long nsteps, int thin_by,
                   double a, double* chain, double* chain_logp, long long* n_accept, void* stream) {
     if (!e || !coords || !logp || nsteps < 0 || thin_by < 1 || !(a > 1.0)) return ALABI_BAD_ARGUMENT;
@@ -848,6 +891,7 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
     // Persistent dataflow path: training set pinned in registers (Npad <= 2048: 256 compute lanes x up to 4 point pairs), one
     // workgroup per list position.  It synchronises at the end to read the time-out flag.
     e->last_path = 0;
+    e->last_state_ok = false;
     // Which persistent kernel: ens_stream_kernel where the training set fits one workgroup's registers (N <= 2048, small d),
     // ens_group_kernel (training set partitioned over groups of workgroups, matrix-core kernel sums) beyond that;
     // ALABI_ENS_GROUP=0 disables the latter, =1 prefers it wherever its blocking is feasible.
@@ -873,21 +917,28 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
         // a time-out of the pair variant is retried below on ens_stream_kernel, from the walkers saved here, before it is reported.
         const bool use_pair = !use_group && can_stream && ens_pair_ready(e);
         e->last_variant = use_pair ? 1 : 0;
-        const size_t WTs = (size_t)e->W * e->E;
-        if (use_pair) {
-            double* sv = e->pair_save;
-            ALABI_HIP_CHECK(hipMemcpyAsync(sv, coords, WTs * e->d * sizeof(double), hipMemcpyDeviceToDevice, s));
-            ALABI_HIP_CHECK(hipMemcpyAsync(sv + WTs * e->d, logp, WTs * sizeof(double), hipMemcpyDeviceToDevice, s));
-            if (n_accept) ALABI_HIP_CHECK(hipMemcpyAsync(sv + WTs * (e->d + 1), n_accept, WTs * sizeof(long long), hipMemcpyDeviceToDevice, s));
-        }
+        const int prop_clean_rows = use_pair ? e->prop_clean : 0;
+        if (use_pair) e->prop_clean = 0;
         if (use_group && (st = set_run_state(e, step0, 0, s)) != ALABI_OK) return st;
-        ALABI_HIP_CHECK(hipMemsetAsync(e->err, 0, sizeof(int), s));
-        long long remaining = nsteps;
-        // The draws depend on nothing but the step counter: in a call of several chunks those of the next chunk are made on the
+        // The draws depend on nothing but the step counter.  In a call of several chunks those of the next chunk are made on the
         // side stream while this chunk's persistent kernel runs (it occupies half of the CUs), into the buffer set the previous
-        // chunk has released.
-        const bool two_sets = !use_group && nsteps > e->chunk_cap && ens_draw_ahead_ready(e);
+        // chunk has released; behind the call's last persistent kernel the same is done for the first chunk of the NEXT call,
+        // which by then finds them in draws2 if it continues where this one ends (step, a, move table).
+        const bool two_sets = !use_group && ens_draw_ahead_ready(e);
         bool ahead_issued = false;
+        if (!use_group) {
+            const bool hit = two_sets && e->ahead_valid && e->ahead_step == step0 && e->ahead_a == a && e->ahead_moves_gen == e->moves_gen &&
+                             need <= e->ahead_n;
+            // hit or not, the main stream goes on behind the pending launch of the side stream: draws2 is never written from two streams
+            if (e->ahead_pending) ALABI_HIP_CHECK(hipStreamWaitEvent(s, e->ev_drawn, 0));
+            e->ahead_pending = false; e->ahead_valid = false;
+            e->draw_set = hit ? 1 : 0;
+            e->boundary_stats[hit ? 0 : 1]++;
+            if (!hit && (st = launch_ens_draw_at(e, e->draws, need, a, false, step0, s)) != ALABI_OK) return st;
+        }
+        // one launch: the walkers saved (a time-out is repeated from there), the flag cleared, row 0 of the history
+        if ((st = launch_ens_call_prologue(e, coords, logp, n_accept, !use_group, s)) != ALABI_OK) return st;
+        long long remaining = nsteps;
         while (remaining > 0) {
             const int K = (int)(remaining < e->chunk_cap ? remaining : e->chunk_cap);
             const long long done = nsteps - remaining;
@@ -896,42 +947,57 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
                 if ((st = launch_ens_group(e, coords, logp, K, thin_by, chain, chain_logp, n_accept, s)) != ALABI_OK) return st;
                 if ((st = launch_ens_advance(e, K, s)) != ALABI_OK) return st;
             } else {
-                const bool odd = two_sets && ((done / e->chunk_cap) & 1);
-                const bool ahead = two_sets && remaining > K;
-                const DrawBuffers& cur = odd ? e->draws2 : e->draws;
+                const bool last = remaining == K;
+                const bool ahead = two_sets;              // the next chunk's draws, or (last) those of the next call's first chunk
+                const DrawBuffers& cur = e->draw_set ? e->draws2 : e->draws;
                 if (ahead_issued) ALABI_HIP_CHECK(hipStreamWaitEvent(s, e->ev_drawn, 0));
-                else if ((st = launch_ens_draw_at(e, cur, K, a, false, step0 + done, s)) != ALABI_OK) return st;
+                else if (done > 0 && (st = launch_ens_draw_at(e, cur, K, a, false, step0 + done, s)) != ALABI_OK) return st;
                 ahead_issued = false;
-                if (ahead) ALABI_HIP_CHECK(hipEventRecord(e->ev_free, s));   // everything that read the other buffer set is behind this point
+                // everything that read the other buffer set is behind this point.  The draws for the next call go into draws2
+                // whichever set this chunk reads, and start behind its persistent kernel, not beside it
+                if (ahead && !last) ALABI_HIP_CHECK(hipEventRecord(e->ev_free, s));
                 const int fill_rows = (done == 0 && clean_rows < need) ? need : 0;
-                if ((st = use_pair ? launch_ens_pair_kernel(e, cur, coords, logp, K, done == 0, fill_rows, s)
-                                   : launch_ens_stream_kernel(e, cur, coords, logp, K, done == 0, fill_rows, s)) != ALABI_OK)
+                const int prop_fill_rows = (done == 0 && prop_clean_rows < need) ? need : 0;
+                if ((st = use_pair ? launch_ens_pair_kernel(e, cur, K, fill_rows, prop_fill_rows, s)
+                                   : launch_ens_stream_kernel(e, cur, K, fill_rows, s)) != ALABI_OK)
                     return st;
+                if (ahead && last) ALABI_HIP_CHECK(hipEventRecord(e->ev_free, s));
                 if (ahead) {
                     const long long rem2 = remaining - K;
-                    const int K2 = (int)(rem2 < e->chunk_cap ? rem2 : e->chunk_cap);
+                    const int K2 = last ? e->chunk_cap : (int)(rem2 < e->chunk_cap ? rem2 : e->chunk_cap);
                     ALABI_HIP_CHECK(hipStreamWaitEvent(e->side_stream, e->ev_free, 0));
-                    if ((st = launch_ens_draw_at(e, odd ? e->draws : e->draws2, K2, a, false, step0 + done + K, e->side_stream)) != ALABI_OK)
+                    if ((st = launch_ens_draw_at(e, (last || e->draw_set == 0) ? e->draws2 : e->draws, K2, a, false, step0 + done + K,
+                                                 e->side_stream)) != ALABI_OK)
                         return st;
                     ALABI_HIP_CHECK(hipEventRecord(e->ev_drawn, e->side_stream));
-                    ahead_issued = true;
+                    if (last) {
+                        e->ahead_pending = true; e->ahead_valid = true;
+                        e->ahead_step = step0 + nsteps; e->ahead_a = a; e->ahead_moves_gen = e->moves_gen; e->ahead_n = K2;
+                    } else {
+                        ahead_issued = true;
+                    }
                 }
-                if ((st = launch_ens_stream_epilogue(e, coords, logp, K, thin_by, chain, chain_logp, n_accept, step0 + done + K, done, s)) != ALABI_OK)
+                if ((st = launch_ens_stream_epilogue(e, coords, logp, K, thin_by, chain, chain_logp, n_accept, step0 + done + K, done,
+                                                     use_pair, last, s)) != ALABI_OK)
                     return st;
+                if (two_sets) e->draw_set ^= 1;
             }
             remaining -= K;
         }
-        int flag = 0;
-        ALABI_HIP_CHECK(hipMemcpyAsync(&flag, e->err, sizeof(int), hipMemcpyDeviceToHost, s));
+        // one read-back: the flag and, on ens_stream_kernel / ens_pair_kernel, the walkers the last epilogue left beside it
+        const size_t WTs = (size_t)e->W * e->E;
+        const size_t back = use_group ? sizeof(unsigned long long) : (1 + WTs * (e->d + 1)) * sizeof(unsigned long long);
+        ALABI_HIP_CHECK(hipMemcpyAsync(e->state_host, e->state_dev, back, hipMemcpyDeviceToHost, s));
         ALABI_HIP_CHECK(hipStreamSynchronize(s));
+        const int flag = *reinterpret_cast<const int*>(e->state_host);
         e->hist_clean = (!use_group && !flag) ? (clean_rows > need ? clean_rows : need) : 0;
+        if (use_pair) e->prop_clean = !flag ? (prop_clean_rows > need ? prop_clean_rows : need) : 0;
+        e->last_state_ok = !use_group && !flag;
+        if (flag) e->ahead_valid = false;             // (the launch stays pending: the next call waits for it before it draws)
         if (flag && use_pair) {
             // restore the walkers, turn the pair variant off for this handle and run the call again on ens_stream_kernel (the history
             // is marked dirty above, the flag is cleared at the start of the call); a second time-out is reported as before
-            const double* sv = e->pair_save;
-            ALABI_HIP_CHECK(hipMemcpyAsync(coords, sv, WTs * e->d * sizeof(double), hipMemcpyDeviceToDevice, s));
-            ALABI_HIP_CHECK(hipMemcpyAsync(logp, sv + WTs * e->d, WTs * sizeof(double), hipMemcpyDeviceToDevice, s));
-            if (n_accept) ALABI_HIP_CHECK(hipMemcpyAsync(n_accept, sv + WTs * (e->d + 1), WTs * sizeof(long long), hipMemcpyDeviceToDevice, s));
+            if ((st = ens_restore(e, coords, logp, n_accept, s)) != ALABI_OK) return st;
             e->pair_state = -1;
             return alabi_ens_run(e, coords, logp, step0, nsteps, thin_by, a, chain, chain_logp, n_accept, stream);
         }

@@ -179,20 +179,39 @@ struct alabi_ens {
     long long* run_state = nullptr;  // device [4]: [0] first global step of the chunk, [1] steps done before it
     // persistent dataflow path (ens_stream_kernel)
     unsigned long long* hist = nullptr;  // [(chunk_cap+1)][E*W][d+1] version history of every walker
-    int* err = nullptr;                  // [1] spin time-out flag
-    // draws one chunk ahead (multi-chunk stream calls): second set of draw buffers, filled on a library-owned side stream while the
-    // previous chunk's persistent kernel runs (allocated on first use; draws2_state -1: not available, single buffer)
+    int* err = nullptr;                  // [1] spin time-out flag: the first word of state_dev
+    // What a stream call reads back, one copy: [err (one 8-byte word) | coords [E*W, d] | logp [E*W]] on the device (the last chunk's
+    // epilogue writes the walkers there) and the same layout in pinned host memory (alabi_ens_last_state copies from it)
+    unsigned long long* state_dev = nullptr;
+    unsigned long long* state_host = nullptr;
+    bool last_state_ok = false;          // state_host holds the walkers the last alabi_ens_run left (it ended cleanly on ens_stream_kernel / ens_pair_kernel)
+    // (coords, logp, n_accept) at the start of a persistent call (ens_call_prologue_kernel): a time-out of the pair variant is retried
+    // on ens_stream_kernel from here, and alabi_ens_restore hands it back to a caller who repeats the call on another path
+    double* save = nullptr;
+    bool save_valid = false, save_accept = false;       // a save was taken; it holds the acceptance counters too
+    // draws one chunk ahead: second set of draw buffers, filled on a library-owned side stream while the previous chunk's persistent
+    // kernel runs, and at the end of a call for the first chunk of the next (allocated on first use; draws2_state -1: not available,
+    // single buffer, every draw on the main stream)
     alabi::DrawBuffers draws2{};
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_free = nullptr, ev_drawn = nullptr;   // main -> side: the buffer is no longer read; side -> main: the draws are there
     int draws2_state = 0;
+    int draw_set = 0;                    // the set the next chunk's records come from: 0 draws, 1 draws2
+    // the records draws2 holds for a call that has not come yet (drawn behind the last persistent kernel of the previous one): valid for
+    // a call that starts at ahead_step with the same `a` and move table and takes at most ahead_n steps in its first chunk
+    bool ahead_valid = false, ahead_pending = false;    // pending: ev_drawn stands for a launch on the side stream nobody has waited for
+    long long ahead_step = 0, ahead_moves_gen = 0;
+    double ahead_a = 0.0;
+    int ahead_n = 0;
+    long long moves_gen = 0;             // bumped by alabi_ens_set_moves
+    long long boundary_stats[4] = {0, 0, 0, 0};         // alabi_ens_boundary_stats: draw-ahead hits, misses, prop fills, hist fills launched
     int hist_clean = 0;                  // rows 1..hist_clean hold the sentinel (left so by ens_hist_epilogue_kernel); rows beyond are filled before use
+    int prop_clean = 0;                  // the same for prop, whose words the epilogue of a pair chunk resets beside those of hist
     int stream_grid = 0;                 // workgroups per ensemble of the persistent kernel
     int last_path = 0;                   // 1 persistent kernel (ens_stream_kernel), 3 group kernel (ens_group_kernel), 0 one launch per half step
     int stream_ok = 0;                   // eligible: training set fits the lanes' registers, one workgroup per CU
     // pair variant of the persistent kernel (ens_pair_kernel)
     unsigned long long* prop = nullptr;  // [(chunk_cap+1)][E*W][d+2] published proposals, allocated on first use
-    double* pair_save = nullptr;         // (coords, logp, n_accept) at the start of a pair call: a time-out is retried on ens_stream_kernel
 #define ALABI_PAIR_STATS_WORDS 16
     unsigned long long* pair_stats = nullptr;   // [ALABI_PAIR_STATS_WORDS] debug counters: [0, 9) alabi_ens_pair_stats, [9, 15) alabi_ens_pair_stats2; allocated on request
     int pair_state = 0;                  // 0 undecided, 1 ready, -1 off (not eligible, ALABI_ENS_PAIR=0, or after a time-out of this handle)
@@ -322,18 +341,18 @@ int alabi_ens_half_step_hist(alabi_ens* e, const double* coords, const double* l
 // ens_stream.hip: the persistent kernel, the version history around a persistent launch (also the group kernel's)
 bool ens_stream_fits(const alabi_ens* e);
 int ens_stream_ppt(const alabi_ens* e);          // point pairs per compute lane of the persistent kernels (0: does not fit)
-int launch_ens_stream_kernel(alabi_ens* e, const DrawBuffers& rec, double* coords, double* logp, int K, bool first, int fill_rows, hipStream_t s);
+int launch_ens_stream_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill_rows, hipStream_t s);
 int launch_ens_hist_fill(unsigned long long* rows, size_t words, hipStream_t s);
-int launch_ens_stream_prologue(alabi_ens* e, double* coords, double* logp, bool first, int fill_rows, hipStream_t s);
+int launch_ens_call_prologue(alabi_ens* e, const double* coords, const double* logp, const long long* n_accept, bool row0, hipStream_t s);
 int launch_ens_stream_epilogue(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
-                               long long* n_accept, long long step_next, long long done0, hipStream_t s);
+                               long long* n_accept, long long step_next, long long done0, bool clean_prop, bool last, hipStream_t s);
 int launch_ens_hist_prologue(alabi_ens* e, double* coords, double* logp, int K, bool fill, hipStream_t s);
 int launch_ens_hist_epilogue(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
                              long long* n_accept, hipStream_t s);
 // ens_pair.hip: the pair variant of the persistent kernel (two workgroups per list position, both outcomes of a pending update)
 bool ens_pair_ready(alabi_ens* e);
 void ens_pair_release(alabi_ens* e);
-int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, double* coords, double* logp, int K, bool first, int fill_rows, hipStream_t s);
+int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill_rows, int prop_fill_rows, hipStream_t s);
 // ens_group.hip
 bool ens_group_fits(const alabi_ens* e);
 bool ens_group_buffers(alabi_ens* e, hipStream_t s);   // the group kernel's hand-off buffers exist (allocates on first use); false: take another path

@@ -363,9 +363,7 @@ bool ens_pair_ready(alabi_ens* e) {
         const size_t WT = (size_t)e->W * e->E, row = e->d + 2;
         const size_t words = ((size_t)e->chunk_cap + 1) * WT * row;
         if (hipMalloc(&e->prop, words * sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); e->prop = nullptr; return false; }
-        if (hipMalloc(&e->pair_save, (WT * (e->d + 1)) * sizeof(double) + WT * sizeof(long long)) != hipSuccess) {
-            (void)hipGetLastError(); (void)hipFree(e->prop); e->prop = nullptr; e->pair_save = nullptr; return false;
-        }
+        e->prop_clean = 0;
         e->pair_state = 1;
     }
     return true;
@@ -373,20 +371,24 @@ bool ens_pair_ready(alabi_ens* e) {
 
 void ens_pair_release(alabi_ens* e) {
     if (e->prop) (void)hipFree(e->prop);
-    if (e->pair_save) (void)hipFree(e->pair_save);
     if (e->pair_stats) (void)hipFree(e->pair_stats);
-    e->prop = nullptr; e->pair_save = nullptr; e->pair_stats = nullptr;
+    e->prop = nullptr; e->pair_stats = nullptr;
 }
 
-// One chunk of K steps on the pair kernel; the arguments of launch_ens_stream_kernel.  Rows 1..K of prop are refilled with the
-// sentinel in front of every chunk (the epilogue restores the sentinel in hist only).
-int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, double* coords, double* logp, int K, bool first, int fill_rows,
-                           hipStream_t s) {
+// One chunk of K steps on the pair kernel; the arguments of launch_ens_stream_kernel, and prop_fill_rows > 0: rows
+// 1..prop_fill_rows of prop cannot be trusted to hold the sentinel and are refilled (the chunk's epilogue puts it back, as in hist).
+int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill_rows, int prop_fill_rows, hipStream_t s) {
     const int n0 = (e->W + 1) / 2;
-    const int WT = e->W * e->E, row = e->d + 2;
-    int st = launch_ens_stream_prologue(e, coords, logp, first, fill_rows, s);
-    if (st != ALABI_OK) return st;
-    if ((st = launch_ens_hist_fill(e->prop + (size_t)WT * row, (size_t)K * WT * row, s)) != ALABI_OK) return st;
+    const size_t WT = (size_t)e->W * e->E, row = e->d + 2;
+    int st;
+    if (fill_rows > 0) {
+        if ((st = launch_ens_hist_fill(e->hist + WT * row, (size_t)fill_rows * WT * row, s)) != ALABI_OK) return st;
+        e->boundary_stats[3]++;
+    }
+    if (prop_fill_rows > 0) {
+        if ((st = launch_ens_hist_fill(e->prop + WT * row, (size_t)prop_fill_rows * WT * row, s)) != ALABI_OK) return st;
+        e->boundary_stats[2]++;
+    }
     PairArgs a{};
     a.s = ens_stream_args(e, rec, K);
     a.prop = e->prop; a.stats = e->pair_stats;

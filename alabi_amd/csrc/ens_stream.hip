@@ -239,6 +239,26 @@ ens_hist_copy_kernel(double* __restrict__ coords, double* __restrict__ logp, uns
     else *src = __longlong_as_double((long long)hist_row[i]);
 }
 
+// The one launch in front of a call's first persistent kernel: (coords, logp, n_accept) -> the handle's save area (what a time-out
+// is repeated from), row 0 of the history <- (coords, logp) as ens_hist_copy_kernel writes it (hist_row0 == nullptr: the group
+// kernel fills its own), and the time-out flag cleared.  One thread per word of a history row.
+__global__ void __launch_bounds__(256)
+ens_call_prologue_kernel(const double* __restrict__ coords, const double* __restrict__ logp, const long long* __restrict__ n_accept,
+                         double* __restrict__ save, unsigned long long* __restrict__ hist_row0, int* __restrict__ err, int WT, int d) {
+    const int i = blockIdx.x * 256 + threadIdx.x, row = d + 2;
+    if (i == 0) *err = 0;
+    if (i >= WT * row) return;
+    const int w = i / row, k = i % row;
+    if (k > d) {
+        if (hist_row0) hist_row0[i] = 0ull;                            // acceptance flag of version 0: unused
+        if (n_accept) reinterpret_cast<long long*>(save + (size_t)WT * (d + 1))[w] = n_accept[w];
+        return;
+    }
+    const double v = (k < d) ? coords[(size_t)w * d + k] : logp[w];
+    save[(k < d) ? (size_t)w * d + k : (size_t)WT * d + w] = v;
+    if (hist_row0) hist_row0[i] = (unsigned long long)__double_as_longlong(v);
+}
+
 // After the persistent kernel: versions 1..K of every walker -> the (thinned) chain, and the acceptance counters.
 // One thread per (version, walker, word); a few MB at HBM speed per launch of K steps.
 __global__ void __launch_bounds__(256)
@@ -270,11 +290,15 @@ ens_hist_chain_kernel(const unsigned long long* __restrict__ hist, int K, int WT
 // groups of VG versions): the row position is the thread index, the thinning phase is divided out once per workgroup, and the
 // acceptance flags are summed per thread over its VG versions -- one atomic per (walker, workgroup).  After a time-out (*err)
 // nothing but run_state is touched: the rows are incomplete, the host restores the walkers and refills the history.
+// prop (pair variant, else nullptr): the published proposals have the history's shape, and the sentinel goes back into the same
+// words of it, so that no chunk needs a fill kernel for it either.  state_out (last chunk of a call, else nullptr): the walkers
+// after the chunk also go to [coords [WT, d] | logp [WT]] there, the block the call reads back.
 #define ALABI_EPI_VG 16
 __global__ void __launch_bounds__(256)
 ens_hist_epilogue_kernel(unsigned long long* __restrict__ hist, int K, int WT, int d, int thin_by, long long step_next, long long done0,
                          const int* __restrict__ err, double* __restrict__ coords, double* __restrict__ logp, double* __restrict__ chain,
-                         double* __restrict__ chain_logp, unsigned long long* __restrict__ n_accept, long long* __restrict__ run_state) {
+                         double* __restrict__ chain_logp, unsigned long long* __restrict__ n_accept, long long* __restrict__ run_state,
+                         unsigned long long* __restrict__ prop, double* __restrict__ state_out) {
     const int k = threadIdx.x, row = d + 2;
     const int w = blockIdx.x * blockDim.y + threadIdx.y;
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && threadIdx.y == 0) { run_state[0] = step_next; run_state[1] = done0 + K; }
@@ -285,7 +309,9 @@ ens_hist_epilogue_kernel(unsigned long long* __restrict__ hist, int K, int WT, i
     long long slot = (done0 + v0) / thin_by;          // version v is stored iff (done0 + v) % thin_by == 0, in slot (done0 + v) / thin_by - 1
     int phase = (int)((done0 + v0) % thin_by);
     const size_t vstride = (size_t)WT * row;
-    unsigned long long* hp = hist + (size_t)v0 * vstride + (size_t)w * row + k;
+    const size_t first = (size_t)v0 * vstride + (size_t)w * row + k;
+    unsigned long long* hp = hist + first;
+    unsigned long long* pp = prop ? prop + first : nullptr;
     unsigned long long nacc = 0;
     for (int v = v0; v <= v1; v += 4, hp += 4 * vstride) {
         unsigned long long word[4];
@@ -295,6 +321,7 @@ ens_hist_epilogue_kernel(unsigned long long* __restrict__ hist, int K, int WT, i
         for (int j = 0; j < 4; ++j) {
             if (v + j > v1) break;
             hp[j * vstride] = ALABI_HIST_EMPTY;
+            if (pp) pp[(size_t)(v - v0 + j) * vstride] = ALABI_HIST_EMPTY;
             if (k == d + 1) nacc += (word[j] == 1ull) ? 1ull : 0ull;
             else {
                 const double val = __longlong_as_double((long long)word[j]);
@@ -306,6 +333,7 @@ ens_hist_epilogue_kernel(unsigned long long* __restrict__ hist, int K, int WT, i
                 if (v + j == K) {                     // the walkers after the chunk, and version 0 of the next one
                     hist[(size_t)w * row + k] = word[j];
                     if (k < d) coords[(size_t)w * d + k] = val; else logp[w] = val;
+                    if (state_out) state_out[(k < d) ? (size_t)w * d + k : (size_t)WT * d + w] = val;
                 }
             }
             if (++phase == thin_by) { phase = 0; ++slot; }
@@ -353,12 +381,14 @@ int launch_ens_hist_fill(unsigned long long* rows, size_t words, hipStream_t s) 
     return ALABI_OK;
 }
 
-// What stands in front of a persistent launch (ens_stream_kernel, ens_pair_kernel): the sentinel in rows that cannot be trusted, row 0
-int launch_ens_stream_prologue(alabi_ens* e, double* coords, double* logp, bool first, int fill_rows, hipStream_t s) {
+// What stands in front of a call's first persistent launch (ens_stream_kernel, ens_pair_kernel, ens_group_kernel): the walkers
+// saved, the flag cleared and, with `row0`, row 0 of the history (later chunks find it there, left by the previous chunk's epilogue)
+int launch_ens_call_prologue(alabi_ens* e, const double* coords, const double* logp, const long long* n_accept, bool row0, hipStream_t s) {
     const int WT = e->W * e->E, row = e->d + 2;
-    if (fill_rows > 0) hipLaunchKernelGGL(ens_hist_fill_kernel, dim3(1024), dim3(256), 0, s, e->hist + (size_t)WT * row, (size_t)fill_rows * WT * row);
-    if (first) hipLaunchKernelGGL(ens_hist_copy_kernel, dim3((WT * row + 255) / 256), dim3(256), 0, s, coords, logp, e->hist, WT, e->d, 1);
+    hipLaunchKernelGGL(ens_call_prologue_kernel, dim3((WT * row + 255) / 256), dim3(256), 0, s, coords, logp, n_accept, e->save,
+                       row0 ? e->hist : nullptr, e->err, WT, e->d);
     ALABI_LAUNCH_CHECK();
+    e->save_valid = true; e->save_accept = n_accept != nullptr;
     return ALABI_OK;
 }
 
@@ -375,13 +405,16 @@ StreamArgs ens_stream_args(alabi_ens* e, const DrawBuffers& rec, int K) {
     return a;
 }
 
-// One chunk of K steps on the persistent kernel, proposal records from `rec`.  `first`: row 0 of the history is taken from
-// (coords, logp) (later chunks of a call find it there, left by the previous chunk's epilogue); fill_rows > 0: rows 1..fill_rows
-// cannot be trusted to hold the sentinel (first use of the handle, after a time-out or the group kernel) and are refilled.
-int launch_ens_stream_kernel(alabi_ens* e, const DrawBuffers& rec, double* coords, double* logp, int K, bool first, int fill_rows,
-                             hipStream_t s) {
-    int st = launch_ens_stream_prologue(e, coords, logp, first, fill_rows, s);
-    if (st != ALABI_OK) return st;
+// One chunk of K steps on the persistent kernel, proposal records from `rec`.  Row 0 of the history holds the walkers (from
+// ens_call_prologue_kernel or the previous chunk's epilogue); fill_rows > 0: rows 1..fill_rows cannot be trusted to hold the
+// sentinel (first use of the handle, after a time-out or the group kernel) and are refilled.
+int launch_ens_stream_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill_rows, hipStream_t s) {
+    int st;
+    if (fill_rows > 0) {
+        const size_t WT = (size_t)e->W * e->E, row = e->d + 2;
+        if ((st = launch_ens_hist_fill(e->hist + WT * row, (size_t)fill_rows * WT * row, s)) != ALABI_OK) return st;
+        e->boundary_stats[3]++;
+    }
     const StreamArgs a = ens_stream_args(e, rec, K);
     e->last_path = 1;
     st = ens_stream_dispatch(e, [&](auto D, auto PPT, auto TMAX, auto GENERIC) {
@@ -393,16 +426,18 @@ int launch_ens_stream_kernel(alabi_ens* e, const DrawBuffers& rec, double* coord
 }
 
 // The chunk's fused epilogue.  step_next / done0: the global step after the chunk and the steps of this call done before it,
-// by value (nothing on the device is read to launch a chunk).
+// by value (nothing on the device is read to launch a chunk).  clean_prop: the chunk ran on ens_pair_kernel, whose proposals get the
+// sentinel back; last: the call's last chunk, whose walkers also go to the block the call reads back.
 int launch_ens_stream_epilogue(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
-                               long long* n_accept, long long step_next, long long done0, hipStream_t s) {
+                               long long* n_accept, long long step_next, long long done0, bool clean_prop, bool last, hipStream_t s) {
     const int WT = e->W * e->E, row = e->d + 2;
     int rp = 16;                                      // words of a row rounded up to a power of two: threadIdx.x is the row position
     while (rp < row) rp <<= 1;
     const int wb = 256 / rp;
     hipLaunchKernelGGL(ens_hist_epilogue_kernel, dim3((WT + wb - 1) / wb, (K + ALABI_EPI_VG - 1) / ALABI_EPI_VG), dim3(rp, wb), 0, s,
                        e->hist, K, WT, e->d, thin_by, step_next, done0, e->err, coords, logp, chain, chain_logp,
-                       reinterpret_cast<unsigned long long*>(n_accept), e->run_state);
+                       reinterpret_cast<unsigned long long*>(n_accept), e->run_state, clean_prop ? e->prop : nullptr,
+                       last ? reinterpret_cast<double*>(e->state_dev + 1) : nullptr);
     ALABI_LAUNCH_CHECK();
     return ALABI_OK;
 }

@@ -334,9 +334,7 @@ class EnsembleSampler:
             if nstore:
                 self._chains.append(chain); self._chain_lps.append(chain_lp); self._thins.append(thin_by)
             return State(self._coords.cpu().numpy(), self._logp.cpu().numpy())
-        # the backup copies are taken on the current stream BEFORE the run stream is made to wait for it: the run's
-        # kernels (which update coords / logp in place) are then ordered after them
-        backup = (self._coords.clone(), self._logp.clone(), self._naccept.clone())
+        # no backup here: a persistent call saves (coords, logp, n_accept) itself, in the launch in front of its first kernel
         self._stream.wait_stream(torch.cuda.current_stream())
 
         def _run():
@@ -350,7 +348,8 @@ class EnsembleSampler:
             # the persistent kernel gave up on a hand-off (e.g. the GPU was shared and its workgroups were not all
             # resident): restore the state and repeat the run with one launch per half step
             self._stream.synchronize()
-            self._coords.copy_(backup[0]); self._logp.copy_(backup[1]); self._naccept.copy_(backup[2])
+            _lib.check(_lib.lib().alabi_ens_restore(self._ens, _lib.ptr(self._coords), _lib.ptr(self._logp), _lib.ptr(self._naccept),
+                                                    C.c_void_p(self._stream.cuda_stream)), "alabi_ens_restore")
             _lib.check(_lib.lib().alabi_ens_set_stream(self._ens, 0), "alabi_ens_set_stream")
             self.stream_fallbacks = getattr(self, "stream_fallbacks", 0) + 1
             st = _run()
@@ -376,6 +375,13 @@ class EnsembleSampler:
             self._chains.append(chain)
             self._chain_lps.append(chain_lp)
             self._thins.append(thin_by)
+        if path.value == 1:
+            # the persistent call has read the walkers back with its time-out flag: no further copy, no synchronisation
+            c = np.empty((self.total_walkers, self.ndim), dtype=np.float64)
+            lp = np.empty(self.total_walkers, dtype=np.float64)
+            _lib.check(_lib.lib().alabi_ens_last_state(self._ens, C.c_void_p(c.ctypes.data), C.c_void_p(lp.ctypes.data)),
+                       "alabi_ens_last_state")
+            return State(c, lp)
         return State(self._coords.cpu().numpy(), self._logp.cpu().numpy())
 
     def reset(self):

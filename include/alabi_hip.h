@@ -281,6 +281,19 @@ int alabi_ens_surrogate(alabi_ens* ens, const double* points, int M, double* lik
 int alabi_ens_run(alabi_ens* ens, double* coords, double* logp, long long step0,
                   long long nsteps, int thin_by, double a, double* chain, double* chain_logp,
                   long long* n_accept, void* stream);
+/* The walkers the last alabi_ens_run left, from the host block that call read back with its time-out flag: coords_out
+ * [E*W,d] and logp_out [E*W] are HOST arrays; no device work, no synchronisation.  ALABI_NOT_COMPUTED unless the last
+ * alabi_ens_run on this handle ended without a time-out on path 1 (ens_stream_kernel / ens_pair_kernel). */
+int alabi_ens_last_state(alabi_ens* ens, double* coords_out /* host */, double* logp_out /* host */);
+/* After ALABI_TIMEOUT: copy back what the call saved at its start -- coords [E*W,d], logp [E*W] and, if the call was given
+ * counters, n_accept [E*W] (device pointers; n_accept may be NULL) -- so that the caller can repeat the call on another path
+ * (alabi_ens_set_stream(ens, 0)).  Enqueues on `stream`.  ALABI_NOT_COMPUTED if no persistent call has run on this handle. */
+int alabi_ens_restore(alabi_ens* ens, double* coords, double* logp, long long* n_accept, void* stream);
+/* Host-side counters of what alabi_ens_run's path 1 did around its persistent kernels since the handle was created:
+ * out[0] calls whose first chunk found its proposal records drawn ahead by the previous call, out[1] calls that had to
+ * draw them first, out[2] fill launches on the published-proposal buffer, out[3] fill launches on the version history
+ * (both are needed on first use and after a time-out only). */
+int alabi_ens_boundary_stats(alabi_ens* ens, long long* out /* host [4] */);
 
 /* sampler.get_autocorr_time(tol=0) -- alabi/mcmc_utils.py:45, alabi/core.py:2387 (emcee.autocorr.integrated_time): the FFT part.
  * chain [n_t, n_w, n_d] (device, as alabi_ens_run stores it) -> acf_mean [n_d, n_t] (device): for every dimension the mean over
