@@ -754,6 +754,26 @@ int alabi_ens_pair_stats2(alabi_ens* e, long long* out, int enable) {
     return ALABI_OK;
 }
 
+int alabi_ens_pair_stats3(alabi_ens* e, long long* out, int enable) {
+    if (!e || !out) return ALABI_BAD_ARGUMENT;
+    int st;
+    if (enable && (st = pair_stats_alloc(e)) != ALABI_OK) return st;
+    for (int i = 0; i < 20; ++i) out[i] = 0;
+    if (!e->pair_stats) return ALABI_OK;
+    ALABI_HIP_CHECK(hipDeviceSynchronize());
+    long long raw[20];                                // per role, by lane of the kernel's counter: [0] verdict looks, [2..4] verdict bins,
+                                                      // [5] input looks, [6] inputs complete without a reload, [7..9] input bins
+    ALABI_HIP_CHECK(hipMemcpy(raw, e->pair_stats + 16, 20 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int r = 0; r < 2; ++r) {
+        const long long* q = raw + 10 * r;
+        long long* o = out + 10 * r;
+        o[0] = q[2] + q[3] + q[4]; o[1] = q[0]; o[2] = q[2]; o[3] = q[3]; o[4] = q[4];
+        o[5] = q[7] + q[8] + q[9]; o[6] = q[5]; o[7] = q[7]; o[8] = q[8]; o[9] = q[9];
+    }
+    ALABI_HIP_CHECK(hipMemset(e->pair_stats + 16, 0, 20 * sizeof(unsigned long long)));
+    return ALABI_OK;
+}
+
 int alabi_ens_last_path(alabi_ens* e, int* path) {
     if (!e || !path) return ALABI_BAD_ARGUMENT;
     *path = e->last_path;

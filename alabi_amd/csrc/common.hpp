@@ -212,8 +212,8 @@ struct alabi_ens {
     int stream_ok = 0;                   // eligible: training set fits the lanes' registers, one workgroup per CU
     // pair variant of the persistent kernel (ens_pair_kernel)
     unsigned long long* prop = nullptr;  // [(chunk_cap+1)][E*W][d+2] published proposals, allocated on first use
-#define ALABI_PAIR_STATS_WORDS 16
-    unsigned long long* pair_stats = nullptr;   // [ALABI_PAIR_STATS_WORDS] debug counters: [0, 9) alabi_ens_pair_stats, [9, 15) alabi_ens_pair_stats2; allocated on request
+#define ALABI_PAIR_STATS_WORDS 36
+    unsigned long long* pair_stats = nullptr;   // [ALABI_PAIR_STATS_WORDS] debug counters: [0, 9) alabi_ens_pair_stats, [9, 15) alabi_ens_pair_stats2, [16, 36) alabi_ens_pair_stats3; allocated on request
     int pair_state = 0;                  // 0 undecided, 1 ready, -1 off (not eligible, ALABI_ENS_PAIR=0, or after a time-out of this handle)
     int last_variant = 0;                // persistent kernel of the last stream call: 0 ens_stream_kernel, 1 ens_pair_kernel
     // group kernel (ens_group_kernel: training set partitioned over the members of a group, proposals streamed through)

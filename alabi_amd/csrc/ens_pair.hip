@@ -38,7 +38,7 @@ struct PairArgs {
     unsigned long long* prop;    // [(K+1)][E*W][d+2] published proposals (words [0, d) of a row are read); rows 1..K pre-filled with ALABI_HIST_EMPTY
     unsigned long long* stats;   // nullptr, or [3 classes][3]: items, rows stored by R, rows stored by A, then [2 roles][2]: items, items
                                  // whose inputs the fetch-ahead had complete, then 2 words kept for the slot counters of alabi_ens_pair_stats2
-                                 // (debug; accumulated outside the chain)
+                                 // then [2 roles][10]: the look counters of alabi_ens_pair_stats3, by lane of st_look (debug; accumulated outside the chain)
 };
 
 #ifdef ALABI_PAIR_PROF
@@ -125,7 +125,14 @@ ens_pair_kernel(PairArgs pa) {
         // ---- hand-off wave: poll -> proposal -> LDS -> A -> (prior term, next decode, VERDICT poll + next inputs, candidate rows) -> B -> accept -> store
         const int n0_lane = lane < p.d ? lane : p.d, n1_lane = lane < p.d ? lane : p.d - 1;
         const int out_lane = lane <= p.d ? lane : p.d + 1, ver_lane = lane == p.d ? p.d : p.d + 1;
-        const long long prop_off = (long long)(pa.prop - p.hist);   // one base pointer: every address stays a global one
+        long long prop_off = (long long)(pa.prop - p.hist);         // one base pointer: every address stays a global one
+        // The generic kernels carry KernelFn in scalar registers and have none to spare, while this wave has vector registers to
+        // spare: there, two wave-uniform values that the items only add to lane addresses are parked in vector registers -- the
+        // offset of prop, and the counters' address, which also says whether they are on.  (The squared-exponential kernels
+        // hold more of the training set per lane and have the scalar registers instead.)
+        unsigned long long* stats_v = pa.stats;
+        if (GENERIC) asm volatile("" : "+v"(prop_off), "+v"(stats_v));
+        auto stats_on = [&] { return __builtin_amdgcn_readfirstlane((int)((unsigned long long)stats_v >> 32)) != 0; };   // (a device address)
         // the next item, decoded ahead
         int n_mode = 0, n_own_a = 0;                  // mode 0 evaluate (the winner is known), 1 speculate, 2 skip; A reads a fresh own row
         double n_zz = 0.0;
@@ -165,7 +172,9 @@ ens_pair_kernel(PairArgs pa) {
         const bool needc = lane < p.d;
         const unsigned long long coord_lanes = (1ull << p.d) - 1;
         int st_items = 0, st_rows = 0;                // debug counters: lane c counts the items of class c
-        int st_all = 0, st_ahead = 0;                 // ... every lane: items, items whose inputs the fetch-ahead had complete
+        int st_look = 0;                              // ... by lane (one compare per counter: the kernel has no scalar register for more masks).  Lane 0: looks of the verdict polls, lanes 2, 3, 4: polls decided at look 1, 2, 3 or
+                                                      //     later; lane 5: looks (reloads) of the input polls, lanes 6..9: polls decided
+                                                      //     without a reload, at look 1, 2, 3 or later
         // The next item's input words, fetched ahead in this item's idle window (item 0: nothing fetched, the sentinel).  Every
         // word of hist and prop goes from the sentinel to its value once per launch, so a fetched word that is not the sentinel
         // is final; a lane that still holds the sentinel sends the wave to the poll below.
@@ -186,7 +195,11 @@ ens_pair_kernel(PairArgs pa) {
                 asm volatile("" : "+v"(ws), "+v"(wc));   // waited for here, not in front of the first test
             });
             // debug counters, in registers (here: the count does not stay live in a scalar register)
-            if (pa.stats) { st_all += 1; st_ahead += (loads == 0); }
+            if (stats_on()) {
+                int lv = loads;
+                asm volatile("" : "+v"(lv));
+                st_look += (lane == 5 ? lv : 0) + (lane == min(lv, 3) + 6);
+            }
 #ifdef ALABI_PAIR_PROF
             prof[11] += (loads == 0);
 #endif
@@ -243,6 +256,8 @@ ens_pair_kernel(PairArgs pa) {
             // The next item's input words (decoded above) are fetched in the same window: with every look of the verdict poll,
             // else once -- a round trip that would otherwise stand in front of the next item although its rows are long there.
             int win = mode == 0;
+            int v_looks = 0;                          // looks of this item's verdict poll, counted in a vector register (debug counters)
+            asm volatile("" : "+v"(v_looks));
 #ifdef ALABI_PAIR_PROF
             const long long c2v = wall_clock64();
 #endif
@@ -252,6 +267,7 @@ ens_pair_kernel(PairArgs pa) {
                     vw = ld_sc1(ver);
                     a_ws = ld_sc1(n_hw);
                     a_wc = ld_sc1(n_hc);
+                    v_looks += 1;
                     return __builtin_amdgcn_ballot_w64(vw == ALABI_HIST_EMPTY) != 0;
                 });
                 if (__builtin_expect(vpend, 0)) {     // time-out: the last proposal, nothing stored
@@ -284,7 +300,10 @@ ens_pair_kernel(PairArgs pa) {
             const bool takes_lp = all_in && lane == p.d;
             if (pending) win = 0;
             // debug counters, in registers; R sees every item
-            if (pa.stats) { st_items += (cls == lane); st_rows += (cls == lane && win); }
+            if (stats_on()) {
+                st_items += (cls == lane); st_rows += (cls == lane && win);
+                st_look += (lane == 0 ? v_looks : 0) + (lane == min(v_looks, 3) + 1);   // (no verdict poll: lane 1, which nobody reads)
+            }
             size_t ow = out_word;
             asm volatile("" : "+v"(ow), "+v"(w_rej), "+v"(w_acc), "+v"(lp_old), "+v"(lnfac), "+v"(lnu), "+v"(prior_q), "+v"(part));
             __builtin_amdgcn_sched_barrier(0);
@@ -307,10 +326,15 @@ ens_pair_kernel(PairArgs pa) {
               if (mode == 1) { prof[5] += c2w - c2v; prof[6] += 1; } }
 #endif
         }
-        if (pa.stats && lane < 3) {
-            if (!role_a) atomicAdd(pa.stats + 3 * lane, (unsigned long long)st_items);
-            atomicAdd(pa.stats + 3 * lane + 1 + role_a, (unsigned long long)st_rows);
-            if (lane < 2) atomicAdd(pa.stats + 9 + 2 * role_a + lane, (unsigned long long)(lane ? st_ahead : st_all));
+        if (stats_on() && lane < 3) {
+            if (!role_a) atomicAdd(stats_v + 3 * lane, (unsigned long long)st_items);
+            atomicAdd(stats_v + 3 * lane + 1 + role_a, (unsigned long long)st_rows);
+        }
+        if (stats_on() && lane < 10) {
+            atomicAdd(stats_v + 16 + 10 * role_a + lane, (unsigned long long)st_look);
+            // alabi_ens_pair_stats2: every item is in one of the input poll's bins, the items fetched complete are the first of them
+            if (lane >= 6) atomicAdd(stats_v + 9 + 2 * role_a, (unsigned long long)st_look);
+            if (lane == 6) atomicAdd(stats_v + 10 + 2 * role_a, (unsigned long long)st_look);
         }
 #ifdef ALABI_PAIR_PROF
         if (tid == 0 && b == 3 && blockIdx.y == 0) {

@@ -260,6 +260,13 @@ int alabi_ens_pair_stats(alabi_ens* ens, long long* out /* host [9] */, int rese
  * while the proposal array has one slot.  enable != 0 switches counting on if it is not
  * (from the next run on); the counters are zeroed after reading.  Synchronises the device. */
 int alabi_ens_pair_stats2(alabi_ens* ens, long long* out /* host [6] */, int enable);
+/* Look counters of ens_pair_kernel's two polls, per role (r = 0: the workgroups that assume "rejected", r = 1: "accepted"):
+ * out[10 r + 0] class-1 items that polled the verdict, [10 r + 1] the looks (tests of a loaded verdict word) of those polls,
+ * [10 r + 2], [10 r + 3], [10 r + 4] the polls decided at look 1, at look 2, at look 3 or later (a poll that timed out counts by
+ * its last look); [10 r + 5 .. 10 r + 9] the same for the input poll at the top of an item, over the items whose inputs the
+ * fetch-ahead did not have complete (a look is a reload).  enable != 0 switches counting on if it is not (from the next run
+ * on); the counters are zeroed after reading.  Synchronises the device. */
+int alabi_ens_pair_stats3(alabi_ens* ens, long long* out /* host [20] */, int enable);
 /* Blocking of the last group-kernel launch of alabi_ens_run (zeros before the first one), so a parity test can pin WHICH
  * instantiation of ens_group_kernel it compared with the oracle: out[0] Q (16-proposal tiles per group), [1] G (members per
  * group), [2] NG (groups per ensemble), [3] RT (point tiles per wave held in registers), [4] tpm (point tiles per member),

@@ -2,20 +2,34 @@
 both workgroups of one pair, the verdict poll of the speculative items, the publish -> detect times of the proposal array and
 of the verdict, and the items whose inputs the fetch-ahead of the previous item had complete, so that the input poll was skipped
 (needs a build with -DALABI_PAIR_PROF: see tools/README.md).  "detected" is the stamp behind the input poll: for an item whose
-inputs were fetched ahead it is the top of the item, not the arrival of the words."""
+inputs were fetched ahead it is the top of the item, not the arrival of the words.
+Every build: the looks of the verdict poll and of the input poll (alabi_ens_pair_stats3), for all pairs.  PROF_CONFIG selects
+C1, C2 or C3 (default), PROF_N the size of the training set."""
 import ctypes, sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from alabi_amd import EnsembleSampler, HipGP, _lib
 from alabi_amd.workloads import make_config
-cfg = make_config("C3", N=int(os.environ.get("PROF_N", "2000")))
+name = os.environ.get("PROF_CONFIG", "C3")
+cfg = make_config(name, N=int(os.environ["PROF_N"]) if "PROF_N" in os.environ else None)
 h = cfg["hyper"]
 gp = HipGP(cfg["d"], h["mean"], h["log_white_noise"], h["log_amp"], h["log_M"]); gp.compute(cfg["X"])
 s = EnsembleSampler(cfg["W"], cfg["d"], gp, cfg["y"], cfg["bounds"], seed=1)
 s.run_mcmc(cfg["p0"], 1024); torch.cuda.synchronize()
+looks = (ctypes.c_longlong * 20)()
+_lib.check(_lib.lib().alabi_ens_pair_stats3(s._ens, looks, 1), "alabi_ens_pair_stats3")     # counting on, from the next run
 t0 = time.perf_counter(); s.run_mcmc(None, 1024); torch.cuda.synchronize(); dt = time.perf_counter() - t0
-out = (ctypes.c_longlong * 26)()
 L = _lib.lib()
+_lib.check(L.alabi_ens_pair_stats3(s._ens, looks, 0), "alabi_ens_pair_stats3")
+print(name, "path", s.last_path, "variant", s.last_stream_variant, "wall us/half-step (counting on)", 1e6 * dt / 2048)
+for role, base in (("R (assumes rejected)", 0), ("A (assumes accepted)", 10)):
+    for poll, q in (("verdict poll, class-1 items", looks[base:base + 5]), ("input poll, items not fetched complete", looks[base + 5:base + 10])):
+        n = max(q[0], 1)
+        print(f"  {role:22s} {poll:40s} polls {q[0]:8d}  looks {q[1]:8d} ({q[1] / n:5.2f} per poll)  decided at look 1: {q[2]:8d} "
+              f"({100.0 * q[2] / n:5.1f}%)  look 2: {q[3]:8d} ({100.0 * q[3] / n:5.1f}%)  look >= 3: {q[4]:8d} ({100.0 * q[4] / n:5.1f}%)")
+if not hasattr(L, "alabi_debug_pair_prof"):
+    sys.exit(0)                                      # not a -DALABI_PAIR_PROF build: no stamps
+out = (ctypes.c_longlong * 26)()
 L.alabi_debug_pair_prof.argtypes = [ctypes.POINTER(ctypes.c_longlong)]
 print("rc", L.alabi_debug_pair_prof(out), "path", s.last_path, "variant", s.last_stream_variant, "wall us/half-step", 1e6 * dt / 2048)
 v = list(out)
