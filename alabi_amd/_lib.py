@@ -78,6 +78,8 @@ SIGNATURES = {
     "alabi_ens_pair_stats": (_i, [_vp, _pll, _i]),
     "alabi_ens_pair_stats2": (_i, [_vp, _pll, _i]),
     "alabi_ens_pair_stats3": (_i, [_vp, _pll, _i]),
+    "alabi_ens_place_stats": (_i, [_vp, _pll, _i]),
+    "alabi_ens_export_placement": (_i, [_vp, _ll, _i, _d, _vp, _vp, _vp, _vp]),
     "alabi_ens_group_plan": (_i, [_vp, _pi]),
     "alabi_ens_lnprob": (_i, [_vp, _vp, _vp, _vp]),
     "alabi_ens_run": (_i, [_vp, _vp, _vp, _ll, _ll, _i, _d, _vp, _vp, _vp, _vp]),

@@ -485,6 +485,8 @@ static void free_draws(DrawBuffers& b) {
     if (b.packed) (void)hipFree(b.packed);
     if (b.pos_of) (void)hipFree(b.pos_of);
     if (b.link) (void)hipFree(b.link);
+    if (b.packed_x) (void)hipFree(b.packed_x);
+    if (b.place) (void)hipFree(b.place);
     b = DrawBuffers{};
 }
 
@@ -558,6 +560,8 @@ static DrawBuffers offset_draws(const DrawBuffers& b, size_t off) {
     DrawBuffers r = b;
     r.order += off; r.cw += off; r.zz += off; r.lnfac += off; r.lnu += off;
     r.partner += off; r.u_z += off; r.u_acc += off; r.packed += 4 * off; r.pos_of += off; r.link += 2 * off;
+    if (r.packed_x) r.packed_x += 4 * off;
+    if (r.place) r.place += off;
     return r;
 }
 
@@ -587,6 +591,10 @@ int alabi_ens_create(alabi_gp* gp, int W, int d, int n_ensembles, const double* 
     long long cap = (4LL << 20) / WT;
     if (cap > 1024) cap = 1024;
     if (cap < 16) cap = 16;
+    if (const char* env = getenv("ALABI_ENS_CHUNK")) {      // a shorter chunk (tests of the chunk boundary at few steps)
+        const long long v = atoll(env);
+        if (v >= 2 && v < cap) cap = v;
+    }
     e->chunk_cap = (int)cap;
     const size_t n = (size_t)e->chunk_cap * WT;
     DrawBuffers& b = e->draws;
@@ -739,6 +747,32 @@ int alabi_ens_pair_stats(alabi_ens* e, long long* out, int reset) {
     ALABI_HIP_CHECK(hipDeviceSynchronize());
     ALABI_HIP_CHECK(hipMemcpy(out, e->pair_stats, 9 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (reset) ALABI_HIP_CHECK(hipMemset(e->pair_stats, 0, 9 * sizeof(unsigned long long)));
+    return ALABI_OK;
+}
+
+int alabi_ens_place_stats(alabi_ens* e, long long* out, int reset) {
+    if (!e || !out) return ALABI_BAD_ARGUMENT;
+    out[0] = e->place_state > 0; out[1] = out[2] = 0;
+    if (!e->place_stats) return ALABI_OK;
+    ALABI_HIP_CHECK(hipDeviceSynchronize());
+    ALABI_HIP_CHECK(hipMemcpy(out + 1, e->place_stats, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (reset) ALABI_HIP_CHECK(hipMemset(e->place_stats, 0, 2 * sizeof(unsigned long long)));
+    return ALABI_OK;
+}
+
+int alabi_ens_export_placement(alabi_ens* e, long long step0, int nsteps, double a, int* place, unsigned long long* packed,
+                               unsigned long long* packed_x, void* stream) {
+    if (!e || !place || nsteps <= 0 || nsteps > e->chunk_cap || !(a > 1.0)) return ALABI_BAD_ARGUMENT;
+    if (e->place_state <= 0) return ALABI_NOT_COMPUTED;
+    hipStream_t s = as_stream(stream);
+    int st;
+    if ((st = launch_ens_draw_at(e, e->draws, nsteps, a, false, step0, s)) != ALABI_OK) return st;
+    if ((st = launch_ens_place(e, e->draws, nsteps, false, s)) != ALABI_OK) return st;
+    e->drawn_n = 0;                                   // (the buffers no longer hold what alabi_ens_draw put there)
+    const size_t n = (size_t)nsteps * e->W * e->E;
+    ALABI_HIP_CHECK(hipMemcpyAsync(place, e->draws.place, n * sizeof(int), hipMemcpyDeviceToDevice, s));
+    if (packed) ALABI_HIP_CHECK(hipMemcpyAsync(packed, e->draws.packed, 4 * n * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+    if (packed_x) ALABI_HIP_CHECK(hipMemcpyAsync(packed_x, e->draws.packed_x, 4 * n * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
     return ALABI_OK;
 }
 
@@ -945,6 +979,9 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
         // chunk has released; behind the call's last persistent kernel the same is done for the first chunk of the NEXT call,
         // which by then finds them in draws2 if it continues where this one ends (step, a, move table).
         const bool two_sets = !use_group && ens_draw_ahead_ready(e);
+        // Pair kernel: every chunk's records go through ens_place_kernel right behind their draws, on the stream that drew them.
+        // A time-out's second run is on ens_stream_kernel and reads the records as they were drawn.
+        const bool place = use_pair && ens_place_ready(e);
         bool ahead_issued = false;
         if (!use_group) {
             const bool hit = two_sets && e->ahead_valid && e->ahead_step == step0 && e->ahead_a == a && e->ahead_moves_gen == e->moves_gen &&
@@ -955,6 +992,7 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
             e->draw_set = hit ? 1 : 0;
             e->boundary_stats[hit ? 0 : 1]++;
             if (!hit && (st = launch_ens_draw_at(e, e->draws, need, a, false, step0, s)) != ALABI_OK) return st;
+            if (place && !(hit && e->ahead_placed) && (st = launch_ens_place(e, hit ? e->draws2 : e->draws, need, true, s)) != ALABI_OK) return st;
         }
         // one launch: the walkers saved (a time-out is repeated from there), the flag cleared, row 0 of the history
         if ((st = launch_ens_call_prologue(e, coords, logp, n_accept, !use_group, s)) != ALABI_OK) return st;
@@ -969,16 +1007,19 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
             } else {
                 const bool last = remaining == K;
                 const bool ahead = two_sets;              // the next chunk's draws, or (last) those of the next call's first chunk
-                const DrawBuffers& cur = e->draw_set ? e->draws2 : e->draws;
+                DrawBuffers& cur = e->draw_set ? e->draws2 : e->draws;
                 if (ahead_issued) ALABI_HIP_CHECK(hipStreamWaitEvent(s, e->ev_drawn, 0));
-                else if (done > 0 && (st = launch_ens_draw_at(e, cur, K, a, false, step0 + done, s)) != ALABI_OK) return st;
+                else if (done > 0) {
+                    if ((st = launch_ens_draw_at(e, cur, K, a, false, step0 + done, s)) != ALABI_OK) return st;
+                    if (place && (st = launch_ens_place(e, cur, K, true, s)) != ALABI_OK) return st;
+                }
                 ahead_issued = false;
                 // everything that read the other buffer set is behind this point.  The draws for the next call go into draws2
                 // whichever set this chunk reads, and start behind its persistent kernel, not beside it
                 if (ahead && !last) ALABI_HIP_CHECK(hipEventRecord(e->ev_free, s));
                 const int fill_rows = (done == 0 && clean_rows < need) ? need : 0;
                 const int prop_fill_rows = (done == 0 && prop_clean_rows < need) ? need : 0;
-                if ((st = use_pair ? launch_ens_pair_kernel(e, cur, K, fill_rows, prop_fill_rows, s)
+                if ((st = use_pair ? launch_ens_pair_kernel(e, cur, K, fill_rows, prop_fill_rows, place, s)
                                    : launch_ens_stream_kernel(e, cur, K, fill_rows, s)) != ALABI_OK)
                     return st;
                 if (ahead && last) ALABI_HIP_CHECK(hipEventRecord(e->ev_free, s));
@@ -986,13 +1027,14 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
                     const long long rem2 = remaining - K;
                     const int K2 = last ? e->chunk_cap : (int)(rem2 < e->chunk_cap ? rem2 : e->chunk_cap);
                     ALABI_HIP_CHECK(hipStreamWaitEvent(e->side_stream, e->ev_free, 0));
-                    if ((st = launch_ens_draw_at(e, (last || e->draw_set == 0) ? e->draws2 : e->draws, K2, a, false, step0 + done + K,
-                                                 e->side_stream)) != ALABI_OK)
-                        return st;
+                    DrawBuffers& into = (last || e->draw_set == 0) ? e->draws2 : e->draws;
+                    if ((st = launch_ens_draw_at(e, into, K2, a, false, step0 + done + K, e->side_stream)) != ALABI_OK) return st;
+                    if (place && (st = launch_ens_place(e, into, K2, !last, e->side_stream)) != ALABI_OK) return st;
                     ALABI_HIP_CHECK(hipEventRecord(e->ev_drawn, e->side_stream));
                     if (last) {
                         e->ahead_pending = true; e->ahead_valid = true;
                         e->ahead_step = step0 + nsteps; e->ahead_a = a; e->ahead_moves_gen = e->moves_gen; e->ahead_n = K2;
+                        e->ahead_placed = place;
                     } else {
                         ahead_issued = true;
                     }

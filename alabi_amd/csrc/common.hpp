@@ -122,6 +122,8 @@ struct DrawBuffers {
     unsigned long long* packed;   // 4 words per list position: walker | partner << 32, zz, lnfac, lnu (persistent kernel)
     int* pos_of;     // list position (0..W-1 within the ensemble) of every walker, keyed by global walker id (inverse of `order`)
     unsigned long long* link;     // group kernel: 2 words per list position, where the two rows the proposal reads were produced (ens_link_kernel)
+    unsigned long long* packed_x; // pair kernel with placement: `packed`, every half step permuted so that position = pair (ens_place_kernel);
+    int* place;                   // ... and the pair of every item, by list position.  Both allocated on first use.
 };
 
 // Proposal moves (emcee's `moves=`): one move per step and ensemble, chosen by ens_draw_kernel from cumulative weights.
@@ -216,6 +218,10 @@ struct alabi_ens {
     unsigned long long* pair_stats = nullptr;   // [ALABI_PAIR_STATS_WORDS] debug counters: [0, 9) alabi_ens_pair_stats, [9, 15) alabi_ens_pair_stats2, [16, 36) alabi_ens_pair_stats3; allocated on request
     int pair_state = 0;                  // 0 undecided, 1 ready, -1 off (not eligible, ALABI_ENS_PAIR=0, or after a time-out of this handle)
     int last_variant = 0;                // persistent kernel of the last stream call: 0 ens_stream_kernel, 1 ens_pair_kernel
+    // placement of the pair kernel's items by XCD class (ens_place.hip)
+    int place_state = 0;                 // 0 undecided, 1 on, -1 off (n0 % 8 != 0, odd W, W > 256, ALABI_ENS_PLACE=0, no memory)
+    unsigned long long* place_stats = nullptr;   // [2] items with a preferred class, items placed on it (every pre-pass of a run adds)
+    bool ahead_placed = false;           // the records drawn ahead for the next call have been through ens_place_kernel
     // group kernel (ens_group_kernel: training set partitioned over the members of a group, proposals streamed through)
     unsigned long long* part = nullptr;  // [2 chunk_cap][E][NG][G][16 Q] partial kernel sums (allocated on first use)
     size_t part_words = 0;
@@ -352,7 +358,9 @@ int launch_ens_hist_epilogue(alabi_ens* e, double* coords, double* logp, int K, 
 // ens_pair.hip: the pair variant of the persistent kernel (two workgroups per list position, both outcomes of a pending update)
 bool ens_pair_ready(alabi_ens* e);
 void ens_pair_release(alabi_ens* e);
-int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill_rows, int prop_fill_rows, hipStream_t s);
+int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill_rows, int prop_fill_rows, bool placed, hipStream_t s);
+bool ens_place_ready(alabi_ens* e);      // ens_place.hip; the caller has checked ens_pair_ready
+int launch_ens_place(alabi_ens* e, DrawBuffers& set, int K, bool count, hipStream_t s);   // allocates set.packed_x / set.place on first use
 // ens_group.hip
 bool ens_group_fits(const alabi_ens* e);
 bool ens_group_buffers(alabi_ens* e, hipStream_t s);   // the group kernel's hand-off buffers exist (allocates on first use); false: take another path

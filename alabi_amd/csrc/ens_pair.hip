@@ -39,6 +39,7 @@ struct PairArgs {
     unsigned long long* stats;   // nullptr, or [3 classes][3]: items, rows stored by R, rows stored by A, then [2 roles][2]: items, items
                                  // whose inputs the fetch-ahead had complete, then 2 words kept for the slot counters of alabi_ens_pair_stats2
                                  // then [2 roles][10]: the look counters of alabi_ens_pair_stats3, by lane of st_look (debug; accumulated outside the chain)
+    int xmap;                    // 1: workgroup -> (pair, role) by XCD class (below); the records are those ens_place_kernel has permuted
 };
 
 #ifdef ALABI_PAIR_PROF
@@ -75,8 +76,12 @@ ens_pair_kernel(PairArgs pa) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool comm = wv == 0, service = wv == nwc + 1, compute = !comm && !service;
-    const int b = blockIdx.x >> 1, e = blockIdx.y, E = gridDim.y;
-    const int role_a = blockIdx.x & 1;                               // 1: this workgroup assumes "accepted"
+    // Workgroups are dealt round-robin over the eight XCDs, so i % 8 labels the workgroups that share one.  With the XCD map
+    // (n0 % 8 == 0) both roles of a pair, and all pairs with equal pair % 8, carry one label: ens_place_kernel hands an item to
+    // a pair of the class that made its fresh input row.  For speed only: any map that is a bijection computes the same chain.
+    const int xk = blockIdx.x >> 3;
+    const int b = pa.xmap ? (xk >> 1) * 8 + (int)(blockIdx.x & 7) : (int)(blockIdx.x >> 1), e = blockIdx.y, E = gridDim.y;
+    const int role_a = pa.xmap ? xk & 1 : blockIdx.x & 1;            // 1: this workgroup assumes "accepted"
     const int WT = p.W * E, row = p.d + 2;
 #ifdef ALABI_PAIR_PROF
     long long prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -396,12 +401,14 @@ bool ens_pair_ready(alabi_ens* e) {
 void ens_pair_release(alabi_ens* e) {
     if (e->prop) (void)hipFree(e->prop);
     if (e->pair_stats) (void)hipFree(e->pair_stats);
-    e->prop = nullptr; e->pair_stats = nullptr;
+    if (e->place_stats) (void)hipFree(e->place_stats);
+    e->prop = nullptr; e->pair_stats = nullptr; e->place_stats = nullptr;
 }
 
 // One chunk of K steps on the pair kernel; the arguments of launch_ens_stream_kernel, and prop_fill_rows > 0: rows
 // 1..prop_fill_rows of prop cannot be trusted to hold the sentinel and are refilled (the chunk's epilogue puts it back, as in hist).
-int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill_rows, int prop_fill_rows, hipStream_t s) {
+// placed: ens_place_kernel has run on this chunk's records; the kernel then reads rec.packed_x under the XCD map.
+int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill_rows, int prop_fill_rows, bool placed, hipStream_t s) {
     const int n0 = (e->W + 1) / 2;
     const size_t WT = (size_t)e->W * e->E, row = e->d + 2;
     int st;
@@ -416,6 +423,7 @@ int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill
     PairArgs a{};
     a.s = ens_stream_args(e, rec, K);
     a.prop = e->prop; a.stats = e->pair_stats;
+    if (placed) { a.s.rec.packed = rec.packed_x; a.xmap = 1; }
     e->last_path = 1;
     st = ens_stream_dispatch(e, [&](auto D, auto PPT, auto TMAX, auto GENERIC) {
         hipLaunchKernelGGL((ens_pair_kernel<D(), PPT(), TMAX(), GENERIC()>), dim3(2 * n0, e->E), dim3(TMAX()), 0, s, a);

@@ -267,6 +267,17 @@ int alabi_ens_pair_stats2(alabi_ens* ens, long long* out /* host [6] */, int ena
  * fetch-ahead did not have complete (a look is a reload).  enable != 0 switches counting on if it is not (from the next run
  * on); the counters are zeroed after reading.  Synchronises the device. */
 int alabi_ens_pair_stats3(alabi_ens* ens, long long* out /* host [20] */, int enable);
+/* Placement of ens_pair_kernel's items by XCD class (ens_place_kernel; on where W is even, W / 2 a multiple of 8 and at most 128,
+ * and ALABI_ENS_PLACE is not 0; decided at the first run): out[0] 1 if placement is on for this handle, out[1] items that had a
+ * preferred class, out[2] items placed on it -- over the records of the calls made so far (records placed ahead for a call that
+ * has not come yet are not counted).  reset != 0 zeroes the counters after reading.  Synchronises the device. */
+int alabi_ens_place_stats(alabi_ens* ens, long long* out /* host [3] */, int reset);
+/* Draws steps step0 .. step0 + nsteps - 1 (nsteps <= the chunk capacity) as ONE chunk into the handle's buffers, runs the
+ * placement pre-pass on them and copies out, by list position: place [nsteps*E*W] the pair every item was handed to and, where
+ * not NULL, the packed records as drawn and as permuted ([nsteps*E*W][4] words each; device pointers).  ALABI_NOT_COMPUTED while
+ * placement is not on.  Leaves nothing drawn for alabi_ens_half_step. */
+int alabi_ens_export_placement(alabi_ens* ens, long long step0, int nsteps, double a, int* place, unsigned long long* packed,
+                               unsigned long long* packed_x, void* stream);
 /* Blocking of the last group-kernel launch of alabi_ens_run (zeros before the first one), so a parity test can pin WHICH
  * instantiation of ens_group_kernel it compared with the oracle: out[0] Q (16-proposal tiles per group), [1] G (members per
  * group), [2] NG (groups per ensemble), [3] RT (point tiles per wave held in registers), [4] tpm (point tiles per member),
