@@ -103,6 +103,9 @@ SIGNATURES = {
     "alabi_ens_export_snooker_draws": (_i, [_vp, _vp, _vp]),
     "alabi_ens_export_partner_ids": (_i, [_vp, _vp, _vp, _vp]),
     "alabi_ens_step_with_randoms_snooker": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _d, _vp, _vp, _vp]),
+    "alabi_ens_step_with_randoms_walk": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "alabi_ens_step_with_randoms_kde": (_i, [_vp, _vp, _vp, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "alabi_ens_kde_singular": (_i, [_vp, _pll]),
     "alabi_ns_create": (_i, [_vp, _i, _pd, _ull, C.POINTER(_vp)]),
     "alabi_ns_destroy": (_i, [_vp]),
     "alabi_ns_set_logp": (_i, [_vp, _d, _d, _i]),

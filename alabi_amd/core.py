@@ -956,8 +956,11 @@ class SurrogateModel(object):
         (the snooker update of ter Braak & Vrugt 2008; ``nwalkers >= 6``), a list of them, or a list of (move, weight) pairs --
         one move is chosen per step.  Multimodal posteriors want ``[(DEMove(), 0.9), (DEMove(gamma0=1.0), 0.1)]``: the stretch
         move alone does not cross between separated modes; the usual companion of DE is ``[(DEMove(), 0.8), (SnookerMove(),
-        0.2)]``.  Any other emcee move raises ``NotImplementedError`` -- emcee's ``DESnookerMove`` among them, whose arithmetic
-        is not the published rule; a ``DEMove`` or ``SnookerMove`` cannot be combined with ``"shard": True``.
+        0.2)]``.  ``alabi_amd.moves.WalkMove(s=None)`` and ``KDEMove(bw_method=None)`` (emcee's own are recognised) use the whole
+        complementary half: a KDE move hops between modes in one step, ``[(KDEMove(), 0.3), (DEMove(), 0.7)]``, and wants many
+        walkers per dimension (``nwalkers >= 2 ndim + 2`` at the least; a warning below ``8 (ndim + 1)``).  Any other emcee move
+        raises ``NotImplementedError`` -- the Metropolis moves and emcee's ``DESnookerMove``, whose arithmetic is not the
+        published rule; none of ``DEMove``, ``SnookerMove``, ``WalkMove``, ``KDEMove`` can be combined with ``"shard": True``.
 
         Several GPUs (the reference's parallel axis is a process pool handed to emcee, core.py:2300, :2322, built at :349-369;
         ``ncore`` / ``pool_method`` have no meaning here): run one process per GPU under ``torch.distributed`` (e.g.

@@ -535,12 +535,23 @@ static void free_move_buffers(MoveBuffers& m) {
     if (m.move) (void)hipFree(m.move);
     if (m.cw3) (void)hipFree(m.cw3);
     if (m.partner3) (void)hipFree(m.partner3);
+    if (m.kind) (void)hipFree(m.kind);
+    if (m.par) (void)hipFree(m.par);
     m = MoveBuffers{};
+}
+
+static void free_kde_buffers(KdeBuffers& k) {
+    if (k.white) (void)hipFree(k.white);
+    if (k.L) (void)hipFree(k.L);
+    if (k.mean) (void)hipFree(k.mean);
+    if (k.flag) (void)hipFree(k.flag);
+    if (k.singular) (void)hipFree(k.singular);
+    k = KdeBuffers{};
 }
 
 // The second-partner arrays of the records (first buffer set), allocated when a move set is first given or a DE step is injected;
 // the third-partner arrays when the set holds a snooker move or a snooker step is injected.
-static int ensure_move_buffers(alabi_ens* e, bool third = false) {
+static int ensure_move_buffers(alabi_ens* e, bool third = false, bool whole_half = false) {
     const size_t n = (size_t)e->chunk_cap * e->W * e->E;
     hipError_t err = hipSuccess;
     if (!e->mv.cw2) {
@@ -552,8 +563,38 @@ static int ensure_move_buffers(alabi_ens* e, bool third = false) {
         err = hipMalloc(&e->mv.cw3, n * sizeof(int));
         if (err == hipSuccess) err = hipMalloc(&e->mv.partner3, n * sizeof(int));
     }
+    if (whole_half && !e->mv.kind && err == hipSuccess) {
+        err = hipMalloc(&e->mv.kind, (size_t)e->chunk_cap * e->E * sizeof(int));
+        if (err == hipSuccess) err = hipMalloc(&e->mv.par, (size_t)e->chunk_cap * e->E * 2 * sizeof(double));
+    }
     if (err != hipSuccess) { free_move_buffers(e->mv); return hip_fail(err, "hipMalloc(move buffers)", __FILE__, __LINE__); }
     return ALABI_OK;
+}
+
+// What the KDE pre-pass leaves for the half-step kernels: whitened rows of the larger half, factor, mean, flag and the counter.
+static int ensure_kde_buffers(alabi_ens* e) {
+    if (e->kde.white) return ALABI_OK;
+    const size_t E = (size_t)e->E, d = (size_t)e->d, ncmax = (size_t)(e->W + 1) / 2;
+    hipError_t err = hipMalloc(&e->kde.white, E * ncmax * d * sizeof(double));
+    if (err == hipSuccess) err = hipMalloc(&e->kde.L, E * d * d * sizeof(double));
+    if (err == hipSuccess) err = hipMalloc(&e->kde.mean, E * d * sizeof(double));
+    if (err == hipSuccess) err = hipMalloc(&e->kde.flag, E * sizeof(int));
+    if (err == hipSuccess) err = hipMalloc(&e->kde.singular, sizeof(unsigned long long));
+    if (err == hipSuccess) err = hipMemset(e->kde.flag, 0, E * sizeof(int));
+    if (err == hipSuccess) err = hipMemset(e->kde.singular, 0, sizeof(unsigned long long));
+    if (err != hipSuccess) { free_kde_buffers(e->kde); return hip_fail(err, "hipMalloc(KDE buffers)", __FILE__, __LINE__); }
+    return ALABI_OK;
+}
+
+// The further-partner arrays and, for a set with a walk or KDE move, the step's kind and the pre-pass buffers, offset to local step t
+static void set_move_args(const alabi_ens* e, HalfArgs& h, size_t t) {
+    const size_t WT = (size_t)e->W * e->E;
+    h.cw2 = e->has_de ? e->mv.cw2 + t * WT : nullptr;
+    h.cw3 = (e->has_snooker || e->has_wk) ? e->mv.cw3 + t * WT : nullptr;
+    h.mvkind = e->has_wk ? e->mv.kind + t * e->E : nullptr;
+    h.mvpar = e->has_wk ? e->mv.par + 2 * t * e->E : nullptr;
+    h.kde = e->kde;
+    h.seed = e->seed;
 }
 
 static DrawBuffers offset_draws(const DrawBuffers& b, size_t off) {
@@ -638,6 +679,7 @@ int alabi_ens_destroy(alabi_ens* e) {
     free_draws(e->draws);
     free_draws(e->draws2);
     free_move_buffers(e->mv);
+    free_kde_buffers(e->kde);
     if (e->side_stream) (void)hipStreamDestroy(e->side_stream);
     if (e->ev_free) (void)hipEventDestroy(e->ev_free);
     if (e->ev_drawn) (void)hipEventDestroy(e->ev_drawn);
@@ -691,7 +733,8 @@ int alabi_ens_set_logp_map(alabi_ens* e, int kind) {
 int alabi_ens_set_moves(alabi_ens* e, int n, const int* kind, const double* cum, const double* p0, const double* p1) {
     if (!e || n < 0 || n > ALABI_MAX_MOVES || (n > 0 && (!kind || !cum || !p0 || !p1))) return ALABI_BAD_ARGUMENT;
     MoveTable mt{};
-    bool de = false, snooker = false;
+    bool de = false, snooker = false, walk = false, kde = false;
+    const int nc_min = e->W / 2, nc_max = (e->W + 1) / 2;   // the two complementary halves
     double prev = 0.0;
     for (int k = 0; k < n; ++k) {
         if (!(cum[k] >= prev) || !std::isfinite(cum[k])) return ALABI_BAD_ARGUMENT;   // cumulative weights do not decrease
@@ -699,17 +742,28 @@ int alabi_ens_set_moves(alabi_ens* e, int n, const int* kind, const double* cum,
         if (kind[k] == 0) { if (!(p0[k] > 1.0) || !std::isfinite(p0[k])) return ALABI_BAD_ARGUMENT; }          // stretch: a > 1
         else if (kind[k] == 1) { if (!std::isfinite(p0[k]) || !std::isfinite(p1[k])) return ALABI_BAD_ARGUMENT; de = true; }
         else if (kind[k] == 2) { if (!std::isfinite(p0[k])) return ALABI_BAD_ARGUMENT; snooker = true; }                // snooker: gammas
+        else if (kind[k] == 3) {                             // walk: p0 = s0 (0: the whole half), 2 <= s0 <= the smaller half
+            const double s0 = p0[k] == 0.0 ? (double)nc_min : p0[k];
+            if (!(s0 >= 2.0) || !(s0 <= (double)nc_min) || s0 != std::floor(s0) || nc_max > 2048) return ALABI_BAD_ARGUMENT;
+            walk = true;
+        } else if (kind[k] == 4) {                           // KDE: the bandwidth factors of the two splits; more rows than dimensions
+            if (!(p0[k] > 0.0) || !std::isfinite(p0[k]) || !(p1[k] > 0.0) || !std::isfinite(p1[k]) || nc_min < e->d + 1) return ALABI_BAD_ARGUMENT;
+            kde = true;
+        }
         else return ALABI_BAD_ARGUMENT;
         mt.kind[k] = kind[k]; mt.cum[k] = cum[k]; mt.p0[k] = p0[k]; mt.p1[k] = p1[k];
     }
     if (n > 0 && !(prev > 0.0)) return ALABI_BAD_ARGUMENT;
     if (de && e->W < 4) return ALABI_BAD_ARGUMENT;       // two distinct partners in a complementary list of W / 2 walkers
     if (snooker && e->W < 6) return ALABI_BAD_ARGUMENT;  // three distinct partners
-    if (n > 0) { const int st = ensure_move_buffers(e, snooker); if (st != ALABI_OK) return st; }
+    if (n > 0) { const int st = ensure_move_buffers(e, snooker || walk || kde, walk || kde); if (st != ALABI_OK) return st; }
+    if (kde) { const int st = ensure_kde_buffers(e); if (st != ALABI_OK) return st; }
     mt.n = n;
     e->moves = mt;
-    e->has_de = de || snooker;                           // more than one partner row: one launch per half step
+    e->has_de = de || snooker || walk || kde;            // more than one partner row: one launch per half step
     e->has_snooker = snooker;
+    e->has_wk = walk || kde;                             // the whole complementary half: the whole-half instantiations
+    e->has_kde = kde;
     e->drawn_n = 0;                                      // records drawn under the old move set are not the new set's
     e->ahead_valid = false;                              // nor are those made ahead for the next stream call
     e->moves_gen++;
@@ -891,12 +945,13 @@ static int enqueue_chunk(alabi_ens* e, HalfArgs h, int n, double a, hipStream_t 
     const size_t WT = (size_t)e->W * e->E;
     for (int t = 0; t < n; ++t) {
         h.rec = offset_draws(e->draws, (size_t)t * WT);
-        h.cw2 = e->has_de ? e->mv.cw2 + (size_t)t * WT : nullptr;
-        h.cw3 = e->has_snooker ? e->mv.cw3 + (size_t)t * WT : nullptr;
+        set_move_args(e, h, (size_t)t);
         h.local_t = t; h.part_begin = 0;
         h.split = 0;
+        if (e->has_kde && (st = launch_ens_kde_prepass(e, h, s)) != ALABI_OK) return st;
         if ((st = launch_ens_half_args(e, h, n0, s)) != ALABI_OK) return st;
         h.split = 1;
+        if (e->has_kde && n1 > 0 && (st = launch_ens_kde_prepass(e, h, s)) != ALABI_OK) return st;
         if ((st = launch_ens_half_args(e, h, n1, s)) != ALABI_OK) return st;
     }
     return launch_ens_advance(e, n, s);
@@ -1127,9 +1182,9 @@ int alabi_ens_half_step(alabi_ens* e, double* coords, double* logp, int t, int s
     const int nS = split == 0 ? h.n0 : e->W - h.n0;
     if (part_begin < 0 || part_end > nS || part_begin > part_end) return ALABI_BAD_ARGUMENT;
     h.rec = offset_draws(e->draws, (size_t)t * e->W);
-    h.cw2 = e->has_de ? e->mv.cw2 + (size_t)t * e->W : nullptr;
-    h.cw3 = e->has_snooker ? e->mv.cw3 + (size_t)t * e->W : nullptr;
+    set_move_args(e, h, (size_t)t);
     h.local_t = t; h.split = split; h.part_begin = part_begin; h.n_accept = n_accept;
+    if (e->has_kde && part_end > part_begin && (st = launch_ens_kde_prepass(e, h, as_stream(stream))) != ALABI_OK) return st;
     return launch_ens_half_args(e, h, part_end - part_begin, as_stream(stream));
 }
 
@@ -1159,9 +1214,9 @@ int alabi_ens_propose(alabi_ens* e, const double* coords, int t, int split, int 
     HalfArgs h = base_args(e, const_cast<double*>(coords), nullptr);
     const int nS = split == 0 ? h.n0 : e->W - h.n0;
     h.rec = offset_draws(e->draws, (size_t)t * e->W);
-    h.cw2 = e->has_de ? e->mv.cw2 + (size_t)t * e->W : nullptr;
-    h.cw3 = e->has_snooker ? e->mv.cw3 + (size_t)t * e->W : nullptr;
+    set_move_args(e, h, (size_t)t);
     h.local_t = t; h.split = split; h.part_begin = 0;
+    if (e->has_kde && nS > 0 && (st = launch_ens_kde_prepass(e, h, as_stream(stream))) != ALABI_OK) return st;
     return launch_ens_propose(e, h, nS, gate_box, q, like, as_stream(stream));
 }
 
@@ -1240,6 +1295,64 @@ int alabi_ens_step_with_randoms_snooker(alabi_ens* e, double* coords, double* lo
     if ((st = launch_ens_half_args(e, h, n0, s)) != ALABI_OK) return st;
     h.split = 1;
     return launch_ens_half_args(e, h, e->W - n0, s);
+}
+
+// one full step of the whole-half instantiation on row 0 of the draw buffers, from a test entry's draws
+static int step_injected_wk(alabi_ens* e, double* coords, double* logp, const int* order, int n0, int kind, double p0, double p1,
+                            const WkInject& inj, const double* u_acc, long long* n_accept, hipStream_t s) {
+    int st;
+    if ((st = sync_consts(e, s)) != ALABI_OK) return st;
+    if ((st = ensure_move_buffers(e, true, true)) != ALABI_OK) return st;
+    if (kind == 4 && (st = ensure_kde_buffers(e)) != ALABI_OK) return st;
+    if ((st = launch_ens_prep_wk(e, order, u_acc, s)) != ALABI_OK) return st;
+    if ((st = launch_ens_set_step_move(e, kind, p0, p1, s)) != ALABI_OK) return st;
+    e->drawn_n = 0;  // row 0 of the draw buffers now holds caller data
+    HalfArgs h = base_args(e, coords, logp);
+    h.rec = e->draws; h.cw2 = e->mv.cw2; h.cw3 = e->mv.cw3; h.mvkind = e->mv.kind; h.mvpar = e->mv.par; h.kde = e->kde; h.seed = e->seed;
+    h.inj = inj;
+    h.n0 = n0; h.n_accept = n_accept; h.local_t = 0; h.part_begin = 0;
+    for (int split = 0; split < 2; ++split) {
+        const int nS = split == 0 ? n0 : e->W - n0;
+        if (nS == 0) continue;
+        h.split = split;
+        if (kind == 4 && (st = launch_ens_kde_prepass(e, h, s)) != ALABI_OK) return st;
+        if ((st = launch_ens_half_args(e, h, nS, s)) != ALABI_OK) return st;
+    }
+    return ALABI_OK;
+}
+
+int alabi_ens_step_with_randoms_walk(alabi_ens* e, double* coords, double* logp, const int* order, int n0, int s0, const int* subset,
+                                     const double* z, const double* u_acc, long long* n_accept, void* stream) {
+    if (!e || !coords || !logp || !order || !subset || !z || !u_acc || n0 < 0 || n0 > e->W || e->E != 1) return ALABI_BAD_ARGUMENT;
+    // every active half needs s0 rows in the other one, which the kernel's lists must hold
+    const int n1 = e->W - n0;
+    if (s0 < 2 || (n0 > 0 && s0 > n1) || (n1 > 0 && s0 > n0) || n0 > 2048 || n1 > 2048) return ALABI_BAD_ARGUMENT;
+    if (!e->gp->computed || !e->gp->has_alpha) return ALABI_NOT_COMPUTED;
+    WkInject inj{subset, z, nullptr};
+    return step_injected_wk(e, coords, logp, order, n0, 3, (double)s0, 0.0, inj, u_acc, n_accept, as_stream(stream));
+}
+
+int alabi_ens_step_with_randoms_kde(alabi_ens* e, double* coords, double* logp, const int* order, int n0, double factor, const int* r,
+                                    const double* z, const double* u_acc, double* lnfac_out, long long* n_accept, void* stream) {
+    if (!e || !coords || !logp || !order || !r || !z || !u_acc || n0 < 0 || n0 > e->W || e->E != 1) return ALABI_BAD_ARGUMENT;
+    const int n1 = e->W - n0;
+    // the pre-pass buffers hold (W + 1) / 2 rows; scipy's gaussian_kde refuses fewer rows than d + 1 as well
+    if (!(factor > 0.0) || !std::isfinite(factor) || n0 > (e->W + 1) / 2 || n1 > (e->W + 1) / 2 || n0 < e->d + 1 || n1 < e->d + 1)
+        return ALABI_BAD_ARGUMENT;
+    if (!e->gp->computed || !e->gp->has_alpha) return ALABI_NOT_COMPUTED;
+    WkInject inj{r, z, lnfac_out};
+    return step_injected_wk(e, coords, logp, order, n0, 4, factor, factor, inj, u_acc, n_accept, as_stream(stream));
+}
+
+int alabi_ens_kde_singular(alabi_ens* e, long long* count) {
+    if (!e || !count) return ALABI_BAD_ARGUMENT;
+    *count = 0;
+    if (!e->kde.singular) return ALABI_OK;
+    unsigned long long v = 0;
+    ALABI_HIP_CHECK(hipDeviceSynchronize());
+    ALABI_HIP_CHECK(hipMemcpy(&v, e->kde.singular, sizeof(v), hipMemcpyDeviceToHost));
+    *count = (long long)v;
+    return ALABI_OK;
 }
 
 int alabi_ens_export_snooker_draws(alabi_ens* e, int* j3, void* stream) {

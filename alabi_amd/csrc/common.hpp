@@ -129,6 +129,8 @@ struct DrawBuffers {
 // Proposal moves (emcee's `moves=`): one move per step and ensemble, chosen by ens_draw_kernel from cumulative weights.
 //   kind 0 StretchMove: p0 = a.   kind 1 DEMove: p0 = gamma0 (mean step), p1 = sigma (its relative scatter).
 //   kind 2 SnookerMove: p0 = gammas (the fixed step along the line), p1 = 0.
+//   kind 3 WalkMove: p0 = s0, the size of the subset of the complementary half (0: all of it), p1 = 0.
+//   kind 4 KDEMove: p0 / p1 = the bandwidth factor f of split 0 / split 1 (the two halves of an odd W differ in size).
 // n = 0 stands for the default, one stretch move with the `a` of the call.
 #define ALABI_MAX_MOVES 8
 struct MoveTable {
@@ -149,6 +151,26 @@ struct MoveBuffers {
     int* move;       // [chunk_cap, E] index of the step's move
     int* cw3;        // [chunk_cap, E, W] global id of the third partner C[j3]; -1: a stretch or differential-evolution record
     int* partner3;   // [chunk_cap, E, W] raw j3 into the complementary list (-1: stretch, DE), for export / tests
+    // walk and KDE moves (kinds 3, 4): their proposals read the whole complementary half, so a record names no partner; the
+    // half-step kernel takes the kind and the parameters of the step's move from here.  Allocated with the third-partner arrays
+    // on a handle that was given such a move.
+    int* kind;       // [chunk_cap, E] kind of the step's move
+    double* par;     // [chunk_cap, E, 2] its p0, p1
+};
+// What ens_kde_prepass_kernel leaves for the KDE proposals of ONE half step (per ensemble): rewritten in front of every half step
+// whose move is a KDE move.  Lives in HBM / L2: Nc x d doubles do not fit the LDS at Nc = 1024, d = 64.
+struct KdeBuffers {
+    double* white;   // [E, ncmax, d] the whitened rows L^-1 (c_j - mean) of the complementary half
+    double* L;       // [E, d, d] lower Cholesky factor of H = f^2 cov (row-major; the upper triangle is not written)
+    double* mean;    // [E, d] mean of the complementary half
+    int* flag;       // [E] 1: a pivot of the factorisation was not positive and finite, every proposal of the half step is rejected
+    unsigned long long* singular;   // [1] half steps (per ensemble) that were rejected so
+};
+// Draws of the walk and KDE test entries (alabi_ens_step_with_randoms_walk / _kde), keyed by WALKER id; null: counter-based draws.
+struct WkInject {
+    const int* idx;      // walk: [W, s0] subset indices into the complementary list; KDE: [W] the row r
+    const double* z;     // walk: [W, s0] the normals of the subset's rows; KDE: [W, d]
+    double* lnfac_out;   // KDE: [W] the proposals' log factor, by walker id (nullable)
 };
 }  // namespace alabi
 
@@ -235,7 +257,9 @@ struct alabi_ens {
     // second partner row), has_snooker: a snooker move (the three-partner instantiations) -- and the records' further-partner arrays
     alabi::MoveTable moves{};
     bool has_de = false, has_snooker = false;
+    bool has_wk = false, has_kde = false;   // a walk or KDE move (the whole-half instantiations run); a KDE move (the pre-pass is launched)
     alabi::MoveBuffers mv{};
+    alabi::KdeBuffers kde{};
 };
 
 namespace alabi {
@@ -325,7 +349,17 @@ struct HalfArgs {
     const int* cw2 = nullptr;
     // snooker records (MoveBuffers::cw3 offset to the step; cw2 is set as well): set -> the three-partner instantiations run
     const int* cw3 = nullptr;
+    // walk and KDE steps (MoveBuffers::kind / ::par offset to the step; cw2 and cw3 are set as well): set -> the whole-half
+    // instantiations run.  seed keys their counter-based draws, inj replaces them (test entries).
+    const int* mvkind = nullptr;
+    const double* mvpar = nullptr;
+    KdeBuffers kde{};
+    WkInject inj{};
+    unsigned long long seed = 0;
 };
+int launch_ens_kde_prepass(alabi_ens* e, const HalfArgs& args, hipStream_t s);
+int launch_ens_prep_wk(alabi_ens* e, const int* order, const double* u_acc, hipStream_t s);
+int launch_ens_set_step_move(alabi_ens* e, int kind, double p0, double p1, hipStream_t s);
 int launch_ens_draw(alabi_ens* e, int nsteps, double a, hipStream_t s);
 int launch_ens_draw_at(alabi_ens* e, const DrawBuffers& into, int nsteps, double a, bool from_state, long long step0, hipStream_t s);   // first step: run_state[0], or step0 by value
 int launch_ens_prep(alabi_ens* e, const int* order, int n0, const double* u_z, const int* partner,

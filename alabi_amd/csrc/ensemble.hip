@@ -20,6 +20,15 @@
 // DE records, since the step's move is chosen on the device.  The multi-proposal kernel has no such instantiation: a set with a
 // snooker move runs one proposal per workgroup.
 //
+// The walk move (Goodman & Weare 2010; emcee 3 moves/walk.py) and the KDE move (emcee 3 moves/kde.py) use the WHOLE complementary
+// half (tests/walk_kde_numpy.py is the CPU statement): walk q = S_k + sum_{j in J} z_j (C[j] - mean_J) / sqrt(s0 - 1) over a subset J
+// of s0 rows (all of them by default), log factor 0; KDE q = C[r] + L z with L the Cholesky factor of f^2 cov(C), log factor
+// kde.logpdf(S_k) - kde.logpdf(q) as two log-sum-exps over the whitened rows.  Their records name no partner: the half-step and the
+// propose kernel have a fourth instantiation (wk_proposal) that takes the step's kind from MoveBuffers::kind, draws the subset, r
+// and the normals where they are used (Philox streams 6-8) and still takes stretch, DE and snooker records.  ens_kde_prepass_kernel,
+// one workgroup per ensemble in front of a half step, leaves mean, L and the whitened rows of the half in KdeBuffers, or the flag
+// of a factorisation that broke down (every proposal of that half step is then rejected and the half step counted).
+//
 // E independent ensembles of W walkers ("independent chains") can share every launch: walker
 // ids are global (e*W + i), lists are per-ensemble segments, blockIdx.y is the ensemble.
 //
@@ -185,6 +194,11 @@ ens_draw_kernel(unsigned long long seed, const long long* __restrict__ run_state
     for (int k = 1; k < ALABI_MAX_MOVES; ++k)
         if (k == mi) { kind = mt.kind[k]; mp0 = mt.p0[k]; mp1 = mt.p1[k]; }
     if (tid == 0 && mv.move) mv.move[(size_t)blockIdx.x * E + e] = mi;
+    if (tid == 0 && mv.kind) {
+        mv.kind[(size_t)blockIdx.x * E + e] = kind;
+        mv.par[2 * ((size_t)blockIdx.x * E + e)] = mp0;
+        mv.par[2 * ((size_t)blockIdx.x * E + e) + 1] = mp1;
+    }
     for (int pos = tid; pos < W; pos += 256) {
         const int i = olist[pos];
         const int li = pos >= n0;
@@ -201,6 +215,14 @@ ens_draw_kernel(unsigned long long seed, const long long* __restrict__ run_state
         b.u_z[base + pos] = uz;
         b.u_acc[base + pos] = ua;
         b.pos_of[base + i] = pos;
+        if (kind >= 3) {
+            // walk, KDE: the proposal reads the whole complementary half and draws where it is formed (streams 6-8); the record
+            // carries the walker and ln u' (the stretch partner fills its slot, nobody reads it)
+            store_record(b, base + pos, (int)g0 + i, (int)g0 + cw, 0.0, 0.0, log(ua));
+            if (mv.cw2) { mv.cw2[base + pos] = -1; mv.partner2[base + pos] = -1; }
+            if (mv.cw3) { mv.cw3[base + pos] = -1; mv.partner3[base + pos] = -1; }
+            continue;
+        }
         if (kind == 0) {
             write_record(b, base + pos, (int)g0 + i, (int)g0 + cw, uz, ua, mp0, d);
             if (mv.cw2) { mv.cw2[base + pos] = -1; mv.partner2[base + pos] = -1; }
@@ -303,6 +325,23 @@ ens_prep_snooker_kernel(const int* __restrict__ order, int n0, int W, const int*
     write_snooker_record(b, mv, pos, wid, cw, cw2, jj2, cw3, jj3, gamma, ua);
 }
 
+// Records of the walk and KDE test entries: the walker and ln u' (bad walker ids yield an inert record, w = -1).
+__global__ void __launch_bounds__(256)
+ens_prep_wk_kernel(const int* __restrict__ order, int W, const double* __restrict__ u_acc, DrawBuffers b, MoveBuffers mv) {
+    const int pos = blockIdx.x * 256 + threadIdx.x;
+    if (pos >= W) return;
+    const int w = order[pos];
+    const bool good = (unsigned)w < (unsigned)W;
+    store_record(b, pos, good ? w : -1, -1, 0.0, 0.0, log(good ? u_acc[w] : 0.5));
+    mv.cw2[pos] = -1; mv.partner2[pos] = -1;
+    mv.cw3[pos] = -1; mv.partner3[pos] = -1;
+}
+
+// kind and parameters of step 0's move (E = 1), for the test entries
+__global__ void ens_set_step_move_kernel(MoveBuffers mv, int kind, double p0, double p1) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) { mv.kind[0] = kind; mv.par[0] = p0; mv.par[1] = p1; }
+}
+
 // Normal-prior term of coordinate `lane` (< d) of a proposal, summed over the wave: lanes >= d contribute 0.
 // consts rows 3 / 4: prior mean, 1 / std (0 where there is no normal prior).  Result valid in every lane.
 // h and the centred inputs of the squared-exponential half-step kernels (alabi_gp::Xc, ::ens_h)
@@ -377,13 +416,301 @@ __device__ __forceinline__ double snooker_coord(int d, double sv, double zv, dou
     return qv;
 }
 
+// ---- walk and KDE moves: proposals from the whole complementary half ----------------------------------------------------------
+// Draws (tests/walk_kde_numpy.py states the same layout): Philox counter (step, global walker id, stream word), stream word =
+// S + 16 b with
+//   S = 6, b = j >> 1:  64-bit key of row j of the complementary list, words (0, 1) for even j, (2, 3) for odd j; row j belongs to the
+//                       subset J iff the rank of its key among the Nc keys (ties by j) is < s0 -- no key is drawn when s0 = Nc;
+//   S = 7, b = j:       z_j, the normal of row j (Box-Muller as stream 4: sqrt(-2 ln(1 - u53(r0, r1))) cos(2 pi u53(r2, r3)));
+//   S = 8, b = 0:       r = (r0 Nc) >> 32, the KDE move's row;  b = 1 + k: the normal z_k of coordinate k.
+// Streams 0-5 are S + 16 b with b = 0 and S < 6: nothing here meets them.
+#define ALABI_WK_MAX_NC 2048     // rows of a complementary half the walk move's lists hold in LDS
+#define ALABI_WK_TILE 2048       // doubles of the tile through which its rows are read
+
+__device__ inline double philox_normal(uint32_t s_lo, uint32_t s_hi, uint32_t gid, uint32_t word, uint32_t k0, uint32_t k1) {
+    uint32_t r[4];
+    philox4x32_10(s_lo, s_hi, gid, word, k0, k1, r);
+    const double u1 = u53(r[0], r[1]), u2 = u53(r[2], r[3]);
+    return sqrt(-2.0 * log(1.0 - u1)) * cos(6.283185307179586 * u2);
+}
+
+// log(exp(m1) s1 + exp(m2) s2) as (max, scaled sum): the running-maximum form of kde.hip
+__device__ inline void lse_merge(double& m, double& s, double m2, double s2) {
+    const double mm = m > m2 ? m : m2;
+    if (mm == -INFINITY) { m = mm; s = 0.0; return; }
+    s = s * exp(m - mm) + s2 * exp(m2 - mm);
+    m = mm;
+}
+
+// The proposal of a walk (kind 3) or KDE (kind 4) step for walker w (global id), called by EVERY thread of the workgroup (it has
+// barriers).  sv: coordinate tid of the walker in lanes tid < d, 0 elsewhere.  Leaves coordinate tid of the proposal in qc (lanes
+// tid < d), the log factor in lnfac (every thread) and reject = 1 where the half step's factorisation broke down.  Returns 0 for
+// a proposal that is a no-op (a test entry's subset or row out of range or repeated).  Operation order: tests/walk_kde_numpy.py.
+template <int D>
+__device__ __forceinline__ int wk_proposal(const HalfArgs& p, int kind, int e, int w, double sv, double& qc, double& lnfac, int& reject) {
+    __shared__ __attribute__((aligned(16))) unsigned char wk_lds[48 * 1024];
+    __shared__ double wk_red[2][16][2];
+    const int tid = threadIdx.x, T = blockDim.x, d = p.d;
+    const int Nc = p.split ? p.n0 : p.W - p.n0;
+    const int* clist = p.rec.order + (size_t)e * p.W + (p.split ? 0 : p.n0);
+    const long long step = p.run_state[0] + p.local_t;
+    const uint32_t s_lo = (uint32_t)step, s_hi = (uint32_t)((unsigned long long)step >> 32);
+    const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
+    const bool in = tid < d;
+    qc = 0.0; lnfac = 0.0; reject = 0;
+    if (kind == 3) {
+        uint64_t* keys = reinterpret_cast<uint64_t*>(wk_lds);                  // [Nc]; after the ranks: zl
+        double* zl = reinterpret_cast<double*>(wk_lds);                        // [s0] normals in sum order
+        int* rank = reinterpret_cast<int*>(wk_lds + 16 * 1024);                // [Nc]
+        int* J = reinterpret_cast<int*>(wk_lds + 24 * 1024);                   // [s0] global walker ids in sum order
+        double* tile = reinterpret_cast<double*>(wk_lds + 32 * 1024);          // [ALABI_WK_TILE]
+        const double p0 = p.mvpar[2 * e];
+        const int s0 = p0 == 0.0 ? Nc : (int)p0;
+        if (s0 < 2 || s0 > Nc || Nc > ALABI_WK_MAX_NC) return 0;               // checked where the moves are set
+        if (p.inj.idx) {
+            int bad = 0;
+            for (int m = tid; m < s0; m += T) {
+                const int j = p.inj.idx[(size_t)w * s0 + m];
+                int c = -1;
+                if ((unsigned)j < (unsigned)Nc) c = clist[j];
+                if (c < 0) bad = 1;
+                for (int m2 = 0; m2 < m; ++m2) bad |= (p.inj.idx[(size_t)w * s0 + m2] == j);
+                J[m] = c;
+                zl[m] = p.inj.z[(size_t)w * s0 + m];
+            }
+            if (__syncthreads_or(bad)) return 0;
+        } else if (s0 == Nc) {
+            for (int j = tid; j < Nc; j += T) {
+                J[j] = clist[j];
+                zl[j] = philox_normal(s_lo, s_hi, (uint32_t)w, 7u + 16u * (uint32_t)j, k0, k1);
+            }
+            __syncthreads();
+        } else {
+            uint32_t r[4];
+            for (int j = tid; j < Nc; j += T) {
+                philox4x32_10(s_lo, s_hi, (uint32_t)w, 6u + 16u * (uint32_t)(j >> 1), k0, k1, r);
+                keys[j] = (j & 1) ? (((uint64_t)r[2] << 32) | r[3]) : (((uint64_t)r[0] << 32) | r[1]);
+            }
+            __syncthreads();
+            for (int j = tid; j < Nc; j += T) {
+                const uint64_t kj = keys[j];
+                int rk = 0;
+                for (int i = 0; i < Nc; ++i) { const uint64_t ki = keys[i]; rk += (ki < kj || (ki == kj && i < j)) ? 1 : 0; }
+                rank[j] = rk;
+            }
+            __syncthreads();                                                   // the keys are dead: zl takes their place
+            for (int j = tid; j < Nc; j += T) {
+                if (rank[j] >= s0) continue;
+                int pos = 0;
+                for (int i = 0; i < j; ++i) pos += rank[i] < s0 ? 1 : 0;
+                J[pos] = clist[j];
+                zl[pos] = philox_normal(s_lo, s_hi, (uint32_t)w, 7u + 16u * (uint32_t)j, k0, k1);
+            }
+            __syncthreads();
+        }
+        // rows of J through an LDS tile (loaded by all threads), summed by lane k in the order m = 0 .. s0-1: mean, then the walk sum
+        const int rows = ALABI_WK_TILE / d;
+        double mean = 0.0, acc = 0.0;
+        for (int pass = 0; pass < 2; ++pass) {
+            for (int m0 = 0; m0 < s0; m0 += rows) {
+                const int nr = s0 - m0 < rows ? s0 - m0 : rows;
+                for (int idx = tid; idx < nr * d; idx += T) tile[idx] = p.coords[(size_t)J[m0 + idx / d] * d + idx % d];
+                __syncthreads();
+                if (in) {
+                    if (pass == 0) for (int m = 0; m < nr; ++m) mean += tile[m * d + tid];
+                    else for (int m = 0; m < nr; ++m) acc += zl[m0 + m] * (tile[m * d + tid] - mean);
+                }
+                __syncthreads();
+            }
+            if (pass == 0) mean = mean / (double)s0;
+        }
+        const double scale = 1.0 / sqrt((double)s0 - 1.0);
+        qc = sv + scale * acc;
+        return 1;
+    }
+    // ---- KDE
+    if (p.kde.flag[e]) { reject = 1; qc = sv; return 1; }                      // workgroup-uniform
+    double* Ls = reinterpret_cast<double*>(wk_lds);                            // [d, d] (32 KB at d = 64)
+    double* yx = reinterpret_cast<double*>(wk_lds + 32 * 1024);                // [d] whitened walker
+    double* yq = yx + ALABI_MAX_DIM;                                           // [d] whitened proposal
+    int ri;
+    if (p.inj.idx) ri = p.inj.idx[w];
+    else {
+        uint32_t r[4];
+        philox4x32_10(s_lo, s_hi, (uint32_t)w, 8u, k0, k1, r);
+        ri = (int)(((uint64_t)r[0] * (uint64_t)Nc) >> 32);
+    }
+    if ((unsigned)ri >= (unsigned)Nc) return 0;                                // workgroup-uniform
+    const int cr = clist[ri];
+    if (cr < 0) return 0;                                                      // a test entry's list with a bad walker id
+    for (int idx = tid; idx < d * d; idx += T) Ls[idx] = p.kde.L[(size_t)e * d * d + idx];
+    __syncthreads();
+    if (tid < 64) {                                                            // wave 0; lanes >= d carry zeros
+        double z = 0.0, crk = 0.0, mk = 0.0;
+        if (in) {
+            z = p.inj.z ? p.inj.z[(size_t)w * d + tid] : philox_normal(s_lo, s_hi, (uint32_t)w, 8u + 16u * (uint32_t)(1 + tid), k0, k1);
+            crk = p.coords[(size_t)cr * d + tid];
+            mk = p.kde.mean[(size_t)e * d + tid];
+        }
+        double acc = 0.0;                                                      // (L z)_k = sum_{m <= k} L[k][m] z_m, m ascending
+        for (int m = 0; m < d; ++m) {
+            const double zm = lane_bcast(z, m);
+            if (in && m <= tid) acc += Ls[tid * d + m] * zm;
+        }
+        qc = crk + acc;
+        // y = L^-1 (v - mean) for v = walker, proposal: column-oriented forward substitution, lane k keeps row k's residual
+        double bx = sv - mk, bq = qc - mk;
+        for (int i = 0; i < d; ++i) {
+            if (tid == i) { const double lii = Ls[i * d + i]; bx = bx / lii; bq = bq / lii; }
+            const double yxi = lane_bcast(bx, i), yqi = lane_bcast(bq, i);
+            if (in && tid > i) { const double lki = Ls[tid * d + i]; bx -= lki * yxi; bq -= lki * yqi; }
+        }
+        if (in) { yx[tid] = bx; yq[tid] = bq; }
+    }
+    __syncthreads();
+    // the two log-sum-exps over the whitened rows, every thread a strided share, merged in a fixed tree
+    double mx = -INFINITY, sx = 0.0, mq = -INFINITY, sq = 0.0;
+    const double* white = p.kde.white + (size_t)e * p.n0 * d;                  // n0 = the larger half
+    for (int j = tid; j < Nc; j += T) {
+        const double* row = white + (size_t)j * d;
+        double ax = 0.0, aq = 0.0;
+        for (int k = 0; k < d; ++k) {
+            const double y = row[k];
+            const double dx = yx[k] - y, dq = yq[k] - y;
+            ax = fma(dx, dx, ax);
+            aq = fma(dq, dq, aq);
+        }
+        lse_merge(mx, sx, -0.5 * ax, 1.0);
+        lse_merge(mq, sq, -0.5 * aq, 1.0);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        lse_merge(mx, sx, __shfl_xor(mx, off, 64), __shfl_xor(sx, off, 64));
+        lse_merge(mq, sq, __shfl_xor(mq, off, 64), __shfl_xor(sq, off, 64));
+    }
+    if ((tid & 63) == 0) { wk_red[0][tid >> 6][0] = mx; wk_red[0][tid >> 6][1] = sx; wk_red[1][tid >> 6][0] = mq; wk_red[1][tid >> 6][1] = sq; }
+    __syncthreads();
+    mx = wk_red[0][0][0]; sx = wk_red[0][0][1]; mq = wk_red[1][0][0]; sq = wk_red[1][0][1];
+    for (int k = 1; k < (T >> 6); ++k) {
+        lse_merge(mx, sx, wk_red[0][k][0], wk_red[0][k][1]);
+        lse_merge(mq, sq, wk_red[1][k][0], wk_red[1][k][1]);
+    }
+    lnfac = (mx + log(sx)) - (mq + log(sq));
+    if (tid == 0 && p.inj.lnfac_out) p.inj.lnfac_out[w] = lnfac;
+    return 1;
+}
+
+// Pre-pass of a KDE half step: one workgroup per ensemble.  Not a KDE step (the move is chosen on the device): exits at once.
+// mean_k = (sum_j c_jk) / Nc, cov_ab = (sum_j (c_ja - mean_a)(c_jb - mean_b)) / (Nc - 1), every sum over j ascending from 0.0 with
+// rounded products, H = (f f) cov, left-looking Cholesky (t = H_ij - sum_{k<j} L_ik L_jk, k ascending; L_jj = sqrt(t_jj),
+// L_ij = t_ij / L_jj), rows whitened by forward substitution -- the order tests/walk_kde_numpy.py states.
+__global__ void __launch_bounds__(256)
+ens_kde_prepass_kernel(HalfArgs p) {
+    __shared__ double Ls[ALABI_MAX_DIM * ALABI_MAX_DIM];
+    __shared__ double tile[ALABI_WK_TILE];                                     // rows of the half, loaded by all threads, read in order
+    __shared__ double mean_s[ALABI_MAX_DIM];
+    const int e = blockIdx.x, tid = threadIdx.x, d = p.d;
+    if (p.mvkind[e] != 4) return;
+    const int Nc = p.split ? p.n0 : p.W - p.n0;
+    const int* clist = p.rec.order + (size_t)e * p.W + (p.split ? 0 : p.n0);
+    const double f = p.mvpar[2 * e + (p.split ? 1 : 0)];
+    const int rows = ALABI_WK_TILE / d;
+    int bad = 0;
+    for (int j = tid; j < Nc; j += 256) bad |= ((unsigned)clist[j] >= (unsigned)(p.W * gridDim.x)) ? 1 : 0;   // a test entry's list
+    bad = __syncthreads_or(bad);
+    if (!bad) {
+        double m = 0.0;
+        for (int j0 = 0; j0 < Nc; j0 += rows) {
+            const int nr = Nc - j0 < rows ? Nc - j0 : rows;
+            for (int idx = tid; idx < nr * d; idx += 256) tile[idx] = p.coords[(size_t)clist[j0 + idx / d] * d + idx % d];
+            __syncthreads();
+            if (tid < d) for (int r = 0; r < nr; ++r) m += tile[r * d + tid];
+            __syncthreads();
+        }
+        if (tid < d) {
+            m = m / (double)Nc;
+            mean_s[tid] = m;
+            p.kde.mean[(size_t)e * d + tid] = m;
+        }
+        __syncthreads();
+        // covariance: entry idx = a (a + 1) / 2 + b, b <= a; a thread owns entries tid, tid + 256, ... (at most 9 at d = 64)
+        constexpr int NQ = (ALABI_MAX_DIM * (ALABI_MAX_DIM + 1) / 2 + 255) / 256;
+        const int ne = d * (d + 1) / 2;
+        int ea[NQ], eb[NQ];
+        double sum[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            int a = 0, rem = tid + 256 * q;
+            if (rem < ne) while (rem > a) { rem -= a + 1; ++a; }
+            ea[q] = a; eb[q] = rem < ne ? rem : 0; sum[q] = 0.0;
+        }
+        for (int j0 = 0; j0 < Nc; j0 += rows) {
+            const int nr = Nc - j0 < rows ? Nc - j0 : rows;
+            for (int idx = tid; idx < nr * d; idx += 256)
+                tile[idx] = p.coords[(size_t)clist[j0 + idx / d] * d + idx % d] - mean_s[idx % d];
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < NQ; ++q)
+                if (tid + 256 * q < ne)
+                    for (int r = 0; r < nr; ++r) sum[q] += tile[r * d + ea[q]] * tile[r * d + eb[q]];
+            __syncthreads();
+        }
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+            if (tid + 256 * q < ne) Ls[ea[q] * d + eb[q]] = (f * f) * (sum[q] / ((double)Nc - 1.0));
+        __syncthreads();
+        for (int j = 0; j < d && !bad; ++j) {
+            double t = 0.0;
+            const int i = j + tid;                                             // row of column j this thread forms (d <= 64 < 256)
+            if (i < d) {
+                t = Ls[i * d + j];
+                for (int k = 0; k < j; ++k) t -= Ls[i * d + k] * Ls[j * d + k];
+                if (i == j) Ls[j * d + j] = t;
+            }
+            __syncthreads();
+            const double piv = Ls[j * d + j];
+            bad = !(piv > 0.0) || !(piv < INFINITY);
+            __syncthreads();
+            if (!bad && i < d) { const double ljj = sqrt(piv); Ls[i * d + j] = (i == j) ? ljj : t / ljj; }
+            __syncthreads();
+        }
+    }
+    if (tid == 0) {
+        p.kde.flag[e] = bad;
+        if (bad) atomicAdd(p.kde.singular, 1ull);
+    }
+    if (bad) return;
+    for (int idx = tid; idx < d * d; idx += 256) p.kde.L[(size_t)e * d * d + idx] = (idx % d <= idx / d) ? Ls[idx] : 0.0;
+    // whitened rows: a tile of centred rows, one thread per row substitutes forward in place, the tile goes out as it lies
+    double* white = p.kde.white + (size_t)e * p.n0 * d;
+    for (int j0 = 0; j0 < Nc; j0 += rows) {
+        const int nr = Nc - j0 < rows ? Nc - j0 : rows;
+        for (int idx = tid; idx < nr * d; idx += 256)
+            tile[idx] = p.coords[(size_t)clist[j0 + idx / d] * d + idx % d] - mean_s[idx % d];
+        __syncthreads();
+        for (int r = tid; r < nr; r += 256) {
+            double* row = tile + r * d;
+            for (int i = 0; i < d; ++i) {
+                double t = row[i];
+                for (int k = 0; k < i; ++k) t -= Ls[i * d + k] * row[k];
+                row[i] = t / Ls[i * d + i];
+            }
+        }
+        __syncthreads();
+        for (int idx = tid; idx < nr * d; idx += 256) white[(size_t)j0 * d + idx] = tile[idx];
+        __syncthreads();
+    }
+}
+
 // DE: the instantiation that reads the records' second partner (HalfArgs::cw2) and branches, workgroup-uniformly, on the
 // record's kind; without it the code is the stretch move's alone.  SNK (with DE): the one that reads the third partner as well
 // (HalfArgs::cw3) and forms a snooker record's proposal and log factor; stretch and DE records take the branches they take in the
-// DE instantiation.
-template <int D, bool GENERIC, bool DE, bool SNK = false>
+// DE instantiation.  WK (with SNK): the one that also forms the proposals of walk and KDE steps (wk_proposal), on a workgroup-uniform
+// branch on the step's kind; every other record takes the branch it takes in the snooker instantiation.
+template <int D, bool GENERIC, bool DE, bool SNK = false, bool WK = false>
 __device__ __forceinline__ void ens_half_body(const HalfArgs& p) {
     static_assert(DE || !SNK, "the three-partner instantiation reads the second partner too");
+    static_assert(SNK || !WK, "the whole-half instantiation takes snooker records too");
     __shared__ double q_s[ALABI_MAX_DIM], qs_s[ALABI_MAX_DIM], old_s[ALABI_MAX_DIM];
     __shared__ double scratch[16];
     const int tid = threadIdx.x, T = blockDim.x;
@@ -428,7 +755,26 @@ __device__ __forceinline__ void ens_half_body(const HalfArgs& p) {
     const double* lo = p.consts + ALABI_MAX_DIM;
     const double* hi = p.consts + 2 * ALABI_MAX_DIM;
     int ok = 1;
-    if (tid < D) {
+    const int wkind = WK ? p.mvkind[e] : 0;                // kind of the step's move; workgroup-uniform
+    if (WK && wkind >= 3) {
+        const bool in = tid < p.d;
+        const double sv = in ? own_c[tid] : 0.0;
+        double qc, lf;
+        int rej;
+        if (!wk_proposal<D>(p, wkind, e, w, sv, qc, lf, rej)) return;   // a test entry's bad subset: the walker stays as it is
+        lnfac = lf;
+        if (rej) ok = 0;                                   // the KDE of this half step has no factor: rejected like a proposal outside the box
+        if (tid < D) {
+            double qv = 0.0;
+            if (in) {
+                ok = ok && (qc > lo[tid]) && (qc < hi[tid]);
+                q_s[tid] = qc; old_s[tid] = sv;
+                qv = qc * inv_len[tid];
+                if (!GENERIC) qv -= p.centre[tid];
+            }
+            qs_s[tid] = qv;
+        }
+    } else if (tid < D) {
         double qv = 0.0;
         if (SNK && snk) {                                  // workgroup-uniform; lanes d .. D-1 take part in the sums with zeros
             const bool in = tid < p.d;
@@ -553,6 +899,10 @@ ens_half_de_kernel(HalfArgs p) { ens_half_body<D, GENERIC, true>(p); }
 template <int D, bool GENERIC>
 __global__ void __launch_bounds__(1024)
 ens_half_snooker_kernel(HalfArgs p) { ens_half_body<D, GENERIC, true, true>(p); }
+
+template <int D, bool GENERIC>
+__global__ void __launch_bounds__(1024)
+ens_half_wk_kernel(HalfArgs p) { ens_half_body<D, GENERIC, true, true, true>(p); }
 
 // NP proposals of the same half step per workgroup: the training set is streamed ONCE per workgroup and used for all of them.
 // With more proposals than CUs (W/2 > 256, or E ensembles) ens_half_kernel is bound by L2 -> CU bandwidth: every workgroup
@@ -744,7 +1094,7 @@ ens_lnprob_kernel(const double* __restrict__ coords, int d, const double* __rest
 //   (host)              lp_new = like + prior_fn(q)   [or like_fn(q) + prior_fn(q)]
 //   ens_accept_kernel   one thread per proposal: accept test with the record's (d-1) ln z and ln u', state update.
 // The ensemble, the draws and the accept decisions stay on the device; only the proposals of a half step travel.
-template <int D, bool GENERIC, bool DE, bool SNK = false>
+template <int D, bool GENERIC, bool DE, bool SNK = false, bool WK = false>
 __device__ __forceinline__ void ens_propose_body(const HalfArgs& p, int gate_box, double* __restrict__ q_out, double* __restrict__ like_out) {
     __shared__ double qs_s[ALABI_MAX_DIM];
     __shared__ double scratch[16];
@@ -763,7 +1113,25 @@ __device__ __forceinline__ void ens_propose_body(const HalfArgs& p, int gate_box
     const bool snk = SNK && cw3 >= 0;
     const bool de = DE && cw2 >= 0 && !snk;
     int ok = 1;
-    if (tid < D) {
+    const int wkind = WK ? p.mvkind[0] : 0;
+    if (WK && wkind >= 3) {                                // as in ens_half_body; a half step without a factor: q = the walker, factor -inf
+        const bool in = tid < p.d;
+        const double sv = in ? p.coords[(size_t)w * p.d + tid] : 0.0;
+        double qc, lf;
+        int rej;
+        const int live = wk_proposal<D>(p, wkind, 0, w, sv, qc, lf, rej);
+        if (tid == 0) p.rec.lnfac[pos] = (live && !rej) ? lf : -INFINITY;
+        if (!live) qc = sv;
+        if (tid < D) {
+            double qv = 0.0;
+            if (in) {
+                ok = (qc > p.consts[ALABI_MAX_DIM + tid]) && (qc < p.consts[2 * ALABI_MAX_DIM + tid]);
+                q_out[(size_t)blockIdx.x * p.d + tid] = qc;
+                qv = qc * p.consts[tid];
+            }
+            qs_s[tid] = qv;
+        }
+    } else if (tid < D) {
         double qv = 0.0;
         if (SNK && snk) {                                  // as in ens_half_body; the log factor goes where ens_accept_kernel reads it
             const bool in = tid < p.d;
@@ -810,6 +1178,12 @@ template <int D, bool GENERIC>
 __global__ void __launch_bounds__(1024)
 ens_propose_snooker_kernel(HalfArgs p, int gate_box, double* __restrict__ q_out, double* __restrict__ like_out) {
     ens_propose_body<D, GENERIC, true, true>(p, gate_box, q_out, like_out);
+}
+
+template <int D, bool GENERIC>
+__global__ void __launch_bounds__(1024)
+ens_propose_wk_kernel(HalfArgs p, int gate_box, double* __restrict__ q_out, double* __restrict__ like_out) {
+    ens_propose_body<D, GENERIC, true, true, true>(p, gate_box, q_out, like_out);
 }
 
 __global__ void __launch_bounds__(256)
@@ -891,6 +1265,26 @@ int launch_ens_prep_snooker(alabi_ens* e, const int* order, int n0, const int* j
     return ALABI_OK;
 }
 
+int launch_ens_prep_wk(alabi_ens* e, const int* order, const double* u_acc, hipStream_t s) {
+    hipLaunchKernelGGL(ens_prep_wk_kernel, dim3((e->W + 255) / 256), dim3(256), 0, s, order, e->W, u_acc, e->draws, e->mv);
+    ALABI_LAUNCH_CHECK();
+    return ALABI_OK;
+}
+
+int launch_ens_set_step_move(alabi_ens* e, int kind, double p0, double p1, hipStream_t s) {
+    hipLaunchKernelGGL(ens_set_step_move_kernel, dim3(1), dim3(64), 0, s, e->mv, kind, p0, p1);
+    ALABI_LAUNCH_CHECK();
+    return ALABI_OK;
+}
+
+// in front of a half step of a set with a KDE move: one workgroup per ensemble, which leaves at once where the step's move is another
+int launch_ens_kde_prepass(alabi_ens* e, const HalfArgs& args, hipStream_t s) {
+    if (!args.mvkind || !args.mvpar || !args.kde.white || args.shist) return ALABI_BAD_ARGUMENT;
+    hipLaunchKernelGGL(ens_kde_prepass_kernel, dim3(e->E), dim3(256), 0, s, args);
+    ALABI_LAUNCH_CHECK();
+    return ALABI_OK;
+}
+
 int launch_ens_half_args(alabi_ens* e, const HalfArgs& args_in, int nblocks, hipStream_t s) {
     if (nblocks <= 0) return ALABI_OK;
     const int db = dim_bucket(e->d);
@@ -913,7 +1307,10 @@ int launch_ens_half_args(alabi_ens* e, const HalfArgs& args_in, int nblocks, hip
         if (env && env[0] == '2') np = 2;
         if (env && env[0] == '1') np = 1;
     }
-    if (args.cw3) {                                   // records with a third partner: one proposal per workgroup
+    if (args.mvkind) {                                // a set with a walk or KDE move: one proposal per workgroup
+        if (args.shist || !args.cw2 || !args.cw3 || !args.mvpar) return ALABI_BAD_ARGUMENT;
+        ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(e->gp->kf.type, hipLaunchKernelGGL((ens_half_wk_kernel<D, GENERIC>), dim3(nblocks, e->E), dim3(threads), 0, s, args)));
+    } else if (args.cw3) {                            // records with a third partner: one proposal per workgroup
         if (args.shist || !args.cw2) return ALABI_BAD_ARGUMENT;
         ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(e->gp->kf.type, hipLaunchKernelGGL((ens_half_snooker_kernel<D, GENERIC>), dim3(nblocks, e->E), dim3(threads), 0, s, args)));
     } else if (args.cw2) {                            // records with a second partner: the two-partner instantiations
@@ -954,7 +1351,11 @@ int launch_ens_lnprob(alabi_ens* e, const double* coords, int nwalkers, double* 
 int launch_ens_propose(alabi_ens* e, const HalfArgs& args, int nblocks, int gate_box, double* q, double* like, hipStream_t s) {
     if (nblocks <= 0) return ALABI_OK;
     const int db = dim_bucket(e->d);
-    if (args.cw3) {
+    if (args.mvkind) {
+        if (!args.cw2 || !args.cw3 || !args.mvpar) return ALABI_BAD_ARGUMENT;
+        ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(e->gp->kf.type, hipLaunchKernelGGL((ens_propose_wk_kernel<D, GENERIC>), dim3(nblocks),
+                                                                                        dim3(e->threads), 0, s, args, gate_box, q, like)));
+    } else if (args.cw3) {
         if (!args.cw2) return ALABI_BAD_ARGUMENT;
         ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(e->gp->kf.type, hipLaunchKernelGGL((ens_propose_snooker_kernel<D, GENERIC>), dim3(nblocks),
                                                                                         dim3(e->threads), 0, s, args, gate_box, q, like)));

@@ -1,8 +1,8 @@
 """Proposal moves of the ensemble sampler: emcee's ``EnsembleSampler(moves=...)``.
 
 The reference documents ``sampler_kwargs['moves']`` ("Custom proposal moves", alabi/core.py:2144) and hands it to
-``emcee.EnsembleSampler`` (alabi/core.py:2319).  Three moves run on the GPU here, alone or as a weighted mixture from which
-ONE move is chosen per step, as emcee does:
+``emcee.EnsembleSampler`` (alabi/core.py:2319).  Five moves run on the GPU here -- emcee's whole red-blue family --, alone or as a
+weighted mixture from which ONE move is chosen per step, as emcee does:
 
 * ``StretchMove(a=2.0)``        -- emcee 3 ``moves/stretch.py`` (the default);
 * ``DEMove(sigma, gamma0)``     -- emcee 3 ``moves/de.py``: q = s + gamma (C[j2] - C[j1]) with two distinct walkers of the
@@ -11,21 +11,34 @@ ONE move is chosen per step, as emcee does:
   distinct walkers z, z1, z2 of the complementary set, e the unit vector from z to s, q = s + gammas (e.z1 - e.z2) e, log
   factor (ndim - 1) (ln|q - z| - ln|s - z|).  Typically mixed with DE: ``[(DEMove(), 0.8), (SnookerMove(), 0.2)]``.
 
-``parse_moves`` is pure host code (no GPU, no library): it accepts what emcee accepts -- None, one move, a list of moves, a
+* ``WalkMove(s=None)``           -- emcee 3 ``moves/walk.py`` (Goodman & Weare 2010): a draw from the Gaussian around the walker with
+  the sample covariance of ``s`` walkers of the complementary set (all of them by default), formed without a factorisation as
+  q = x + sum_j z_j (C[j] - mean) / sqrt(s - 1) with standard normal z_j; log factor 0;
+* ``KDEMove(bw_method=None)``   -- emcee 3 ``moves/kde.py``: an independence sampler that draws from a Gaussian KDE of the
+  complementary set (``scipy.stats.gaussian_kde``'s "scott", "silverman" or scalar bandwidth) with the Hastings factor
+  kde.logpdf(x) - kde.logpdf(q); it hops between separated modes in one step.  It wants MANY walkers per dimension: with 6
+  complementary walkers in 5-D it still samples the right distribution but accepts about 5 % of its proposals.  A complementary
+  set without a Cholesky factor (emcee raises ``LinAlgError``) rejects that half step's proposals and is counted in
+  ``EnsembleSampler.kde_singular_half_steps``.
+
+The subset of a walk move, the KDE move's row and all normals are counter-based Philox draws (streams 6-8 of the library), not
+emcee's ``RandomState``.  ``parse_moves`` is pure host code (no GPU, no library): it accepts what emcee accepts -- None, one move, a list of moves, a
 list of (move, weight) pairs -- and recognises this module's classes as well as foreign ``StretchMove`` / ``DEMove`` objects by
-class name and attributes, so real ``emcee.moves`` objects of these two classes work where emcee is installed.  Every other
-move raises ``NotImplementedError``; that includes emcee's ``DESnookerMove``, which stands for different arithmetic (half the
+class name and attributes (``WalkMove`` with ``s``, ``KDEMove`` with ``bw_method`` too), so real ``emcee.moves`` objects of these
+classes work where emcee is installed.  Every other move raises ``NotImplementedError``: the Metropolis moves (``MHMove``,
+``GaussianMove``), which do not split the ensemble, and emcee's ``DESnookerMove``, which stands for different arithmetic (half the
 published log factor, a four-way split): ask for ``SnookerMove`` instead.
 """
 from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["StretchMove", "DEMove", "SnookerMove", "MoveSet", "parse_moves", "MAX_MOVES", "KIND_STRETCH", "KIND_DE",
-           "KIND_SNOOKER"]
+__all__ = ["StretchMove", "DEMove", "SnookerMove", "WalkMove", "KDEMove", "MoveSet", "parse_moves", "MAX_MOVES", "KIND_STRETCH",
+           "KIND_DE", "KIND_SNOOKER", "KIND_WALK", "KIND_KDE", "WALK_MAX_NC"]
 
 MAX_MOVES = 8                    # ALABI_MAX_MOVES of the library: the table travels in the draw kernel's arguments
-KIND_STRETCH, KIND_DE, KIND_SNOOKER = 0, 1, 2
+KIND_STRETCH, KIND_DE, KIND_SNOOKER, KIND_WALK, KIND_KDE = 0, 1, 2, 3, 4
+WALK_MAX_NC = 2048               # rows of a complementary half the walk move's kernel lists hold
 
 
 class StretchMove:
@@ -67,8 +80,58 @@ class SnookerMove:
         return f"SnookerMove(gammas={self.gammas})"
 
 
-def _table_row(m, ndim):
-    """(kind, p0, p1) of a move in the library's table."""
+class WalkMove:
+    """Walk move (emcee.moves.WalkMove; Goodman & Weare 2010): a Gaussian proposal with the sample covariance of ``s`` walkers of
+    the complementary set, ``s=None``: all of them.  Needs 2 <= s <= nwalkers // 2."""
+
+    def __init__(self, s=None):
+        if s is not None:
+            if int(s) != s or int(s) < 2:
+                raise ValueError("WalkMove needs an integer s >= 2 (or None for the whole complementary set)")
+            s = int(s)
+        self.s = s
+
+    def __repr__(self):
+        return f"WalkMove(s={self.s})"
+
+
+class KDEMove:
+    """KDE move (emcee.moves.KDEMove): proposals from a Gaussian kernel density estimate of the complementary set, with
+    ``bw_method`` as ``scipy.stats.gaussian_kde`` takes it -- None / "scott", "silverman" or a scalar; a callable is refused.
+    Needs nwalkers >= 2 ndim + 2, and many more to accept often."""
+
+    def __init__(self, bw_method=None):
+        if callable(bw_method):
+            raise NotImplementedError("KDEMove(bw_method=<callable>) is not available on the GPU: the bandwidth factor is resolved "
+                                      "on the host before the run; pass 'scott', 'silverman' or a scalar")
+        if isinstance(bw_method, str):
+            if bw_method not in ("scott", "silverman"):
+                raise ValueError("`bw_method` should be 'scott', 'silverman' or a scalar")
+        elif bw_method is not None:
+            bw_method = float(bw_method)
+            if not (np.isfinite(bw_method) and bw_method > 0.0):
+                raise ValueError("KDEMove needs a positive, finite scalar bw_method")
+        self.bw_method = bw_method
+
+    def factor(self, nc, ndim):
+        """The bandwidth factor for ``nc`` complementary walkers, as gaussian_kde resolves it with unit weights (neff = nc)."""
+        from types import SimpleNamespace
+        from .kde import kde_factor
+        return float(kde_factor(self.bw_method, SimpleNamespace(neff=float(nc), d=int(ndim))))
+
+    def __repr__(self):
+        return f"KDEMove(bw_method={self.bw_method!r})"
+
+
+def _table_row(m, ndim, nc=None):
+    """(kind, p0, p1) of a move in the library's table.  ``nc`` = (|C| of split 0, |C| of split 1): a KDE move's two factors need
+    it and are NaN without."""
+    if isinstance(m, WalkMove):
+        return KIND_WALK, 0.0 if m.s is None else float(m.s), 0.0
+    if isinstance(m, KDEMove):
+        if nc is None:
+            return KIND_KDE, np.nan, np.nan
+        return KIND_KDE, m.factor(nc[0], ndim), m.factor(nc[1], ndim)
     if isinstance(m, DEMove):
         return KIND_DE, 2.38 / np.sqrt(2 * ndim) if m.gamma0 is None else m.gamma0, m.sigma
     if isinstance(m, SnookerMove):
@@ -78,17 +141,50 @@ def _table_row(m, ndim):
 
 class MoveSet:
     """A parsed move set: ``moves`` (this module's objects), normalised ``weights`` and the table the library takes --
-    ``kind``, ``cum`` = np.cumsum(w / w.sum()), ``p0`` (a | gamma0 with its default resolved | gammas), ``p1`` (0 | sigma | 0)."""
+    ``kind``, ``cum`` = np.cumsum(w / w.sum()), ``p0`` (a | gamma0 with its default resolved | gammas | s, 0 for all | KDE factor of
+    split 0), ``p1`` (0 | sigma | 0 | 0 | KDE factor of split 1).  The KDE factors depend on the number of walkers: they are NaN
+    until ``resolve(nwalkers)`` (called by EnsembleSampler, or pass ``nwalkers`` here)."""
 
-    def __init__(self, moves, weights, ndim):
+    def __init__(self, moves, weights, ndim, nwalkers=None):
         self.moves = list(moves)
+        self.ndim = int(ndim)
         w = np.asarray(weights, dtype=np.float64)
         self.weights = w / w.sum()
         self.cum = np.cumsum(w / w.sum())
-        rows = [_table_row(m, ndim) for m in self.moves]
+        self.nwalkers = None
+        self._fill(None)
+        if nwalkers is not None:
+            self.resolve(nwalkers)
+
+    def _fill(self, nc):
+        rows = [_table_row(m, self.ndim, nc) for m in self.moves]
         self.kind = np.array([r[0] for r in rows], dtype=np.int32)
         self.p0 = np.array([r[1] for r in rows], dtype=np.float64)
         self.p1 = np.array([r[2] for r in rows], dtype=np.float64)
+
+    def resolve(self, nwalkers):
+        """Check the moves against the number of walkers and fill in what depends on it (the KDE factors).  The complementary set
+        has W - n0 walkers in split 0 and n0 in split 1, n0 = (W + 1) // 2."""
+        W = int(nwalkers)
+        n0 = (W + 1) // 2
+        nc = (W - n0, n0)
+        for m in self.moves:
+            if isinstance(m, WalkMove):
+                s0 = min(nc) if m.s is None else m.s
+                if min(nc) < 2:
+                    raise ValueError("WalkMove needs two walkers in each half of the ensemble: nwalkers >= 4")
+                if s0 > min(nc):
+                    raise ValueError(f"WalkMove(s={m.s}) draws s distinct walkers from the complementary half, which has {min(nc)} "
+                                     f"with nwalkers = {W}: s <= nwalkers // 2")
+                if max(nc) > WALK_MAX_NC:
+                    raise ValueError(f"WalkMove runs with at most {2 * WALK_MAX_NC} walkers per ensemble")
+            elif isinstance(m, KDEMove):
+                if min(nc) < self.ndim + 1:
+                    raise ValueError(f"KDEMove needs more complementary walkers than dimensions (a covariance of full rank): nwalkers "
+                                     f">= 2 ndim + 2 = {2 * self.ndim + 2}, got {W}")
+        self.nwalkers = W
+        self._fill(nc)
+        return self
 
     @property
     def has_de(self):
@@ -99,9 +195,18 @@ class MoveSet:
         return bool(np.any(self.kind == KIND_SNOOKER))
 
     @property
+    def has_walk(self):
+        return bool(np.any(self.kind == KIND_WALK))
+
+    @property
+    def has_kde(self):
+        return bool(np.any(self.kind == KIND_KDE))
+
+    @property
     def multi_partner(self):
-        """Some move reads more than one partner row (DE, snooker): one launch per half step, no sharding."""
-        return self.has_de or self.has_snooker
+        """Some move reads more than one partner row (DE, snooker) or the whole complementary half (walk, KDE): one launch per
+        half step, no sharding."""
+        return self.has_de or self.has_snooker or self.has_walk or self.has_kde
 
     def __len__(self):
         return len(self.moves)
@@ -109,9 +214,13 @@ class MoveSet:
 
 def _as_move(obj):
     """This module's move for ``obj``: one of its own, or a foreign object recognised by class name and attributes."""
-    if isinstance(obj, (StretchMove, DEMove, SnookerMove)):
+    if isinstance(obj, (StretchMove, DEMove, SnookerMove, WalkMove, KDEMove)):
         return obj
     name = type(obj).__name__
+    if name == "WalkMove" and hasattr(obj, "s"):
+        return WalkMove(s=obj.s)
+    if name == "KDEMove" and hasattr(obj, "bw_method"):
+        return KDEMove(bw_method=obj.bw_method)
     if name == "StretchMove" and hasattr(obj, "a"):
         return StretchMove(a=obj.a)
     if name == "DEMove" and hasattr(obj, "sigma") and hasattr(obj, "gamma0"):
@@ -120,8 +229,8 @@ def _as_move(obj):
     if name == "DESnookerMove":
         hint = ("; emcee's DESnookerMove stands for different arithmetic (half the published log factor, a four-way split) -- "
                 "use alabi_amd.moves.SnookerMove, the published snooker update")
-    raise NotImplementedError(f"move {name} is not available on the GPU: the ensemble sampler runs StretchMove, DEMove, "
-                              f"alabi_amd.moves.SnookerMove and weighted mixtures of them{hint}")
+    raise NotImplementedError(f"move {name} is not available on the GPU: the ensemble sampler runs StretchMove, DEMove, WalkMove, "
+                              f"KDEMove, alabi_amd.moves.SnookerMove and weighted mixtures of them{hint}")
 
 
 def parse_moves(moves, ndim):

@@ -55,11 +55,14 @@ class EnsembleSampler:
         ``like_fn=None`` the surrogate part is evaluated by the propose kernel; ``gate_box`` says whether that value is
         -inf outside ``bounds`` (True when the prior is the box itself, False when ``prior_fn`` is the whole prior).
         ``moves``: emcee's proposal moves (alabi_amd.moves) -- None (the stretch move with ``a``), a ``StretchMove``,
-        ``DEMove`` or ``SnookerMove`` (the snooker update of ter Braak & Vrugt 2008), a list of them, or a list of (move, weight)
-        pairs from which one move is chosen per step; emcee's own ``StretchMove`` / ``DEMove`` objects are recognised, its
-        ``DESnookerMove`` is refused (different arithmetic).  Works with ``n_ensembles`` > 1 and with host callables; a set holding a
-        ``DEMove`` needs ``nwalkers >= 4``, one holding a ``SnookerMove`` ``nwalkers >= 6``; either runs with one launch per half
-        step and cannot be sharded.
+        ``DEMove``, ``SnookerMove`` (the snooker update of ter Braak & Vrugt 2008), ``WalkMove`` or ``KDEMove``, a list of them, or a
+        list of (move, weight) pairs from which one move is chosen per step; emcee's own ``StretchMove`` / ``DEMove`` / ``WalkMove`` /
+        ``KDEMove`` objects are recognised, its ``DESnookerMove`` and its Metropolis moves are refused.  Works with ``n_ensembles``
+        > 1 and with host callables; a set holding a ``DEMove`` needs ``nwalkers >= 4``, one holding a ``SnookerMove`` ``nwalkers >=
+        6``, a ``WalkMove(s)`` ``2 <= s <= nwalkers // 2``, a ``KDEMove`` ``nwalkers >= 2 ndim + 2`` (and warns below about
+        ``8 (ndim + 1)``: few walkers per dimension mean few accepted proposals); each of these runs with one launch per half step
+        and cannot be sharded.  ``kde_singular_half_steps`` counts the half steps whose KDE had no Cholesky factor (all their
+        proposals were rejected; emcee would raise ``LinAlgError``).
         ``shard=True`` under an initialised ``torch.distributed`` group of more than one rank (``group``: default WORLD): ONE
         ensemble whose active half is partitioned over the ranks, an all-gather of the new rows per half step
         (alabi_amd.dist.ShardedRun -> alabi_ens_run_sharded); every rank must construct the sampler with the same arguments and
@@ -105,8 +108,14 @@ class EnsembleSampler:
             if self._move_set.has_snooker and self.nwalkers < 6:
                 raise ValueError("SnookerMove draws three distinct walkers from the complementary half: nwalkers >= 6")
             if self.shard:
-                raise ValueError("shard=True cannot run a DEMove or a SnookerMove: the sharded history links one partner row per "
-                                 "proposal")
+                raise ValueError("shard=True cannot run a DEMove, SnookerMove, WalkMove or KDEMove: the sharded history links one "
+                                 "partner row per proposal")
+            self._move_set.resolve(self.nwalkers)          # WalkMove's s and KDEMove's ndim against nwalkers; the KDE factors
+            if self._move_set.has_kde and self.nwalkers // 2 < 4 * (self.ndim + 1):
+                import warnings
+                warnings.warn(f"KDEMove with {self.nwalkers // 2} complementary walkers in {self.ndim} dimensions: a kernel density "
+                              f"estimate from fewer than about 4 (ndim + 1) = {4 * (self.ndim + 1)} points makes poor proposals and "
+                              "few are accepted (about 5 % with 6 walkers in 5-D); use more walkers", RuntimeWarning, stacklevel=2)
         if seed is None:
             seed = int(np.random.SeedSequence().generate_state(2, dtype=np.uint32).view(np.uint64)[0])
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -158,6 +167,16 @@ class EnsembleSampler:
             from .moves import StretchMove
             return [(StretchMove(self.a), 1.0)]
         return list(zip(self._move_set.moves, (float(w) for w in self._move_set.weights)))
+
+    @property
+    def kde_singular_half_steps(self):
+        """Half steps (counted per ensemble) of this sampler's handle in which a KDEMove found a complementary set without a
+        Cholesky factor -- emcee would raise LinAlgError; here every proposal of that half step was rejected."""
+        if getattr(self, "_ens", None) is None:
+            return 0
+        n = C.c_longlong(0)
+        _lib.check(_lib.lib().alabi_ens_kde_singular(self._ens, C.byref(n)), "alabi_ens_kde_singular")
+        return int(n.value)
 
     def _release(self):
         _lib.destroy(getattr(self, "_ens", None), "alabi_ens_destroy", sync=True)

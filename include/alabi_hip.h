@@ -232,7 +232,19 @@ int alabi_ens_set_logp_map(alabi_ens* ens, int kind);
  * the `a` of each call); with n > 0 the `a` arguments of run / draw / export_draws are not used.  Streams 0-2 (labels, u_z and
  * partner, u') do not depend on the moves, streams 3-4 not on a snooker move.  A set holding a DE move needs W >= 4, one holding a
  * snooker move W >= 6; either runs alabi_ens_run with one launch per half step (a snooker set: one proposal per workgroup) and
- * is refused by the sharded run.  Takes effect from the next call on. */
+ * is refused by the sharded run.  Takes effect from the next call on.
+ * kind 3 = WalkMove (Goodman & Weare 2010; emcee 3 moves/walk.py) with p0 = s0, the size of the subset J of the complementary half
+ * (0: the whole half) and p1 = 0: q = s + sum_{j in J} z_j (C[j] - mean_J) / sqrt(s0 - 1), z_j standard normal, log factor 0 -- a
+ * draw from the Gaussian with the sample covariance of the subset.  Needs 2 <= s0 <= W / 2 (the smaller half; integral) and
+ * (W + 1) / 2 <= 2048.  kind 4 = KDEMove (emcee 3 moves/kde.py) with p0 / p1 = the bandwidth factor f (> 0) of split 0 / split 1
+ * (the halves of an odd W differ in size; scipy.stats.gaussian_kde's scotts_factor / silverman_factor / scalar, resolved by the
+ * caller): once per half step the mean, the unbiased covariance and the Cholesky factor L of f^2 cov of the complementary half,
+ * q = C[r] + L z, log factor kde.logpdf(s) - kde.logpdf(q).  Needs W / 2 >= d + 1.  A factorisation with a pivot that is not
+ * positive and finite (emcee would raise LinAlgError) rejects every proposal of that half step and ensemble and is counted
+ * (alabi_ens_kde_singular).  The subset, r and the normals come from Philox streams 6-8 where the proposal is formed (layout in
+ * ensemble.hip); streams 0-5 do not depend on these moves.  Both run like a snooker set: one launch per half step, one proposal
+ * per workgroup, in front of every half step of a set with a KDE move one pre-pass launch; refused by the sharded run.  A
+ * violated bound is ALABI_BAD_ARGUMENT. */
 int alabi_ens_set_moves(alabi_ens* ens, int n, const int* kind, const double* cum, const double* p0, const double* p1);
 
 /* Enable / disable the persistent dataflow kernel for alabi_ens_run on this handle (default: enabled when the
@@ -404,6 +416,24 @@ int alabi_ens_export_partner_ids(alabi_ens* ens, int* cw2, int* cw3, void* strea
 int alabi_ens_step_with_randoms_snooker(alabi_ens* ens, double* coords, double* logp, const int* order, int n0,
                                         const int* j1, const int* j2, const int* j3, double gamma, const double* u_acc,
                                         long long* n_accept, void* stream);
+
+/* Test entries of the walk and KDE moves (kinds 3 and 4 of alabi_ens_set_moves; emcee's moves= as documented at
+ * alabi/core.py:2144 and handed over at alabi/core.py:2319), siblings of alabi_ens_step_with_randoms_de / _snooker
+ * (n_ensembles == 1, all arrays on the device, draws keyed by WALKER id).
+ * alabi_ens_step_with_randoms_walk: one full walk step; subset[W, s0] int32 indexes the complementary list (s0 distinct rows per
+ * walker), z[W, s0] holds the rows' normals, the sums run over m = 0 .. s0-1 in that order.  Out-of-range or repeated subset
+ * indices make that proposal a no-op.  2 <= s0 <= min(n0, W - n0), both halves <= 2048, else ALABI_BAD_ARGUMENT.
+ * alabi_ens_step_with_randoms_kde: one full KDE step with the bandwidth factor `factor` for both splits; r[W] int32 is the row of
+ * the complementary list, z[W, d] the normals, lnfac_out[W] (nullable) receives the proposals' log factor.  An out-of-range r
+ * makes that proposal a no-op.  Both halves need between d + 1 and (W + 1) / 2 rows, else ALABI_BAD_ARGUMENT.
+ * alabi_ens_kde_singular: the number of (half step, ensemble) pairs of this handle whose KDE had no Cholesky factor (host value;
+ * synchronises the device). */
+int alabi_ens_step_with_randoms_walk(alabi_ens* ens, double* coords, double* logp, const int* order, int n0, int s0,
+                                     const int* subset, const double* z, const double* u_acc, long long* n_accept, void* stream);
+int alabi_ens_step_with_randoms_kde(alabi_ens* ens, double* coords, double* logp, const int* order, int n0, double factor,
+                                    const int* r, const double* z, const double* u_acc, double* lnfac_out, long long* n_accept,
+                                    void* stream);
+int alabi_ens_kde_singular(alabi_ens* ens, long long* count /* host */);
 
 /* Nested sampling (dynesty's NestedSampler / DynamicNestedSampler with sample="rwalk" as driven by
  * SurrogateModel.run_dynesty, alabi/core.py:2417-2787, likelihood = surrogate_log_likelihood core.py:1446-1508, prior =

@@ -1,8 +1,10 @@
-"""Launch-per-half-step cost of the DE and snooker moves against the stretch move at C3 (N = 2000, d = 10, W = 256).
+"""Launch-per-half-step cost of the DE, snooker, walk and KDE moves against the stretch move at C3 (N = 2000, d = 10, W = 256).
 
 A move set holding a DEMove or a SnookerMove runs alabi_ens_run with one launch per half step (the two- and three-partner
 instantiations of ens_half_kernel); the stretch move is measured on the same path (ALABI_ENS_STREAM=0), so the sets differ in
-the proposal's construction alone.  Prints the median of --runs timed runs of --steps steps each, in us per half step, as one
+the proposal's construction alone.  A set holding a WalkMove or a KDEMove runs the whole-half instantiation, a KDE set one
+pre-pass launch in front of every half step as well ("de_with_idle_prepass": a KDE move of weight 0 beside DE, so the pre-pass
+is launched and leaves at once).  Prints the median of --runs timed runs of --steps steps each, in us per half step, as one
 JSON line.
 
     python tools/prof_moves.py                      # this checkout
@@ -67,4 +69,14 @@ else:
     else:
         out["snooker"] = measure(moves=SnookerMove())
         out["de_snooker_mix"] = measure(moves=[(DEMove(), 0.8), (SnookerMove(), 0.2)])
+    try:
+        from alabi_amd.moves import KDEMove, WalkMove
+    except ImportError:
+        out["walk"] = None                          # a checkout without the walk and KDE moves
+    else:
+        out["walk"] = measure(moves=WalkMove())
+        out["walk_s8"] = measure(moves=WalkMove(s=8))
+        out["kde"] = measure(moves=KDEMove())
+        out["de_kde_mix"] = measure(moves=[(DEMove(), 0.7), (KDEMove(), 0.3)])
+        out["de_with_idle_prepass"] = measure(moves=[(DEMove(), 1.0), (KDEMove(), 0.0)])
 print(json.dumps(out))
