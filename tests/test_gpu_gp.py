@@ -79,6 +79,8 @@ def test_kernel_get_value(torch_gpu):
     X2 = np.random.RandomState(1).uniform(-3, 3, (70, 6))
     K = g.kernel.get_value(X, X2)
     np.testing.assert_allclose(K, sqexp_kernel(X, X2, h["log_amp"], h["log_M"]), rtol=1e-13, atol=1e-300)
+    # the whole range of r^2 (0, the denormal tail, exact underflow) against an extended-precision reference, element by element
+    # through the forward-error bound of exp_neg_half: tests/test_gpu_kernel_sums.py::test_kernel_matrix
 
 
 def test_known_answers_and_properties(torch_gpu):
