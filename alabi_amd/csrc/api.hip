@@ -405,6 +405,12 @@ int alabi_gp_last_factor_path(alabi_gp* gp, int* path) {
     return ALABI_OK;
 }
 
+int alabi_gp_last_solve_path(alabi_gp* gp, int* path) {
+    if (!gp || !path) return ALABI_BAD_ARGUMENT;
+    *path = gp->solve_path;
+    return ALABI_OK;
+}
+
 int alabi_gp_get_inverse(alabi_gp* gp, double* Kinv_out, void* stream) {
     if (!gp || !Kinv_out) return ALABI_BAD_ARGUMENT;
     if (!gp->computed) return ALABI_NOT_COMPUTED;

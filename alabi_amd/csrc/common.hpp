@@ -105,6 +105,7 @@ struct alabi_gp {
     double* Xc = nullptr;     // [dim_bucket(d), Npad]
     double* ens_h = nullptr;  // [Npad]
     long long ens_h_gen = -1;
+    int solve_path = 0;       // alabi_gp_last_solve_path: which kernels produced alpha (launch_alpha)
 };
 
 namespace alabi {

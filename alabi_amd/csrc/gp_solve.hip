@@ -267,6 +267,7 @@ int launch_alpha(alabi_gp* gp, hipStream_t s) {
     static std::atomic<int> stream_penalty{0};
     const bool penalised = stream_penalty.load(std::memory_order_relaxed) > 0;
     if (penalised) stream_penalty.fetch_sub(1, std::memory_order_relaxed);
+    bool timed_out = false;
     if (nb <= 200 && gp->flags && !penalised && !(env && env[0] == '0')) {
         // single-launch dataflow solve (all nb workgroups resident); z / alpha hand-off buffers live in `work`
         unsigned long long* zbuf = reinterpret_cast<unsigned long long*>(z);
@@ -280,9 +281,10 @@ int launch_alpha(alabi_gp* gp, hipStream_t s) {
         int flag = 0;
         ALABI_HIP_CHECK(hipMemcpyAsync(&flag, gp->flags, sizeof(int), hipMemcpyDeviceToHost, s));
         ALABI_HIP_CHECK(hipStreamSynchronize(s));
-        if (!flag) return ALABI_OK;
+        if (!flag) { gp->solve_path = 1; return ALABI_OK; }
         // timed out (workgroups not co-resident?): fall through to the launch-per-step kernels, and skip the dataflow
         // kernel for the next 256 solves of this process
+        timed_out = true;
         stream_penalty.store(256, std::memory_order_relaxed);
         hipLaunchKernelGGL(residual_kernel, dim3((gp->Npad + 255) / 256), dim3(256), 0, s, gp->y, gp->N, gp->Npad, gp->mean, r);
     }
@@ -291,6 +293,7 @@ int launch_alpha(alabi_gp* gp, hipStream_t s) {
     for (int kb = nb - 1; kb >= 0; --kb)
         hipLaunchKernelGGL(trsv_bwd_step_kernel, dim3(kb + 1), dim3(256), 0, s, gp->L, ld, kb, gp->dinv, z, gp->alpha);
     ALABI_LAUNCH_CHECK();
+    gp->solve_path = timed_out ? 3 : 2;
     return ALABI_OK;
 }
 

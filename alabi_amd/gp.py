@@ -97,6 +97,14 @@ class _SolverView:
         _lib.check(_lib.lib().alabi_gp_last_factor_path(self._gp._handle, C.byref(out)), "alabi_gp_last_factor_path")
         return {0: None, 1: "steps", 2: "queue", 3: "queue-timeout"}[out.value]
 
+    @property
+    def solve_path(self):
+        """Which kernels produced the current alpha: "stream" (one-launch dataflow solve), "steps" (launch per block step) or
+        "stream-timeout" (the dataflow solve's wait ran out; solved again step by step).  None before the first solve."""
+        out = C.c_int(0)
+        _lib.check(_lib.lib().alabi_gp_last_solve_path(self._gp._handle, C.byref(out)), "alabi_gp_last_solve_path")
+        return {0: None, 1: "stream", 2: "steps", 3: "stream-timeout"}[out.value]
+
     def get_factor(self):
         gp = self._gp
         gp._require_computed()

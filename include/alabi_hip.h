@@ -167,6 +167,10 @@ int alabi_gp_n(alabi_gp* gp, int* n /* host */);
 /* How the last alabi_gp_compute factorised (tests, soak runs): 0 = not computed, 1 = launch per step, 2 = the one-launch task queue,
  * 3 = the queue's wait ran out and the matrix was assembled and factorised again step by step. */
 int alabi_gp_last_factor_path(alabi_gp* gp, int* path /* host */);
+/* Which kernels produced the handle's current alpha (the last alabi_gp_set_y): 0 = none yet, 1 = the one-launch dataflow solve,
+ * 2 = launch per block step (ALABI_TRSV_STREAM=0, more than 200 block rows, or within 256 solves of a time-out), 3 = the dataflow
+ * solve's wait ran out and the launch-per-step kernels solved again. */
+int alabi_gp_last_solve_path(alabi_gp* gp, int* path /* host */);
 
 /* kernel.get_value(x1, x2) -- alabi/utility.py:549, :607.  K_out is [n1,n2] row-major,
  * no white noise. */

@@ -4,7 +4,8 @@ k-fold cross-validation search, reference alabi/gp_utils.py:511-700 and alabi/co
 * factors bit-identical to the single-matrix path (alabi_gp_compute on the same rows with the same hyper-parameters),
   alpha / log-likelihood / held-out mean against that path and against the oracle;
 * fold scores against vectors produced by the REFERENCE's own worker (tests/golden/make_golden_cv.py);
-* a job that is not positive definite does not disturb its neighbours; the launch-per-step fallback gives the same results."""
+* a job that is not positive definite does not disturb its neighbours; the launch-per-step fallback gives the same results.
+The batch's factors, alpha and likelihood against an extended-precision truth: tests/test_gpu_solve_truth.py::test_batched_fit."""
 import os
 
 import numpy as np

@@ -7,6 +7,8 @@ Tolerances (fp64, stated per quantity):
   mu*                 : |dmu| / (|mu| + 1) <= 1e-8
   var*                : |dvar| <= 1e-6 amp  (two algebraically equal formulas, error ~ cond(K) eps amp)
   logdet / logL       : 1e-9 relative
+The factor, alpha, the two reductions, K^-1 and the append are held to an extended-precision truth, element by element and at
+the honest rounding error, in tests/test_gpu_solve_truth.py; the assertions here stay as the coarse parity with the oracle.
 """
 import numpy as np
 import pytest

@@ -29,6 +29,7 @@ import numpy as np
 import pytest
 
 import kernel_sum_reference as ksr
+import solve_reference as sr
 from conftest import make_problem
 
 pytestmark = pytest.mark.gpu
@@ -152,9 +153,7 @@ def _factor_attribution(g, X, ref, amp, inv_len, M):
     Ld = g.solver.get_factor().cpu().numpy()
     K, L = np.asarray(ref["K"], dtype=ksr.LD), np.asarray(ref["L"], dtype=np.float64)
     dK = (Ld.astype(ksr.LD) @ Ld.astype(ksr.LD).T - K).astype(np.float64)
-    idx = np.minimum(np.arange(N)[:, None], np.arange(N)[None, :]) + 5.0
-    allowed = ksr.U * (idx * (np.abs(L) @ np.abs(L).T) + np.abs(K.astype(np.float64)) *
-                       (ksr.E_EXP_NEG_HALF + ksr.c_difference(d) * ksr.arg_difference(X, inv_len, X)))
+    allowed = sr.factor_allowed(X, inv_len, K, L, d)
     ks = np.asarray(ref["ks"], dtype=np.float64)[:, :M]
     v = solve_triangular(L.T, solve_triangular(L, ks, lower=True), lower=False)
     first_order = np.sum(v * (dK @ v), axis=0)
