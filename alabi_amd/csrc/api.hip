@@ -65,6 +65,28 @@ int dev_alloc_cached(void** p, size_t need, size_t* bytes) {
     return (int)hipSuccess;
 }
 
+int grow_cached(double** p, size_t* bytes, size_t need, hipStream_t s) {
+    if (need <= *bytes) return ALABI_OK;
+    if (*p) {
+        ALABI_HIP_CHECK(hipStreamSynchronize(s));
+        dev_cache_give(*p, *bytes);
+        *p = nullptr; *bytes = 0;
+    }
+    return dev_alloc_cached((void**)p, need, bytes) == (int)hipSuccess ? ALABI_OK : ALABI_NOT_COMPUTED;
+}
+
+int grow_plain(double** p, size_t* bytes, size_t need, hipStream_t s) {
+    if (need <= *bytes) return ALABI_OK;
+    if (*p) {
+        ALABI_HIP_CHECK(hipStreamSynchronize(s));
+        ALABI_HIP_CHECK(hipFree(*p));
+        *p = nullptr; *bytes = 0;
+    }
+    ALABI_HIP_CHECK(hipMalloc(p, need));
+    *bytes = need;
+    return ALABI_OK;
+}
+
 static int fill_dimvec(DimVec& v, const double* src, int d, int stride, int off, double pad) {
     for (int k = 0; k < ALABI_MAX_DIM; ++k) v.v[k] = (k < d) ? src[k * stride + off] : pad;
     return 0;
@@ -285,20 +307,14 @@ int alabi_gp_predict(alabi_gp* gp, const double* Xs, long long M, double* mu, do
     if (!gp->computed || !gp->has_alpha) return ALABI_NOT_COMPUTED;
     if (M == 0) return ALABI_OK;
     hipStream_t s = as_stream(stream);
+    const PredictSwitches sw = predict_switches();
     if (var) {
-        // up to 128 queries (64 beyond Npad = 2048): groups of 16 multiply with the cached L^-1, one workgroup per (block row,
-        // group), K* evaluated in place -- no pre-pass, no substitution chain (the path of per-point objective calls:
-        // utility.py:1030-1163, core.py:1441, and of small batches); measured cross-over against the tile kernels with the
-        // split K* pre-pass: tools/prof_medium_batch.py
-        const char* env = getenv("ALABI_PV_SMALL");
-        const long long small_max = gp->Npad <= 2048 ? 128 : 64;
-        if (M <= small_max && gp->Npad >= 256 && gp->d <= 32 && !(env && env[0] == '0')) {
-            (void)want_winv(gp, M);            // count the request
-            return launch_predict_var_small(gp, Xs, (int)M, mu, var, s);
-        }
-        return launch_predict_var(gp, Xs, M, mu, var, s);
+        // small batches: groups of 16 multiply with the cached L^-1, one workgroup per (block row, group), K* evaluated in
+        // place -- no pre-pass, no substitution chain (the path of per-point objective calls: utility.py:1030-1163, core.py:1441)
+        if (predict_var_small(M, gp->Npad, gp->d, sw)) return launch_predict_var_small(gp, Xs, (int)M, mu, var, sw, s);
+        return launch_predict_var(gp, Xs, M, mu, var, sw, s);
     }
-    return launch_predict_mean(gp, Xs, M, mu, s);
+    return launch_predict_mean(gp, Xs, M, mu, sw, s);
 }
 
 int alabi_gp_predict_grad(alabi_gp* gp, const double* Xs, long long M, double* mu, double* var, double* dmu, double* dvar,
@@ -448,22 +464,14 @@ int alabi_utility_scan(alabi_gp* gp, int algo, const double* Xs, long long M, co
     hipStream_t s = as_stream(stream);
     const int nblocks = 1024;
     const size_t need = ((size_t)3 * M + 2 * nblocks) * sizeof(double);
-    if (need > gp->scan_bytes) {
-        if (gp->scan) {
-            ALABI_HIP_CHECK(hipStreamSynchronize(s));
-            ALABI_HIP_CHECK(hipFree(gp->scan));
-            gp->scan = nullptr; gp->scan_bytes = 0;
-        }
-        ALABI_HIP_CHECK(hipMalloc(&gp->scan, need));
-        gp->scan_bytes = need;
-    }
+    int st;
+    if ((st = grow_plain(&gp->scan, &gp->scan_bytes, need, s)) != ALABI_OK) return st;
     double* pv = gp->scan;
     long long* pi = reinterpret_cast<long long*>(gp->scan + nblocks);
     double* mu = mu_out ? mu_out : gp->scan + 2 * nblocks;
     double* var = var_out ? var_out : gp->scan + 2 * nblocks + M;
     double* uu = u ? u : gp->scan + 2 * nblocks + 2 * M;
-    int st;
-    if ((st = launch_predict_var(gp, Xs, M, mu, var, s)) != ALABI_OK) return st;
+    if ((st = launch_predict_var(gp, Xs, M, mu, var, predict_switches(), s)) != ALABI_OK) return st;
     DimVec lo, hi;
     fill_dimvec(lo, bounds, gp->d, 2, 0, 0.0);
     fill_dimvec(hi, bounds, gp->d, 2, 1, 0.0);

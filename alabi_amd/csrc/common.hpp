@@ -9,6 +9,7 @@
 
 #include "../../include/alabi_hip.h"
 #include "chol_tasks.hpp"
+#include "predict_plan.hpp"
 
 #define ALABI_BLK 64  // Cholesky / TRSM block edge; matrices are padded to a multiple of it
 
@@ -37,6 +38,14 @@ struct DimVec {
 };
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+
+// CUs of the current device; 256 when the query fails
+inline int device_cu_count() {
+    int dev = 0, n_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        n_cu <= 0) n_cu = 256;
+    return n_cu;
+}
 
 // Radial part of the stationary kernel: k(x,x') = amp * f(r2), r2 = sum_k (x_k - x'_k)^2 / M_k.
 //   0 ExpSquaredKernel exp(-r2/2)              1 Matern32Kernel (1 + s) exp(-s), s = sqrt(3 r2)
@@ -88,12 +97,10 @@ struct alabi_gp {
     size_t ws_bytes = 0;
     double* scan = nullptr;   // utility-scan scratch (partials)
     size_t scan_bytes = 0;
-    double* winv = nullptr;   // L^-1, tile-major, for variance requests of at most 16 queries (built lazily per factor)
+    double* winv = nullptr;   // L^-1, tile-major: every variance request, the gradients and the append step multiply with it (built lazily per factor)
     size_t winv_bytes = 0;
     long long factor_gen = 0; // bumped by every successful compute
     long long winv_gen = -1;  // factor_gen the cached L^-1 belongs to
-    long long req_gen = -1;   // factor_gen the counter below belongs to
-    int var_requests = 0;     // variance requests seen for the current factor (decides when the cache pays)
     double* small = nullptr;  // [Npad / 64][16] partial sums of the small-batch variance kernel
     size_t small_bytes = 0;
     double* mupart = nullptr; // partial mean sums of the K* pre-pass when the training points are split over workgroups
@@ -291,27 +298,32 @@ void chol_batch_free(CholBatchQueue& q);
 // gp_solve.hip
 int launch_alpha(alabi_gp* gp, hipStream_t s);
 int launch_reductions(alabi_gp* gp, hipStream_t s);
-// gp_predict.hip
-int launch_predict_mean(alabi_gp* gp, const double* Xs, long long M, double* mu, hipStream_t s);
-int ens_se_prepare(alabi_gp* gp, hipStream_t s);     // Xc and ens_h of the current (inputs, alpha) for the squared-exponential half-step kernels
+// gp_predict.hip (launchers; device code in predict_mean / predict_var_subst / predict_var_winv.hpp, routes and switches in predict_plan.hip).
+// The entry points of api.hip read predict_switches() once per call and hand it down.
+int launch_predict_mean(alabi_gp* gp, const double* Xs, long long M, double* mu, const PredictSwitches& sw, hipStream_t s);
 int ensure_xa(alabi_gp* gp, hipStream_t s);           // augmented, centred rows Xa of the current factor (matrix-core predict-mean, group ensemble kernel)
 // Process-wide cache of the large scratch buffers (variance workspace, cached L^-1): the reference creates a new GP object
 // for every refit (gp_utils.py:233), and a 1-2 GiB hipMalloc per new handle costs tens of milliseconds.
 void* dev_cache_take(size_t need, size_t* bytes);   // a cached buffer of at least `need` bytes, or nullptr
 void dev_cache_give(void* p, size_t bytes);         // hand a buffer back (may free it or another one)
 int dev_alloc_cached(void** p, size_t need, size_t* bytes);   // cache first, then hipMalloc; hipError_t as int
+// Grow-only scratch of a handle: afterwards *p holds at least `need` bytes.  A buffer that is too small is handed back first -- once
+// the stream has drained, kernels in flight may still use it -- to the cache above (grow_cached: ws, winv) or to hipFree (grow_plain).
+// grow_cached returns ALABI_NOT_COMPUTED when the memory cannot be had (*p is null then; the caller decides what that means),
+// either returns ALABI_HIP_ERROR for a failed runtime call.
+int grow_cached(double** p, size_t* bytes, size_t need, hipStream_t s);
+int grow_plain(double** p, size_t* bytes, size_t need, hipStream_t s);
 int launch_factor_inverse(alabi_gp* gp, hipStream_t s);
 int launch_append(alabi_gp* gp, const double* x_new, hipStream_t s);   // gp_append.hip
 int launch_factor_inverse_dnc(alabi_gp* gp, double* R, double* dst, hipStream_t s);   // gp_inverse.hip
 int launch_predict_grad(alabi_gp* gp, const double* Xs, long long M, double* mu, double* var, double* dmu, double* dvar,
                         hipStream_t s);                                  // gp_predict_grad.hip
-int want_winv(alabi_gp* gp, long long M);            // counts the request; 1 when the cached L^-1 should serve it
 int ensure_winv(alabi_gp* gp, hipStream_t s);        // the cached L^-1 of the current factor in gp->winv (ALABI_NOT_COMPUTED: no room)
 int launch_factor_inverse_into(alabi_gp* gp, double* dst, hipStream_t s);
-int launch_predict_var_small(alabi_gp* gp, const double* Xs, int M, double* mu, double* var, hipStream_t s);
+int launch_predict_var_small(alabi_gp* gp, const double* Xs, int M, double* mu, double* var, const PredictSwitches& sw, hipStream_t s);
 int launch_grad_log_likelihood(alabi_gp* gp, double* grad_dev, hipStream_t s);
 int launch_get_inverse(alabi_gp* gp, double* Kinv_out, hipStream_t s);   // gp_grad.hip: K^-1 = W^T W, [N,N] row-major
-int launch_predict_var(alabi_gp* gp, const double* Xs, long long M, double* mu, double* var,
+int launch_predict_var(alabi_gp* gp, const double* Xs, long long M, double* mu, double* var, const PredictSwitches& sw,
                        hipStream_t s);
 // utility.hip
 int launch_utility_eval(int algo, const double* Xs, long long M, int d, const DimVec& lo,
@@ -320,6 +332,7 @@ int launch_utility_eval(int algo, const double* Xs, long long M, int d, const Di
 int launch_argmin(const double* u, long long M, double* partial_val, long long* partial_idx,
                   int nblocks, hipStream_t s);
 // ensemble.hip
+int ens_se_prepare(alabi_gp* gp, hipStream_t s);     // Xc and ens_h of the current (inputs, alpha) for the squared-exponential half-step kernels
 struct HalfArgs {
     double* coords;              // [E*W,d] in/out
     double* logp;                // [E*W] in/out

@@ -99,9 +99,7 @@ int launch_cholesky_tasks(alabi_gp* gp, hipStream_t s, int* launched) {
     int ntasks = 0, st;
     const CholSwitches sw = chol_switches();
     if ((st = chol_task_list(nb, sw.list, &tasks, &ntasks)) != ALABI_OK) return st;
-    int dev = 0, n_cu = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+    const int n_cu = device_cu_count();
     int grid = ntasks < n_cu ? ntasks : n_cu;
     const int spin = sw.spin_limit;
     // eight waves per workgroup from ALABI_CHOL_W8_MIN_NB block columns on (ALABI_CHOL_W8=0 / 1 forces four / eight)
@@ -277,9 +275,7 @@ int chol_batch_prepare(CholBatchQueue& q, int B, const int* ld, double* const* A
 
 // One launch of the batched queue; the time-out flag is q.ctl[1] (read it after synchronising: non-zero = undefined matrices).
 int chol_batch_launch(CholBatchQueue& q, hipStream_t s) {
-    int dev = 0, n_cu = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+    const int n_cu = device_cu_count();
     const int grid = q.ntasks < n_cu ? q.ntasks : n_cu;
     const int spin = chol_switches().spin_limit;
     hipLaunchKernelGGL(chol_tasks8_batch_kernel, dim3(grid), dim3(512), 0, s, q.mats, q.tasks, q.ntasks, q.list_off, q.nlists, q.ctl, spin);

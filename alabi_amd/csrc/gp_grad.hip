@@ -204,15 +204,7 @@ int launch_grad_log_likelihood(alabi_gp* gp, double* grad_dev, hipStream_t s) {
     const int nb = gp->Npad / 64, nblocks = nb * (nb + 1) / 2;
     const int db = dim_bucket(gp->d);
     const size_t need = (size_t)nblocks * (db + 3) * sizeof(double);
-    if (need > gp->scan_bytes) {
-        if (gp->scan) {
-            ALABI_HIP_CHECK(hipStreamSynchronize(s));
-            ALABI_HIP_CHECK(hipFree(gp->scan));
-            gp->scan = nullptr; gp->scan_bytes = 0;
-        }
-        ALABI_HIP_CHECK(hipMalloc(&gp->scan, need));
-        gp->scan_bytes = need;
-    }
+    if ((st = grow_plain(&gp->scan, &gp->scan_bytes, need, s)) != ALABI_OK) return st;
     const double amp = exp(gp->log_amp), wn = exp(gp->log_wn);
     ALABI_DISPATCH_DIM(db, hipLaunchKernelGGL(grad_contract_kernel<D>, dim3(nblocks), dim3(256), 0, s, Wsrc, gp->Xt, gp->alpha,
                                               gp->N, gp->Npad, amp, gp->kf, gp->scan));

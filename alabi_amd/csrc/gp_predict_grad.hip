@@ -184,33 +184,19 @@ pgrad_final_kernel(const double* __restrict__ Xt, const double* __restrict__ alp
     }
 }
 
-static int ensure_pgrad(alabi_gp* gp, size_t bytes, hipStream_t s) {
-    if (gp->pgrad_bytes >= bytes) return ALABI_OK;
-    if (gp->pgrad) {
-        ALABI_HIP_CHECK(hipStreamSynchronize(s));
-        ALABI_HIP_CHECK(hipFree(gp->pgrad));
-        gp->pgrad = nullptr; gp->pgrad_bytes = 0;
-    }
-    ALABI_HIP_CHECK(hipMalloc(&gp->pgrad, bytes));
-    gp->pgrad_bytes = bytes;
-    return ALABI_OK;
-}
-
 int launch_predict_grad(alabi_gp* gp, const double* Xs, long long M, double* mu, double* var, double* dmu, double* dvar,
                         hipStream_t s) {
     const int Npad = gp->Npad, nb = Npad / 64, db = dim_bucket(gp->d), d = gp->d;
     if (db < 0) return ALABI_BAD_ARGUMENT;
     int st = ensure_winv(gp, s);
     if (st != ALABI_OK) return st == ALABI_NOT_COMPUTED ? ALABI_HIP_ERROR : st;   // no room for L^-1: nothing to fall back on
-    int dev = 0, n_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n_cu <= 0) n_cu = 256;
+    const int n_cu = device_cu_count();
     int parts = 1;
     while (parts < 8 && nb * parts < 2 * n_cu) parts *= 2;
     if (parts > nb) parts = nb > 0 ? nb : 1;
     // scratch: v [Npad][16] | partial [nb][16] | zpart [parts][Npad][16]
     const size_t nv = (size_t)Npad * 16, np = (size_t)nb * 16, nz = (size_t)parts * Npad * 16;
-    if ((st = ensure_pgrad(gp, (nv + np + nz) * sizeof(double), s)) != ALABI_OK) return st;
+    if ((st = grow_plain(&gp->pgrad, &gp->pgrad_bytes, (nv + np + nz) * sizeof(double), s)) != ALABI_OK) return st;
     double* v = gp->pgrad; double* partial = v + nv; double* zpart = partial + np;
     const double amp = exp(gp->log_amp);
     for (long long m0 = 0; m0 < M; m0 += 16) {
