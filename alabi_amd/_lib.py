@@ -65,6 +65,7 @@ SIGNATURES = {
     "alabi_utility_polish": (_i, [_vp, _i, _vp, _vp, _d, _i, _vp, _pd, _pi, _vp]),
     "alabi_utility_eval": (_i, [_i, _vp, _ll, _i, _pd, _d, _vp, _vp, _vp, _vp]),
     "alabi_ens_create": (_i, [_vp, _i, _i, _i, _pd, _ull, C.POINTER(_vp)]),
+    "alabi_ens_create_metropolis": (_i, [_vp, _i, _i, _i, _pd, _ull, C.POINTER(_vp)]),
     "alabi_ens_destroy": (_i, [_vp]),
     "alabi_ens_set_logp_affine": (_i, [_vp, _d, _d]),
     "alabi_ens_set_normal_prior": (_i, [_vp, _pd, _pd]),
@@ -73,6 +74,8 @@ SIGNATURES = {
     "alabi_ens_propose": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "alabi_ens_accept": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "alabi_ens_set_moves": (_i, [_vp, _i, _pi, _pd, _pd, _pd]),
+    "alabi_ens_set_move_scale": (_i, [_vp, _i, _pd, _i]),
+    "alabi_ens_mh_plan": (_i, [_vp, _pi]),
     "alabi_ens_set_stream": (_i, [_vp, _i]),
     "alabi_ens_last_path": (_i, [_vp, _pi]),
     "alabi_ens_stream_variant": (_i, [_vp, _pi]),
@@ -107,6 +110,8 @@ SIGNATURES = {
     "alabi_ens_step_with_randoms_walk": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "alabi_ens_step_with_randoms_kde": (_i, [_vp, _vp, _vp, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     "alabi_ens_kde_singular": (_i, [_vp, _pll]),
+    "alabi_ens_step_with_randoms_gauss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp]),
+    "alabi_ens_export_gauss_draws": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "alabi_ns_create": (_i, [_vp, _i, _pd, _ull, C.POINTER(_vp)]),
     "alabi_ns_destroy": (_i, [_vp]),
     "alabi_ns_set_logp": (_i, [_vp, _d, _d, _i]),

@@ -958,9 +958,15 @@ class SurrogateModel(object):
         move alone does not cross between separated modes; the usual companion of DE is ``[(DEMove(), 0.8), (SnookerMove(),
         0.2)]``.  ``alabi_amd.moves.WalkMove(s=None)`` and ``KDEMove(bw_method=None)`` (emcee's own are recognised) use the whole
         complementary half: a KDE move hops between modes in one step, ``[(KDEMove(), 0.3), (DEMove(), 0.7)]``, and wants many
-        walkers per dimension (``nwalkers >= 2 ndim + 2`` at the least; a warning below ``8 (ndim + 1)``).  Any other emcee move
-        raises ``NotImplementedError`` -- the Metropolis moves and emcee's ``DESnookerMove``, whose arithmetic is not the
-        published rule; none of ``DEMove``, ``SnookerMove``, ``WalkMove``, ``KDEMove`` can be combined with ``"shard": True``.
+        walkers per dimension (``nwalkers >= 2 ndim + 2`` at the least; a warning below ``8 (ndim + 1)``).
+        ``alabi_amd.moves.GaussianMove(cov, mode="vector", factor=None)`` is emcee's Gaussian Metropolis move -- ``cov`` a scalar, a
+        vector of variances or a matrix, e.g. the inverse Hessian at ``find_map()`` or the covariance of an earlier chain: a set of
+        Gaussian moves alone runs the walkers as independent random-walk Metropolis chains on the surrogate, any number of them,
+        all steps of a call in one kernel launch; it mixes with the red-blue moves too.  ``alabi_amd.moves.MHMove(fn)`` and any
+        object with a callable ``get_proposal`` (emcee's own ``MHMove`` / ``GaussianMove``) run a Python proposal function on a
+        host-driven loop, one round trip per step: slow by nature.  Any other emcee move raises ``NotImplementedError`` -- in
+        particular emcee's ``DESnookerMove``, whose arithmetic is not the published rule; none of ``DEMove``, ``SnookerMove``,
+        ``WalkMove``, ``KDEMove``, ``GaussianMove``, ``MHMove`` can be combined with ``"shard": True``.
 
         Several GPUs (the reference's parallel axis is a process pool handed to emcee, core.py:2300, :2322, built at :349-369;
         ``ncore`` / ``pool_method`` have no meaning here): run one process per GPU under ``torch.distributed`` (e.g.
@@ -976,6 +982,9 @@ class SurrogateModel(object):
         rank, world = adist.world_info()
         kw = dict(sampler_kwargs)
         move_set = parse_moves(kw.get("moves"), self.ndim)       # unsupported moves fail here, before anything runs
+        if kw.get("shard", False) and move_set is not None and (move_set.has_gauss or move_set.all_mh):
+            raise ValueError('sampler_kwargs={"shard": True} cannot run a GaussianMove or an MHMove: a Metropolis proposal reads no '
+                             'other walker, so there is nothing to exchange -- run replicas instead')
         if kw.get("shard", False) and move_set is not None and move_set.multi_partner:
             raise ValueError('sampler_kwargs={"shard": True} cannot run a DEMove or a SnookerMove: the sharded ensemble links one '
                              'partner row per proposal')

@@ -609,6 +609,9 @@ static void set_move_args(const alabi_ens* e, HalfArgs& h, size_t t) {
     h.mvpar = e->has_wk ? e->mv.par + 2 * t * e->E : nullptr;
     h.kde = e->kde;
     h.seed = e->seed;
+    h.mvidx = e->has_gauss ? e->mv.move + t * e->E : nullptr;
+    h.gauss_C = e->has_gauss ? e->gauss_C : nullptr;
+    h.gauss_diag = e->gauss_diag;
 }
 
 static DrawBuffers offset_draws(const DrawBuffers& b, size_t off) {
@@ -620,9 +623,9 @@ static DrawBuffers offset_draws(const DrawBuffers& b, size_t off) {
     return r;
 }
 
-int alabi_ens_create(alabi_gp* gp, int W, int d, int n_ensembles, const double* bounds, unsigned long long seed,
-                     alabi_ens** out) {
-    if (!gp || !out || !bounds || W < 2 || W > 8192 || d != gp->d || n_ensembles < 1 || n_ensembles > 4096)
+// alabi_ens_create and alabi_ens_create_metropolis: the same handle, they differ in the fewest walkers they take (min_w)
+static int ens_create(alabi_gp* gp, int W, int min_w, int d, int n_ensembles, const double* bounds, unsigned long long seed, alabi_ens** out) {
+    if (!gp || !out || !bounds || W < min_w || W > 8192 || d != gp->d || n_ensembles < 1 || n_ensembles > 4096)
         return ALABI_BAD_ARGUMENT;
     if ((long long)W * n_ensembles > (1LL << 22)) return ALABI_BAD_ARGUMENT;
     alabi_ens* e = new (std::nothrow) alabi_ens();
@@ -686,6 +689,18 @@ int alabi_ens_create(alabi_gp* gp, int W, int d, int n_ensembles, const double* 
     return ALABI_OK;
 }
 
+int alabi_ens_create(alabi_gp* gp, int W, int d, int n_ensembles, const double* bounds, unsigned long long seed,
+                     alabi_ens** out) {
+    return ens_create(gp, W, 2, d, n_ensembles, bounds, seed, out);
+}
+
+// A handle for Metropolis sets: one walker is enough.  With W < 2 every entry that would draw a red-blue record refuses a table
+// that is not all Gaussian (alabi_ens_set_moves, alabi_ens_run, alabi_ens_draw).
+int alabi_ens_create_metropolis(alabi_gp* gp, int W, int d, int n_ensembles, const double* bounds, unsigned long long seed,
+                                alabi_ens** out) {
+    return ens_create(gp, W, 1, d, n_ensembles, bounds, seed, out);
+}
+
 int alabi_ens_destroy(alabi_ens* e) {
     if (!e) return ALABI_OK;
     if (e->graph_exec) (void)hipGraphExecDestroy(e->graph_exec);
@@ -694,6 +709,7 @@ int alabi_ens_destroy(alabi_ens* e) {
     free_draws(e->draws2);
     free_move_buffers(e->mv);
     free_kde_buffers(e->kde);
+    if (e->gauss_C) (void)hipFree(e->gauss_C);
     if (e->side_stream) (void)hipStreamDestroy(e->side_stream);
     if (e->ev_free) (void)hipEventDestroy(e->ev_free);
     if (e->ev_drawn) (void)hipEventDestroy(e->ev_drawn);
@@ -747,7 +763,7 @@ int alabi_ens_set_logp_map(alabi_ens* e, int kind) {
 int alabi_ens_set_moves(alabi_ens* e, int n, const int* kind, const double* cum, const double* p0, const double* p1) {
     if (!e || n < 0 || n > ALABI_MAX_MOVES || (n > 0 && (!kind || !cum || !p0 || !p1))) return ALABI_BAD_ARGUMENT;
     MoveTable mt{};
-    bool de = false, snooker = false, walk = false, kde = false;
+    bool de = false, snooker = false, walk = false, kde = false, gauss = false, all_gauss = n > 0;
     const int nc_min = e->W / 2, nc_max = (e->W + 1) / 2;   // the two complementary halves
     double prev = 0.0;
     for (int k = 0; k < n; ++k) {
@@ -763,21 +779,30 @@ int alabi_ens_set_moves(alabi_ens* e, int n, const int* kind, const double* cum,
         } else if (kind[k] == 4) {                           // KDE: the bandwidth factors of the two splits; more rows than dimensions
             if (!(p0[k] > 0.0) || !std::isfinite(p0[k]) || !(p1[k] > 0.0) || !std::isfinite(p1[k]) || nc_min < e->d + 1) return ALABI_BAD_ARGUMENT;
             kde = true;
+        } else if (kind[k] == 5) {                           // Gaussian: p0 = ln factor >= 0 (0: none), p1 = mode 0 / 1 / 2
+            if (!(p0[k] >= 0.0) || !std::isfinite(p0[k]) || !(p1[k] == 0.0 || p1[k] == 1.0 || p1[k] == 2.0)) return ALABI_BAD_ARGUMENT;
+            // its scale factor has been handed over for this slot (alabi_ens_set_move_scale), diagonal where one coordinate moves
+            if (!((e->gauss_staged >> k) & 1) || (p1[k] != 0.0 && !((e->gauss_diag >> k) & 1))) return ALABI_BAD_ARGUMENT;
+            gauss = true;
         }
         else return ALABI_BAD_ARGUMENT;
+        if (kind[k] != 5) all_gauss = false;
         mt.kind[k] = kind[k]; mt.cum[k] = cum[k]; mt.p0[k] = p0[k]; mt.p1[k] = p1[k];
     }
     if (n > 0 && !(prev > 0.0)) return ALABI_BAD_ARGUMENT;
+    if (e->W < 2 && !all_gauss) return ALABI_BAD_ARGUMENT;   // a red-blue move needs a complementary half
     if (de && e->W < 4) return ALABI_BAD_ARGUMENT;       // two distinct partners in a complementary list of W / 2 walkers
     if (snooker && e->W < 6) return ALABI_BAD_ARGUMENT;  // three distinct partners
-    if (n > 0) { const int st = ensure_move_buffers(e, snooker || walk || kde, walk || kde); if (st != ALABI_OK) return st; }
+    if (n > 0) { const int st = ensure_move_buffers(e, snooker || walk || kde || gauss, walk || kde || gauss); if (st != ALABI_OK) return st; }
     if (kde) { const int st = ensure_kde_buffers(e); if (st != ALABI_OK) return st; }
     mt.n = n;
     e->moves = mt;
-    e->has_de = de || snooker || walk || kde;            // more than one partner row: one launch per half step
+    e->has_de = de || snooker || walk || kde || gauss;   // more than one partner row, or none: one launch per half step
     e->has_snooker = snooker;
-    e->has_wk = walk || kde;                             // the whole complementary half: the whole-half instantiations
+    e->has_wk = walk || kde || gauss;                    // proposals formed where they are used: the whole-half instantiations
     e->has_kde = kde;
+    e->has_gauss = gauss; e->all_gauss = gauss && all_gauss;
+    e->gauss_staged = 0;                                 // scale factors belong to the table they were handed over for
     e->drawn_n = 0;                                      // records drawn under the old move set are not the new set's
     e->ahead_valid = false;                              // nor are those made ahead for the next stream call
     e->moves_gen++;
@@ -786,10 +811,43 @@ int alabi_ens_set_moves(alabi_ens* e, int n, const int* kind, const double* cum,
     return ALABI_OK;
 }
 
+int alabi_ens_set_move_scale(alabi_ens* e, int k, const double* C, int diagonal) {
+    if (!e || !C || k < 0 || k >= ALABI_MAX_MOVES) return ALABI_BAD_ARGUMENT;
+    const int d = e->d;
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j < d; ++j) {
+            const double v = C[(size_t)i * d + j];
+            if (!std::isfinite(v) || (j > i && v != 0.0) || (diagonal && j != i && v != 0.0) || (j == i && !(v > 0.0))) return ALABI_BAD_ARGUMENT;
+        }
+    // slot k of the current table is in use by a Gaussian move that moves one coordinate per step: a diagonal factor, as in emcee
+    if (k < e->moves.n && e->moves.kind[k] == 5 && e->moves.p1[k] != 0.0 && !diagonal) return ALABI_BAD_ARGUMENT;
+    if (!e->gauss_C) {
+        hipError_t err = hipMalloc(&e->gauss_C, (size_t)ALABI_MAX_MOVES * ALABI_MAX_DIM * ALABI_MAX_DIM * sizeof(double));
+        if (err != hipSuccess) { e->gauss_C = nullptr; return hip_fail(err, "hipMalloc(move scale factors)", __FILE__, __LINE__); }
+    }
+    ALABI_HIP_CHECK(hipDeviceSynchronize());               // nothing in flight reads the old factor
+    ALABI_HIP_CHECK(hipMemcpy(e->gauss_C + (size_t)k * d * d, C, (size_t)d * d * sizeof(double), hipMemcpyHostToDevice));
+    e->gauss_staged |= 1 << k;
+    if (diagonal) e->gauss_diag |= 1 << k; else e->gauss_diag &= ~(1 << k);
+    e->settings_gen++;
+    if (e->graph_exec) { (void)hipGraphExecDestroy(e->graph_exec); e->graph_exec = nullptr; }   // captured launches carry gauss_diag
+    return ALABI_OK;
+}
+
+int alabi_ens_mh_plan(alabi_ens* e, int* out) {
+    if (!e || !out) return ALABI_BAD_ARGUMENT;
+    for (int i = 0; i < 4; ++i) out[i] = e->mh_plan[i];
+    return ALABI_OK;
+}
+
 int alabi_ens_set_stream(alabi_ens* e, int enabled) {
     if (!e) return ALABI_BAD_ARGUMENT;
-    if (enabled && !(e->hist && e->err)) return ALABI_BAD_ARGUMENT;
-    e->stream_ok = enabled ? 1 : 0;
+    // The switch belongs to the handle, not to the move table: it covers the persistent kernels of a red-blue table (they need
+    // the version history) and ens_mh_kernel of an all-Gaussian one (it needs nothing), whichever table the next run finds.
+    const bool can_stream = e->hist && e->err;
+    if (enabled && !can_stream && !e->all_gauss) return ALABI_BAD_ARGUMENT;
+    e->mh_ok = enabled ? 1 : 0;
+    e->stream_ok = (enabled && can_stream) ? 1 : 0;
     e->settings_gen++;
     return ALABI_OK;
 }
@@ -1011,6 +1069,22 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
     hipStream_t s = as_stream(stream);
     int st;
     if ((st = sync_consts(e, s)) != ALABI_OK) return st;
+    if (e->W < 2 && !e->all_gauss) return ALABI_BAD_ARGUMENT;         // a red-blue move needs a complementary half
+    // An all-Gaussian set: W independent chains, one workgroup per walker, every step of a chunk in one launch (ens_mh_kernel).
+    // The step counters travel by value; nothing is read back.
+    if (e->all_gauss && e->mh_ok) {
+        const int chunk = ens_mh_chunk(e);
+        if (chunk > 0) {
+            e->last_path = 4;
+            e->last_state_ok = false;
+            for (long long done = 0; done < nsteps; done += chunk) {
+                const int K = (int)(nsteps - done < chunk ? nsteps - done : chunk);
+                if ((st = launch_ens_mh(e, coords, logp, step0, done, K, thin_by, chain, chain_logp, n_accept, s)) != ALABI_OK) return st;
+            }
+            e->mh_plan[1] = chunk;
+            return ALABI_OK;
+        }
+    }
     // Persistent dataflow path: training set pinned in registers (Npad <= 2048: 256 compute lanes x up to 4 point pairs), one
     // workgroup per list position.  It synchronises at the end to read the time-out flag.
     e->last_path = 0;
@@ -1178,6 +1252,7 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
 
 int alabi_ens_draw(alabi_ens* e, long long step0, int nsteps, double a, void* stream) {
     if (!e || nsteps <= 0 || nsteps > e->chunk_cap || !(a > 1.0)) return ALABI_BAD_ARGUMENT;
+    if (e->W < 2 && !e->all_gauss) return ALABI_BAD_ARGUMENT;         // a red-blue record names a walker of the other half
     hipStream_t s = as_stream(stream);
     int st;
     if ((st = set_run_state(e, step0, 0, s)) != ALABI_OK) return st;
@@ -1356,6 +1431,37 @@ int alabi_ens_step_with_randoms_kde(alabi_ens* e, double* coords, double* logp, 
     if (!e->gp->computed || !e->gp->has_alpha) return ALABI_NOT_COMPUTED;
     WkInject inj{r, z, lnfac_out};
     return step_injected_wk(e, coords, logp, order, n0, 4, factor, factor, inj, u_acc, n_accept, as_stream(stream));
+}
+
+int alabi_ens_step_with_randoms_gauss(alabi_ens* e, double* coords, double* logp, const int* order, int n0, int k_move, double f,
+                                      const int* coord, const double* z, const double* u_acc, long long* n_accept, void* stream) {
+    if (!e || !coords || !logp || !order || !coord || !z || !u_acc || n0 < 0 || n0 > e->W || e->E != 1) return ALABI_BAD_ARGUMENT;
+    if (k_move < 0 || k_move >= e->moves.n || e->moves.kind[k_move] != 5 || !std::isfinite(f))
+        return ALABI_BAD_ARGUMENT;
+    if (!e->gp->computed || !e->gp->has_alpha) return ALABI_NOT_COMPUTED;
+    hipStream_t s = as_stream(stream);
+    int st;
+    if ((st = sync_consts(e, s)) != ALABI_OK) return st;
+    if ((st = ensure_move_buffers(e, true, true)) != ALABI_OK) return st;
+    if ((st = launch_ens_prep_wk(e, order, u_acc, s)) != ALABI_OK) return st;
+    if ((st = launch_ens_set_step_move(e, 5, e->moves.p0[k_move], e->moves.p1[k_move], s)) != ALABI_OK) return st;
+    e->drawn_n = 0;  // row 0 of the draw buffers now holds caller data
+    HalfArgs h = base_args(e, coords, logp);
+    h.rec = e->draws; h.cw2 = e->mv.cw2; h.cw3 = e->mv.cw3; h.mvkind = e->mv.kind; h.mvpar = e->mv.par; h.kde = e->kde; h.seed = e->seed;
+    h.inj = WkInject{coord, z, nullptr};
+    h.gauss_C = e->gauss_C; h.gauss_diag = e->gauss_diag; h.gauss_k = k_move; h.gauss_f = f;
+    h.n0 = n0; h.n_accept = n_accept; h.local_t = 0; h.part_begin = 0;
+    for (int split = 0; split < 2; ++split) {
+        const int nS = split == 0 ? n0 : e->W - n0;
+        h.split = split;
+        if ((st = launch_ens_half_args(e, h, nS, s)) != ALABI_OK) return st;
+    }
+    return ALABI_OK;
+}
+
+int alabi_ens_export_gauss_draws(alabi_ens* e, double* f, int* coord, double* z, void* stream) {
+    if (!e || !f || !coord || !z || e->drawn_n < 1 || !e->mv.kind) return ALABI_BAD_ARGUMENT;
+    return launch_ens_gauss_export(e, f, coord, z, as_stream(stream));
 }
 
 int alabi_ens_kde_singular(alabi_ens* e, long long* count) {

@@ -139,6 +139,8 @@ struct DrawBuffers {
 //   kind 2 SnookerMove: p0 = gammas (the fixed step along the line), p1 = 0.
 //   kind 3 WalkMove: p0 = s0, the size of the subset of the complementary half (0: all of it), p1 = 0.
 //   kind 4 KDEMove: p0 / p1 = the bandwidth factor f of split 0 / split 1 (the two halves of an odd W differ in size).
+//   kind 5 GaussianMove: p0 = ln factor (0: no scale factor), p1 = mode (0 vector, 1 random, 2 sequential); the scale factor C of
+//   the proposal q = x + f C z travels apart from the table, ahead of it (alabi_ens_set_move_scale).
 // n = 0 stands for the default, one stretch move with the `a` of the call.
 #define ALABI_MAX_MOVES 8
 struct MoveTable {
@@ -268,6 +270,15 @@ struct alabi_ens {
     bool has_wk = false, has_kde = false;   // a walk or KDE move (the whole-half instantiations run); a KDE move (the pre-pass is launched)
     alabi::MoveBuffers mv{};
     alabi::KdeBuffers kde{};
+    // Gaussian Metropolis moves (kind 5): the scale factors [ALABI_MAX_MOVES][d, d] on the device, one slot per move of the table;
+    // gauss_staged: the slots alabi_ens_set_move_scale has filled since the last alabi_ens_set_moves, which accepts a Gaussian move
+    // only on such a slot; gauss_diag: the slots whose factor is diagonal; all_gauss: every move of the table is a Gaussian move,
+    // the set ens_mh_kernel runs (mh_ok: not turned off by alabi_ens_set_stream)
+    double* gauss_C = nullptr;
+    int gauss_staged = 0, gauss_diag = 0;
+    bool has_gauss = false, all_gauss = false;
+    int mh_ok = 1;
+    int mh_plan[4] = {0};     // last ens_mh_kernel launch: threads, steps per launch, LDS bytes, tiled (alabi_ens_mh_plan)
 };
 
 namespace alabi {
@@ -370,10 +381,18 @@ struct HalfArgs {
     KdeBuffers kde{};
     WkInject inj{};
     unsigned long long seed = 0;
+    // Gaussian steps (kind 5): the index of the step's move (MoveBuffers::move offset to the step) and the moves' scale factors
+    // [ALABI_MAX_MOVES][d, d] with bit k of gauss_diag set where factor k is diagonal.  Test entry: gauss_k >= 0 names the move,
+    // gauss_f is the step's scale factor, inj.idx [W] the coordinate (-1: all), inj.z [W, d] the normals.
+    const int* mvidx = nullptr;
+    const double* gauss_C = nullptr;
+    int gauss_diag = 0, gauss_k = -1;
+    double gauss_f = 1.0;
 };
 int launch_ens_kde_prepass(alabi_ens* e, const HalfArgs& args, hipStream_t s);
 int launch_ens_prep_wk(alabi_ens* e, const int* order, const double* u_acc, hipStream_t s);
 int launch_ens_set_step_move(alabi_ens* e, int kind, double p0, double p1, hipStream_t s);
+int launch_ens_gauss_export(alabi_ens* e, double* f, int* coord, double* z, hipStream_t s);   // the Gaussian draws of drawn step 0
 int launch_ens_draw(alabi_ens* e, int nsteps, double a, hipStream_t s);
 int launch_ens_draw_at(alabi_ens* e, const DrawBuffers& into, int nsteps, double a, bool from_state, long long step0, hipStream_t s);   // first step: run_state[0], or step0 by value
 int launch_ens_prep(alabi_ens* e, const int* order, int n0, const double* u_z, const int* partner,
@@ -383,6 +402,10 @@ int launch_ens_prep_de(alabi_ens* e, const int* order, int n0, const int* j1, co
 int launch_ens_prep_snooker(alabi_ens* e, const int* order, int n0, const int* j1, const int* j2, const int* j3, double gamma,
                             const double* u_acc, hipStream_t s);
 int launch_ens_half_args(alabi_ens* e, const HalfArgs& args, int nblocks, hipStream_t s);
+// ens_mh.hip: all steps of a chunk of an all-Gaussian set in one launch, one workgroup per walker
+int launch_ens_mh(alabi_ens* e, double* coords, double* logp, long long step0, long long done0, int K, int thin_by, double* chain,
+                  double* chain_logp, long long* n_accept, hipStream_t s);
+int ens_mh_chunk(const alabi_ens* e);    // steps per launch (0: the set does not run on ens_mh_kernel)
 int launch_ens_lnprob(alabi_ens* e, const double* coords, int nwalkers, double* logp, int gate_box, hipStream_t s);
 int launch_ens_propose(alabi_ens* e, const HalfArgs& args, int nblocks, int gate_box, double* q, double* like, hipStream_t s);
 int launch_ens_accept(alabi_ens* e, const HalfArgs& args, int count, const double* q, const double* lp_new, hipStream_t s);

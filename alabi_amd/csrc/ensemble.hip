@@ -206,7 +206,7 @@ ens_draw_kernel(unsigned long long seed, const long long* __restrict__ run_state
         const double uz = u53(r[0], r[1]);
         const uint64_t nc = li ? (uint64_t)n0 : (uint64_t)(W - n0);
         const int pr = (int)(((uint64_t)r[2] * nc) >> 32);
-        const int cw = olist[(li ? 0 : n0) + pr];
+        const int cw = nc ? olist[(li ? 0 : n0) + pr] : i;   // one walker (a Metropolis set): no complementary half, the record names itself
         const uint32_t r3 = r[3];
         philox4x32_10(s_lo, s_hi, g0 + (uint32_t)i, 2u, k0, k1, r);
         const double ua = u53(r[0], r[1]);
@@ -342,8 +342,6 @@ __global__ void ens_set_step_move_kernel(MoveBuffers mv, int kind, double p0, do
     if (threadIdx.x == 0 && blockIdx.x == 0) { mv.kind[0] = kind; mv.par[0] = p0; mv.par[1] = p1; }
 }
 
-// Normal-prior term of coordinate `lane` (< d) of a proposal, summed over the wave: lanes >= d contribute 0.
-// consts rows 3 / 4: prior mean, 1 / std (0 where there is no normal prior).  Result valid in every lane.
 // h and the centred inputs of the squared-exponential half-step kernels (alabi_gp::Xc, ::ens_h)
 __global__ void __launch_bounds__(256)
 ens_se_prepare_kernel(const double* __restrict__ Xt, const double* __restrict__ centre, const double* __restrict__ alpha, int N, int Npad,
@@ -370,10 +368,23 @@ ens_se_prepare_kernel(const double* __restrict__ Xt, const double* __restrict__ 
     h[n] = out;
 }
 
-__device__ inline double normal_prior_sum(const double* pmean, const double* pistd, int lane, int d, double x) {
-    double t = 0.0;
-    if (lane < d) { t = (x - pmean[lane]) * pistd[lane]; t = -0.5 * t * t; }
-    return lane_bcast(wave_sum_dpp(t), 63);
+// The Gaussian move's draws of drawn step 0 (alabi_ens_export_gauss_draws): f per ensemble, the coordinate and the d normals per
+// walker, from the kind and parameters the draw kernel left for the step (f = 1, coordinate -1 where its move is another).
+__global__ void __launch_bounds__(256)
+ens_gauss_export_kernel(unsigned long long seed, const long long* __restrict__ run_state, int W, int E, int d, MoveBuffers mv,
+                        double* __restrict__ f_out, int* __restrict__ coord_out, double* __restrict__ z_out) {
+    const int gid = blockIdx.x * 256 + threadIdx.x;
+    if (gid >= W * E) return;
+    const int e = gid / W;
+    const long long step = run_state[0];
+    const uint32_t s_lo = (uint32_t)step, s_hi = (uint32_t)((unsigned long long)step >> 32);
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    double f = 1.0;
+    int c = -1;
+    if (mv.kind[e] == 5) gauss_step_draws(s_lo, s_hi, (uint32_t)(e * W), (uint32_t)gid, k0, k1, step, mv.par[2 * e], (int)mv.par[2 * e + 1], d, f, c);
+    if (gid == e * W) f_out[e] = f;
+    coord_out[gid] = c;
+    for (int k = 0; k < d; ++k) z_out[(size_t)gid * d + k] = philox_normal(s_lo, s_hi, (uint32_t)gid, 10u + 16u * (uint32_t)k, k0, k1);
 }
 
 // The proposal of a record from the rows it names, in NumPy's operation order (the library is built without contraction):
@@ -423,16 +434,9 @@ __device__ __forceinline__ double snooker_coord(int d, double sv, double zv, dou
 //                       subset J iff the rank of its key among the Nc keys (ties by j) is < s0 -- no key is drawn when s0 = Nc;
 //   S = 7, b = j:       z_j, the normal of row j (Box-Muller as stream 4: sqrt(-2 ln(1 - u53(r0, r1))) cos(2 pi u53(r2, r3)));
 //   S = 8, b = 0:       r = (r0 Nc) >> 32, the KDE move's row;  b = 1 + k: the normal z_k of coordinate k.
-// Streams 0-5 are S + 16 b with b = 0 and S < 6: nothing here meets them.
+// Streams 0-5 are S + 16 b with b = 0 and S < 6: nothing here meets them.  S = 9 and 10 belong to the Gaussian move (ens_device.hpp).
 #define ALABI_WK_MAX_NC 2048     // rows of a complementary half the walk move's lists hold in LDS
 #define ALABI_WK_TILE 2048       // doubles of the tile through which its rows are read
-
-__device__ inline double philox_normal(uint32_t s_lo, uint32_t s_hi, uint32_t gid, uint32_t word, uint32_t k0, uint32_t k1) {
-    uint32_t r[4];
-    philox4x32_10(s_lo, s_hi, gid, word, k0, k1, r);
-    const double u1 = u53(r[0], r[1]), u2 = u53(r[2], r[3]);
-    return sqrt(-2.0 * log(1.0 - u1)) * cos(6.283185307179586 * u2);
-}
 
 // log(exp(m1) s1 + exp(m2) s2) as (max, scaled sum): the running-maximum form of kde.hip
 __device__ inline void lse_merge(double& m, double& s, double m2, double s2) {
@@ -458,6 +462,26 @@ __device__ __forceinline__ int wk_proposal(const HalfArgs& p, int kind, int e, i
     const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
     const bool in = tid < d;
     qc = 0.0; lnfac = 0.0; reject = 0;
+    if (kind == 5) {
+        // Gaussian Metropolis move (ens_device.hpp: gauss_step_draws, gauss_coord): reads nothing but the walker itself
+        double* Cs = reinterpret_cast<double*>(wk_lds);                        // [d, d] (32 KB at d = 64)
+        const int mi = p.gauss_k >= 0 ? p.gauss_k : p.mvidx[e];
+        if (!p.gauss_C || (unsigned)mi >= (unsigned)ALABI_MAX_MOVES) return 0;  // checked where the moves are set
+        const int diagonal = (p.gauss_diag >> mi) & 1;
+        double f;
+        int c;
+        if (p.inj.z) { f = p.gauss_f; c = p.inj.idx[w]; }
+        else gauss_step_draws(s_lo, s_hi, (uint32_t)(e * p.W), (uint32_t)w, k0, k1, step, p.mvpar[2 * e], (int)p.mvpar[2 * e + 1], d, f, c);
+        if (c < -1 || c >= d) return 0;                                        // a test entry's coordinate out of range; workgroup-uniform
+        for (int idx = tid; idx < d * d; idx += T) Cs[idx] = p.gauss_C[(size_t)mi * d * d + idx];
+        __syncthreads();
+        if (tid < 64) {
+            double z = 0.0;
+            if (in) z = p.inj.z ? p.inj.z[(size_t)w * d + tid] : philox_normal(s_lo, s_hi, (uint32_t)w, 10u + 16u * (uint32_t)tid, k0, k1);
+            qc = gauss_coord(Cs, diagonal, d, tid, sv, z, f, c);
+        }
+        return 1;
+    }
     if (kind == 3) {
         uint64_t* keys = reinterpret_cast<uint64_t*>(wk_lds);                  // [Nc]; after the ranks: zl
         double* zl = reinterpret_cast<double*>(wk_lds);                        // [s0] normals in sum order
@@ -807,43 +831,7 @@ __device__ __forceinline__ void ens_half_body(const HalfArgs& p) {
         double q[D];
 #pragma unroll
         for (int k = 0; k < D; ++k) q[k] = qs_s[k];
-        double acc;
-        if (!GENERIC) {
-            const double nhq = se_neg_half_norm<D>(q);
-            double fa, fb;
-            se_pair_terms<D>(xa, aa, q, nhq, fa, fb);
-            acc = 0.0; acc += fa; acc += fb;
-            for (int j = tid + T; j < half; j += T) {
-                f64x2 x[D];
-#pragma unroll
-                for (int k = 0; k < D; ++k) x[k] = reinterpret_cast<const f64x2*>(Xsrc + (size_t)k * p.Npad)[j];
-                se_pair_terms<D>(x, reinterpret_cast<const f64x2*>(Asrc)[j], q, nhq, fa, fb);
-                acc += fa; acc += fb;
-            }
-        } else {
-            double r2a = 0.0, r2b = 0.0;
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-                const double da = xa[k].x - q[k], db = xa[k].y - q[k];
-                r2a = fma(da, da, r2a);
-                r2b = fma(db, db, r2b);
-            }
-            acc = aa.x * radial<GENERIC>(r2a, p.kf);
-            acc = fma(aa.y, radial<GENERIC>(r2b, p.kf), acc);
-            for (int j = tid + T; j < half; j += T) {
-                double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                    const f64x2 x = reinterpret_cast<const f64x2*>(p.Xt + (size_t)k * p.Npad)[j];
-                    const double d0 = x.x - q[k], d1 = x.y - q[k];
-                    s0 = fma(d0, d0, s0);
-                    s1 = fma(d1, d1, s1);
-                }
-                const f64x2 al = reinterpret_cast<const f64x2*>(p.alpha)[j];
-                acc = fma(al.x, radial<GENERIC>(s0, p.kf), acc);
-                acc = fma(al.y, radial<GENERIC>(s1, p.kf), acc);
-            }
-        }
+        const double acc = half_lane_sum<D, GENERIC>(xa, aa, q, Xsrc, Asrc, p.Npad, tid, T, p.kf);
         // (3) wave totals by DPP, one LDS word per wave, ONE barrier; only wave 0 goes on
         const double wsum = wave_sum_dpp(acc);
         if ((tid & 63) == 63) scratch[tid >> 6] = wsum;
@@ -1273,6 +1261,13 @@ int launch_ens_prep_wk(alabi_ens* e, const int* order, const double* u_acc, hipS
 
 int launch_ens_set_step_move(alabi_ens* e, int kind, double p0, double p1, hipStream_t s) {
     hipLaunchKernelGGL(ens_set_step_move_kernel, dim3(1), dim3(64), 0, s, e->mv, kind, p0, p1);
+    ALABI_LAUNCH_CHECK();
+    return ALABI_OK;
+}
+
+int launch_ens_gauss_export(alabi_ens* e, double* f, int* coord, double* z, hipStream_t s) {
+    hipLaunchKernelGGL(ens_gauss_export_kernel, dim3((e->W * e->E + 255) / 256), dim3(256), 0, s, e->seed, e->run_state, e->W, e->E, e->d,
+                       e->mv, f, coord, z);
     ALABI_LAUNCH_CHECK();
     return ALABI_OK;
 }

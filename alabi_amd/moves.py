@@ -1,8 +1,8 @@
 """Proposal moves of the ensemble sampler: emcee's ``EnsembleSampler(moves=...)``.
 
 The reference documents ``sampler_kwargs['moves']`` ("Custom proposal moves", alabi/core.py:2144) and hands it to
-``emcee.EnsembleSampler`` (alabi/core.py:2319).  Five moves run on the GPU here -- emcee's whole red-blue family --, alone or as a
-weighted mixture from which ONE move is chosen per step, as emcee does:
+``emcee.EnsembleSampler`` (alabi/core.py:2319).  Six moves run on the GPU here -- emcee's whole red-blue family and its Gaussian
+Metropolis move --, alone or as a weighted mixture from which ONE move is chosen per step, as emcee does:
 
 * ``StretchMove(a=2.0)``        -- emcee 3 ``moves/stretch.py`` (the default);
 * ``DEMove(sigma, gamma0)``     -- emcee 3 ``moves/de.py``: q = s + gamma (C[j2] - C[j1]) with two distinct walkers of the
@@ -21,23 +21,38 @@ weighted mixture from which ONE move is chosen per step, as emcee does:
   set without a Cholesky factor (emcee raises ``LinAlgError``) rejects that half step's proposals and is counted in
   ``EnsembleSampler.kde_singular_half_steps``.
 
-The subset of a walk move, the KDE move's row and all normals are counter-based Philox draws (streams 6-8 of the library), not
+* ``GaussianMove(cov, mode="vector", factor=None)`` -- emcee 3 ``moves/gaussian.py``: a Metropolis proposal q = x + f C z around the
+  walker itself, C C^T = cov (a scalar, a vector of variances or a full matrix, factorised on the host), z standard normal; mode
+  "vector" moves every coordinate, "random" one coordinate drawn per walker and step, "sequential" coordinate (step mod ndim);
+  with ``factor`` the scale f = exp(v), v ~ U(-ln factor, ln factor), is drawn once per step and ensemble; log factor 0.  A
+  proposal reads no other walker, so a set of Gaussian moves alone is ``nwalkers`` independent Metropolis chains: it runs with ANY
+  number of walkers, one workgroup per walker and all steps of a call in one launch (``ens_mh_kernel``).  Mixed with red-blue moves
+  it runs with one launch per half step, the same rule applied to each half in turn.
+
+``MHMove(proposal_function, ndim=None)`` is emcee's generic Metropolis move: ``proposal_function(coords[W, d], rng) -> (q[W, d],
+log_factors[W])`` is a Python callable, so it runs on a host-driven step loop (one round trip per step: slow by nature), the
+log-probability still on the device.  A set that holds an ``MHMove`` consists of ``MHMove`` objects only.
+
+The subset of a walk move, the KDE move's row and all normals are counter-based Philox draws (streams 6-10 of the library), not
 emcee's ``RandomState``.  ``parse_moves`` is pure host code (no GPU, no library): it accepts what emcee accepts -- None, one move, a list of moves, a
 list of (move, weight) pairs -- and recognises this module's classes as well as foreign ``StretchMove`` / ``DEMove`` objects by
 class name and attributes (``WalkMove`` with ``s``, ``KDEMove`` with ``bw_method`` too), so real ``emcee.moves`` objects of these
-classes work where emcee is installed.  Every other move raises ``NotImplementedError``: the Metropolis moves (``MHMove``,
-``GaussianMove``), which do not split the ensemble, and emcee's ``DESnookerMove``, which stands for different arithmetic (half the
-published log factor, a four-way split): ask for ``SnookerMove`` instead.
+classes work where emcee is installed.  A foreign object with the attributes ``cov``, ``mode`` and ``factor`` is taken as a
+``GaussianMove``; one of any class name with a callable ``get_proposal`` -- where emcee's ``MHMove`` and its ``GaussianMove``
+subclass keep their proposal function -- as an ``MHMove``, on the host loop.  Every other move raises ``NotImplementedError``, in
+particular emcee's ``DESnookerMove``, which stands for different arithmetic (half the published log factor, a four-way split):
+ask for ``SnookerMove`` instead.
 """
 from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["StretchMove", "DEMove", "SnookerMove", "WalkMove", "KDEMove", "MoveSet", "parse_moves", "MAX_MOVES", "KIND_STRETCH",
-           "KIND_DE", "KIND_SNOOKER", "KIND_WALK", "KIND_KDE", "WALK_MAX_NC"]
+__all__ = ["StretchMove", "DEMove", "SnookerMove", "WalkMove", "KDEMove", "GaussianMove", "MHMove", "MoveSet", "parse_moves",
+           "MAX_MOVES", "KIND_STRETCH", "KIND_DE", "KIND_SNOOKER", "KIND_WALK", "KIND_KDE", "KIND_GAUSS", "WALK_MAX_NC"]
 
 MAX_MOVES = 8                    # ALABI_MAX_MOVES of the library: the table travels in the draw kernel's arguments
-KIND_STRETCH, KIND_DE, KIND_SNOOKER, KIND_WALK, KIND_KDE = 0, 1, 2, 3, 4
+KIND_STRETCH, KIND_DE, KIND_SNOOKER, KIND_WALK, KIND_KDE, KIND_GAUSS = 0, 1, 2, 3, 4, 5
+GAUSS_MODES = {"vector": 0, "random": 1, "sequential": 2}
 WALK_MAX_NC = 2048               # rows of a complementary half the walk move's kernel lists hold
 
 
@@ -123,9 +138,83 @@ class KDEMove:
         return f"KDEMove(bw_method={self.bw_method!r})"
 
 
+class GaussianMove:
+    """Gaussian Metropolis move (emcee.moves.GaussianMove): q = x + f C z with C C^T = ``cov``.  ``cov``: a positive scalar
+    (isotropic), a vector of ``ndim`` positive variances (diagonal) or a positive definite ``ndim`` x ``ndim`` matrix (factorised
+    here by ``numpy.linalg.cholesky``).  ``mode``: "vector" (every coordinate), "random" (one coordinate per walker and step) or
+    "sequential" (coordinate step mod ndim); a full matrix allows "vector" only.  ``factor``: None or a number > 1 -- the scale
+    is then multiplied by exp(v), v ~ U(-ln factor, ln factor), one draw per step and ensemble."""
+
+    def __init__(self, cov, mode="vector", factor=None):
+        if mode not in GAUSS_MODES:
+            raise ValueError("GaussianMove: mode must be 'vector', 'random' or 'sequential'")
+        self.mode = mode
+        if factor is not None:
+            factor = float(factor)
+            if not (np.isfinite(factor) and factor > 1.0):
+                raise ValueError("GaussianMove: factor must be None or a finite number > 1")
+        self.factor = factor
+        try:
+            c = np.array(cov, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("Invalid proposal scale dimensions") from None
+        if c.ndim > 2 or (c.ndim == 2 and c.shape[0] != c.shape[1]) or c.size == 0:
+            raise ValueError("Invalid proposal scale dimensions")
+        if not np.all(np.isfinite(c)):
+            raise ValueError("GaussianMove: cov must be finite")
+        self.cov = c
+        self.form = ("scalar", "vector", "matrix")[c.ndim]
+        if c.ndim < 2:
+            if np.any(c <= 0.0):
+                raise ValueError("GaussianMove: a scalar or diagonal cov must be positive")
+            self._scale = np.sqrt(c)               # scalar, or [ndim]
+        else:
+            if mode != "vector":
+                raise ValueError("GaussianMove: a full covariance matrix allows mode='vector' only")
+            try:
+                self._scale = np.linalg.cholesky(c)
+            except np.linalg.LinAlgError:
+                raise ValueError("GaussianMove: the covariance matrix is not positive definite") from None
+        self.ndim = None if c.ndim == 0 else int(c.shape[0])
+
+    @property
+    def diagonal(self):
+        return self.form != "matrix"
+
+    def scale_matrix(self, ndim):
+        """The lower-triangular scale factor C [ndim, ndim] (row-major, zeros above the diagonal) the library takes."""
+        if self.ndim is not None and self.ndim != int(ndim):
+            raise ValueError("Dimension mismatch in proposal")
+        if self.form == "matrix":
+            return np.ascontiguousarray(np.tril(self._scale))
+        return np.ascontiguousarray(np.diag(np.broadcast_to(self._scale, (int(ndim),)).astype(np.float64)))
+
+    def __repr__(self):
+        return f"GaussianMove(cov=<{self.form}>, mode={self.mode!r}, factor={self.factor})"
+
+
+class MHMove:
+    """Generic Metropolis move (emcee.moves.MHMove): ``proposal_function(coords[W, d], rng) -> (q[W, d], log_factors[W])`` with
+    ``rng`` a ``numpy.random.RandomState``.  A Python callable cannot run on the device: the sampler drives such a set from the
+    host, one round trip per step (slow by nature), and evaluates the log-probability on the device."""
+
+    def __init__(self, proposal_function, ndim=None):
+        if not callable(proposal_function):
+            raise ValueError("MHMove needs a callable proposal_function(coords, rng) -> (q, log_factors)")
+        self.get_proposal = proposal_function
+        self.ndim = None if ndim is None else int(ndim)
+
+    def __repr__(self):
+        return f"MHMove({getattr(self.get_proposal, '__name__', 'proposal_function')}, ndim={self.ndim})"
+
+
 def _table_row(m, ndim, nc=None):
     """(kind, p0, p1) of a move in the library's table.  ``nc`` = (|C| of split 0, |C| of split 1): a KDE move's two factors need
     it and are NaN without."""
+    if isinstance(m, GaussianMove):
+        return KIND_GAUSS, 0.0 if m.factor is None else float(np.log(m.factor)), float(GAUSS_MODES[m.mode])
+    if isinstance(m, MHMove):
+        return -1, 0.0, 0.0                        # not a row of the library's table: the host loop runs it
     if isinstance(m, WalkMove):
         return KIND_WALK, 0.0 if m.s is None else float(m.s), 0.0
     if isinstance(m, KDEMove):
@@ -142,7 +231,8 @@ def _table_row(m, ndim, nc=None):
 class MoveSet:
     """A parsed move set: ``moves`` (this module's objects), normalised ``weights`` and the table the library takes --
     ``kind``, ``cum`` = np.cumsum(w / w.sum()), ``p0`` (a | gamma0 with its default resolved | gammas | s, 0 for all | KDE factor of
-    split 0), ``p1`` (0 | sigma | 0 | 0 | KDE factor of split 1).  The KDE factors depend on the number of walkers: they are NaN
+    split 0 | ln factor, 0 for None), ``p1`` (0 | sigma | 0 | 0 | KDE factor of split 1 | mode 0 / 1 / 2).  A Gaussian move's scale
+    factor travels apart: ``scales()``.  The KDE factors depend on the number of walkers: they are NaN
     until ``resolve(nwalkers)`` (called by EnsembleSampler, or pass ``nwalkers`` here)."""
 
     def __init__(self, moves, weights, ndim, nwalkers=None):
@@ -186,6 +276,24 @@ class MoveSet:
         self._fill(nc)
         return self
 
+    def scales(self):
+        """[(k, C [ndim, ndim], diagonal)] for the Gaussian moves of the table (alabi_ens_set_move_scale, ahead of alabi_ens_set_moves)."""
+        return [(k, m.scale_matrix(self.ndim), m.diagonal) for k, m in enumerate(self.moves) if isinstance(m, GaussianMove)]
+
+    @property
+    def has_gauss(self):
+        return bool(np.any(self.kind == KIND_GAUSS))
+
+    @property
+    def all_metropolis(self):
+        """Every member is a GaussianMove: the walkers are independent Metropolis chains (ens_mh_kernel)."""
+        return bool(len(self.moves) > 0 and np.all(self.kind == KIND_GAUSS))
+
+    @property
+    def all_mh(self):
+        """Every member is an MHMove: the host-driven step loop."""
+        return bool(len(self.moves) > 0 and all(isinstance(m, MHMove) for m in self.moves))
+
     @property
     def has_de(self):
         return bool(np.any(self.kind == KIND_DE))
@@ -214,9 +322,13 @@ class MoveSet:
 
 def _as_move(obj):
     """This module's move for ``obj``: one of its own, or a foreign object recognised by class name and attributes."""
-    if isinstance(obj, (StretchMove, DEMove, SnookerMove, WalkMove, KDEMove)):
+    if isinstance(obj, (StretchMove, DEMove, SnookerMove, WalkMove, KDEMove, GaussianMove, MHMove)):
         return obj
     name = type(obj).__name__
+    if name == "GaussianMove" and all(hasattr(obj, a) for a in ("cov", "mode", "factor")):
+        return GaussianMove(obj.cov, mode=obj.mode, factor=obj.factor)
+    if callable(getattr(obj, "get_proposal", None)):
+        return MHMove(obj.get_proposal, ndim=getattr(obj, "ndim", None))
     if name == "WalkMove" and hasattr(obj, "s"):
         return WalkMove(s=obj.s)
     if name == "KDEMove" and hasattr(obj, "bw_method"):
@@ -229,6 +341,9 @@ def _as_move(obj):
     if name == "DESnookerMove":
         hint = ("; emcee's DESnookerMove stands for different arithmetic (half the published log factor, a four-way split) -- "
                 "use alabi_amd.moves.SnookerMove, the published snooker update")
+    if name in ("GaussianMove", "MHMove"):
+        hint = ("; a Metropolis move is recognised by its attributes (cov, mode and factor, or a callable get_proposal) -- use "
+                "alabi_amd.moves.GaussianMove")
     raise NotImplementedError(f"move {name} is not available on the GPU: the ensemble sampler runs StretchMove, DEMove, WalkMove, "
                               f"KDEMove, alabi_amd.moves.SnookerMove and weighted mixtures of them{hint}")
 
@@ -253,4 +368,12 @@ def parse_moves(moves, ndim):
         raise ValueError("move weights must be non-negative, finite and not all zero")
     if len(parsed) > MAX_MOVES:
         raise ValueError(f"at most {MAX_MOVES} moves in a mixture")
+    if any(isinstance(m, MHMove) for m in parsed) and not all(isinstance(m, MHMove) for m in parsed):
+        raise ValueError("a move set that holds an MHMove must consist of MHMove objects only: its proposal function runs on the "
+                         "host, every other move on the device")
+    for m in parsed:
+        if isinstance(m, GaussianMove):
+            m.scale_matrix(int(ndim))              # emcee's ValueError("Dimension mismatch in proposal")
+        elif isinstance(m, MHMove) and m.ndim is not None and m.ndim != int(ndim):
+            raise ValueError("Dimension mismatch in proposal")
     return MoveSet(parsed, w, int(ndim))

@@ -57,7 +57,14 @@ class EnsembleSampler:
         ``moves``: emcee's proposal moves (alabi_amd.moves) -- None (the stretch move with ``a``), a ``StretchMove``,
         ``DEMove``, ``SnookerMove`` (the snooker update of ter Braak & Vrugt 2008), ``WalkMove`` or ``KDEMove``, a list of them, or a
         list of (move, weight) pairs from which one move is chosen per step; emcee's own ``StretchMove`` / ``DEMove`` / ``WalkMove`` /
-        ``KDEMove`` objects are recognised, its ``DESnookerMove`` and its Metropolis moves are refused.  Works with ``n_ensembles``
+        ``KDEMove`` objects are recognised, its ``DESnookerMove`` is refused.  A ``GaussianMove(cov, mode, factor)`` is emcee's
+        Gaussian Metropolis move: a set of Gaussian moves alone is ``nwalkers`` independent chains (any ``nwalkers >= 1``; one
+        workgroup per walker and all steps of a call in one launch, ``last_path == "metropolis"``), mixed with red-blue moves it
+        runs with one launch per half step.  An ``MHMove(proposal_function)`` -- or any object with a callable ``get_proposal``,
+        emcee's own Metropolis moves among them -- runs on a host-driven loop: per step the walkers travel to the host, the
+        proposal function is called with a ``numpy.random.RandomState`` seeded from ``seed`` and the log-probability of the
+        proposals is evaluated on the device; one round trip per step, slow by nature; ``n_ensembles == 1`` and such moves only.
+        Neither can be sharded.  Moves work with ``n_ensembles``
         > 1 and with host callables; a set holding a ``DEMove`` needs ``nwalkers >= 4``, one holding a ``SnookerMove`` ``nwalkers >=
         6``, a ``WalkMove(s)`` ``2 <= s <= nwalkers // 2``, a ``KDEMove`` ``nwalkers >= 2 ndim + 2`` (and warns below about
         ``8 (ndim + 1)``: few walkers per dimension mean few accepted proposals); each of these runs with one launch per half step
@@ -77,8 +84,10 @@ class EnsembleSampler:
         if self.ndim != gp.ndim:
             raise ValueError("ndim does not match the GP")
         if self.nwalkers < 2 * self.ndim and not live_dangerously:
-            raise RuntimeError("It is unadvisable to use a red-blue move with fewer walkers than twice the "
-                               "number of dimensions.")
+            few = parse_moves(moves, self.ndim)           # looked at here only to see whether the rule applies: a set of
+            if few is None or not (few.all_metropolis or few.all_mh):   # Metropolis moves has no halves to keep populated
+                raise RuntimeError("It is unadvisable to use a red-blue move with fewer walkers than twice the "
+                                   "number of dimensions.")
         self.gp = gp
         self._y = y
         self.bounds = np.ascontiguousarray(np.asarray(bounds, dtype=np.float64).reshape(self.ndim, 2))
@@ -102,6 +111,18 @@ class EnsembleSampler:
         if self.shard and (self.generic or self.n_ensembles != 1):
             raise ValueError("shard=True needs the fused log-probability (no host callables) and n_ensembles == 1")
         self._move_set = parse_moves(moves, self.ndim)
+        metropolis = self._move_set is not None and (self._move_set.all_metropolis or self._move_set.all_mh)
+        if self.nwalkers < 1:
+            raise ValueError("nwalkers must be at least 1")
+        if self.nwalkers < 2 and not metropolis:
+            raise ValueError("a red-blue move needs at least two walkers")
+        if self._move_set is not None and (self._move_set.has_gauss or self._move_set.all_mh):
+            if self.shard:
+                raise ValueError("shard=True cannot run a GaussianMove or an MHMove: a Metropolis proposal reads no other walker, so "
+                                 "there is nothing to exchange -- run replicas (n_ensembles, or one sampler per rank) instead")
+            if self._move_set.all_mh and self.n_ensembles != 1:
+                raise ValueError("an MHMove runs on the host loop, which needs n_ensembles == 1")
+        self._mh_rng = None
         if self._move_set is not None and self._move_set.multi_partner:
             if self._move_set.has_de and self.nwalkers < 4:
                 raise ValueError("DEMove draws two distinct walkers from the complementary half: nwalkers >= 4")
@@ -140,7 +161,8 @@ class EnsembleSampler:
             return
         self._release()
         e = C.c_void_p()
-        st = _lib.lib().alabi_ens_create(h, self.nwalkers, self.ndim, self.n_ensembles,
+        create = _lib.lib().alabi_ens_create if self.nwalkers >= 2 else _lib.lib().alabi_ens_create_metropolis
+        st = create(h, self.nwalkers, self.ndim, self.n_ensembles,
                                          _lib.host_doubles(self.bounds.ravel()), C.c_ulonglong(self.seed), C.byref(e))
         _lib.check(st, "alabi_ens_create")
         if self.logp_affine != (1.0, 0.0):
@@ -152,8 +174,11 @@ class EnsembleSampler:
                        "alabi_ens_set_normal_prior")
         if self.logp_map is not None:
             _lib.check(_lib.lib().alabi_ens_set_logp_map(e, {"nlog": 1, "log": 2}[self.logp_map]), "alabi_ens_set_logp_map")
-        if self._move_set is not None:
+        if self._move_set is not None and not self._move_set.all_mh:
             m = self._move_set
+            for k, Cm, diagonal in m.scales():            # a Gaussian move's factor goes ahead of the table that names it
+                _lib.check(_lib.lib().alabi_ens_set_move_scale(e, k, _lib.host_doubles(Cm.ravel()), int(diagonal)),
+                           "alabi_ens_set_move_scale")
             _lib.check(_lib.lib().alabi_ens_set_moves(e, len(m), (C.c_int * len(m))(*[int(k) for k in m.kind]),
                                                       _lib.host_doubles(m.cum), _lib.host_doubles(m.p0), _lib.host_doubles(m.p1)),
                        "alabi_ens_set_moves")
@@ -292,6 +317,43 @@ class EnsembleSampler:
             done += n
         torch.cuda.current_stream().synchronize()
 
+    def _run_mh(self, nsteps, thin_by, chain, chain_lp):
+        """The host loop of an all-MHMove set: per step one move is drawn from the weights, the walkers travel to the host, the
+        move's proposal function makes q and its log factors, the log-probability of q is evaluated on the device (or through
+        the host callables) and a proposal is accepted where log(rng.rand(W)) < lp' - lp + lf.  One round trip per step."""
+        ms, W, d = self._move_set, self.nwalkers, self.ndim
+        if getattr(self, "_mh_rng", None) is None:
+            self._mh_rng = np.random.RandomState(self.seed & 0xFFFFFFFF)
+        rng = self._mh_rng
+        dev = self._coords.device
+        x = self._coords.cpu().numpy()
+        lp = self._logp.cpu().numpy()
+        nacc = np.zeros(W, dtype=np.int64)
+        for t in range(nsteps):
+            move = ms.moves[int(rng.choice(len(ms.moves), p=ms.weights))] if len(ms.moves) > 1 else ms.moves[0]
+            q, lf = move.get_proposal(x, rng)
+            q = np.asarray(q, dtype=np.float64)
+            lf = np.asarray(lf, dtype=np.float64)
+            if q.shape != (W, d) or lf.shape != (W,):
+                raise ValueError(f"an MHMove's proposal function must return (q[{W}, {d}], log_factors[{W}]), got shapes "
+                                 f"{q.shape} and {lf.shape}")
+            lpq = self.compute_log_prob(torch.as_tensor(np.ascontiguousarray(q), device=dev)).cpu().numpy()
+            if np.any(np.isnan(lpq)):
+                raise ValueError("Probability function returned NaN")
+            with np.errstate(invalid="ignore"):
+                acc = np.log(rng.rand(W)) < lpq - lp + lf
+            x = np.where(acc[:, None], q, x)
+            lp = np.where(acc, lpq, lp)
+            nacc += acc
+            k = t + 1
+            if chain is not None and k % thin_by == 0:
+                chain[k // thin_by - 1].copy_(torch.as_tensor(x, device=dev))
+                chain_lp[k // thin_by - 1].copy_(torch.as_tensor(lp, device=dev))
+        self._coords = torch.as_tensor(np.ascontiguousarray(x), device=dev)
+        self._logp = torch.as_tensor(np.ascontiguousarray(lp), device=dev)
+        self._naccept += torch.as_tensor(nacc, device=dev)
+        torch.cuda.current_stream().synchronize()
+
     def run_mcmc(self, initial_state, nsteps, thin_by=1, progress=False, store=True, skip_initial_state_check=False, **kw):
         nsteps = int(nsteps)
         thin_by = int(thin_by)
@@ -344,9 +406,13 @@ class EnsembleSampler:
         chain = torch.empty((nstore, self.total_walkers, self.ndim), dtype=torch.float64, device=dev) if nstore else None
         chain_lp = torch.empty((nstore, self.total_walkers), dtype=torch.float64, device=dev) if nstore else None
         t0 = time.perf_counter()
-        if self.generic:
-            self._run_generic(nsteps, thin_by, chain, chain_lp)
-            self.last_path = "host-callback"
+        mh = self._move_set is not None and self._move_set.all_mh
+        if self.generic or mh:
+            if mh:
+                self._run_mh(nsteps, thin_by, chain, chain_lp)
+            else:
+                self._run_generic(nsteps, thin_by, chain, chain_lp)
+            self.last_path = "host-mh" if mh else "host-callback"
             self.last_run_seconds = time.perf_counter() - t0
             self.iteration += nsteps
             self._rng_step += nsteps
@@ -375,8 +441,8 @@ class EnsembleSampler:
         _lib.check(st, "alabi_ens_run")
         path = C.c_int(0)
         _lib.lib().alabi_ens_last_path(self._ens, C.byref(path))
-        self.last_path = {1: "stream", 3: "group"}.get(path.value, "launch-per-half-step")
-        self.last_stream_kernel = {1: "ens_stream_kernel", 3: "ens_group_kernel"}.get(path.value)
+        self.last_path = {1: "stream", 3: "group", 4: "metropolis"}.get(path.value, "launch-per-half-step")
+        self.last_stream_kernel = {1: "ens_stream_kernel", 3: "ens_group_kernel", 4: "ens_mh_kernel"}.get(path.value)
         variant = C.c_int(0)                                  # path 1: one workgroup per list position, or a pair of them
         _lib.lib().alabi_ens_stream_variant(self._ens, C.byref(variant))
         self.last_stream_variant = {0: "single", 1: "pair"}[variant.value] if path.value == 1 else None

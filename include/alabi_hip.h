@@ -205,6 +205,10 @@ int alabi_utility_eval(int algo, const double* Xs, long long M, int d, const dou
  * inside their ensemble.  bounds is a host array [d,2] in the GP's (scaled) coordinates. */
 int alabi_ens_create(alabi_gp* gp, int W, int d, int n_ensembles, const double* bounds,
                      unsigned long long seed, alabi_ens** out);
+/* alabi_ens_create for Metropolis sets, which need no complementary half: W >= 1.  On a handle with W == 1 alabi_ens_set_moves,
+ * alabi_ens_run and alabi_ens_draw are ALABI_BAD_ARGUMENT unless every move of the table is a Gaussian move (kind 5). */
+int alabi_ens_create_metropolis(alabi_gp* gp, int n_walkers, int d, int n_ensembles, const double* bounds,
+                                unsigned long long seed, alabi_ens** out);
 int alabi_ens_destroy(alabi_ens* ens);
 /* Independent normal priors on selected coordinates on top of the uniform box: the reference's lnprior_normal
  * (alabi/utility.py:370-378; passed to run_emcee as prior_fn, alabi/core.py:2108).  mean[d], std[d] on the HOST in the
@@ -248,15 +252,48 @@ int alabi_ens_set_logp_map(alabi_ens* ens, int kind);
  * (alabi_ens_kde_singular).  The subset, r and the normals come from Philox streams 6-8 where the proposal is formed (layout in
  * ensemble.hip); streams 0-5 do not depend on these moves.  Both run like a snooker set: one launch per half step, one proposal
  * per workgroup, in front of every half step of a set with a KDE move one pre-pass launch; refused by the sharded run.  A
- * violated bound is ALABI_BAD_ARGUMENT. */
+ * violated bound is ALABI_BAD_ARGUMENT.
+ * kind 5 GaussianMove (emcee 3 moves/gaussian.py: a Metropolis proposal q = x + f C z around the walker, log factor 0): p0 = ln
+ * factor >= 0 (0: no scale factor, f = 1; otherwise f = exp(v), v ~ U(-ln factor, ln factor), ONE draw per step and ensemble), p1 =
+ * mode: 0 moves every coordinate, 1 one coordinate drawn per walker and step, 2 coordinate (step mod d).  The lower-triangular
+ * scale factor C travels apart from the table and AHEAD of it: alabi_ens_set_move_scale(ens, k, ...) for every Gaussian move k,
+ * then alabi_ens_set_moves, which is ALABI_BAD_ARGUMENT for a kind-5 move whose slot has been given no factor since the last
+ * table was set (or, in modes 1 and 2, a factor that is not diagonal): a table never holds a Gaussian move it cannot run.  Draws: Philox counter (step, global walker id, stream word S + 16 b) --
+ * S = 9, b = 0: v = (2 u53(r0, r1) - 1) ln factor at the ensemble's walker 0; S = 9, b = 1: the coordinate of mode 1,
+ * (r0 d) >> 32, at the walker; S = 10, b = k: the normal z_k (Box-Muller as stream 4); accept uniform and move choice are streams
+ * 2 and 3 as for every move; streams 0-8 do not depend on a Gaussian move.  Arithmetic: s_k = sum_{i <= k} C[k][i] z_i, i
+ * ascending, by fma from 0 (a diagonal C: the single term), q_k = fma(f, s_k, x_k); in modes 1 and 2 every other coordinate is
+ * copied.  A proposal reads nothing of the other half, so in the launch-per-half-step kernels (mixtures with red-blue moves, host
+ * callables, alabi_ens_set_stream(ens, 0)) a full Metropolis step is the rule applied to split 0 and then to split 1.  A table of
+ * Gaussian moves alone runs on ens_mh_kernel (path 4 of alabi_ens_last_path): one workgroup per walker, every step of a chunk in
+ * one launch, the same bits as path 0; it accepts W == 1.  Such a table runs on path 0 instead -- alabi_ens_last_path says so, the
+ * results are the same -- after alabi_ens_set_stream(ens, 0), with ALABI_ENS_MH=0 in the environment, with workgroups of more
+ * than 512 lanes (ALABI_ENS_THREADS=1024) or where its factors need more than 128 KB of LDS (more than four moves at d = 64).
+ * ALABI_ENS_MH_CHUNK=k caps the steps of one launch at k; both variables are read at every alabi_ens_run.  Refused by the
+ * sharded run. */
 int alabi_ens_set_moves(alabi_ens* ens, int n, const int* kind, const double* cum, const double* p0, const double* p1);
 
+/* The scale factor of slot k (0 <= k < 8) of the move table, for the Gaussian move that the NEXT alabi_ens_set_moves puts there
+ * (see kind 5 above): C host [d, d] row-major, lower triangular with a positive diagonal and zeros above it; diagonal != 0 says
+ * that it is diagonal (required for modes 1 and 2).  Where slot k of the current table holds a Gaussian move, that move runs
+ * with the new factor from the next call on (ALABI_BAD_ARGUMENT if it moves one coordinate and the factor is not diagonal).  At
+ * most 8 x 64 x 64 doubles are held on the device.  Synchronises the device. */
+int alabi_ens_set_move_scale(alabi_ens* ens, int k, const double* C /* host */, int diagonal);
+/* ens_mh_kernel's last launch: out[4] = workgroup size, steps per launch, LDS bytes, 1 if the training set is streamed in tiles
+ * (Npad / 2 exceeds the workgroup). */
+int alabi_ens_mh_plan(alabi_ens* ens, int* out /* host [4] */);
+
 /* Enable / disable the persistent dataflow kernel for alabi_ens_run on this handle (default: enabled when the
- * ensemble fits one workgroup per CU).  Returns ALABI_BAD_ARGUMENT when enabling is impossible. */
+ * ensemble fits one workgroup per CU).  Returns ALABI_BAD_ARGUMENT when enabling is impossible.
+ * The same switch turns ens_mh_kernel (path 4, a table of Gaussian moves alone) on and off; it is a setting of the handle and
+ * holds for whichever move table a later alabi_ens_run finds, not only for the one set when it is called.  ens_mh_kernel needs
+ * no version history, so enabling succeeds on a handle without one while its table is all Gaussian; a red-blue table set later
+ * on such a handle runs with one launch per half step, as before. */
 int alabi_ens_set_stream(alabi_ens* ens, int enabled);
 /* Which path the last alabi_ens_run took: 1 = persistent dataflow kernel with the training set in one workgroup's
  * registers (ens_stream_kernel: N <= 2048, small d), 3 = persistent group kernel (ens_group_kernel: training set
- * partitioned over groups of workgroups, kernel sums on the matrix cores; d <= 30), 0 = one launch per half step. */
+ * partitioned over groups of workgroups, kernel sums on the matrix cores; d <= 30), 4 = ens_mh_kernel (a table of Gaussian moves
+ * alone: one workgroup per walker; alabi_ens_set_stream(ens, 0) sends such a table to path 0), 0 = one launch per half step. */
 int alabi_ens_last_path(alabi_ens* ens, int* path /* host */);
 /* Which persistent kernel the last alabi_ens_run of path 1 launched: 0 = ens_stream_kernel (one workgroup per list position),
  * 1 = ens_pair_kernel (two per list position, which evaluate both outcomes of a pending update; chosen where 2 ceil(W/2) E
@@ -438,6 +475,17 @@ int alabi_ens_step_with_randoms_kde(alabi_ens* ens, double* coords, double* logp
                                     const int* r, const double* z, const double* u_acc, double* lnfac_out, long long* n_accept,
                                     void* stream);
 int alabi_ens_kde_singular(alabi_ens* ens, long long* count /* host */);
+
+/* Test entries of the Gaussian move (kind 5 of alabi_ens_set_moves), siblings of alabi_ens_step_with_randoms_de (n_ensembles == 1,
+ * all arrays on the device, draws keyed by WALKER id).
+ * alabi_ens_step_with_randoms_gauss: one full step of move k_move of the table (its scale factor set) with the step's scale
+ * factor f, coord[W] int32 the coordinate that moves (-1: all of them; out of range: that proposal is a no-op), z[W, d] the
+ * normals and u_acc[W] the accept uniform.
+ * alabi_ens_export_gauss_draws: for the step last drawn by alabi_ens_export_draws -- f [E] the scale factor of each ensemble's
+ * step, coord [E*W] and z [E*W, d] by walker id (f = 1 and coord = -1 where the step's move is not a Gaussian move). */
+int alabi_ens_step_with_randoms_gauss(alabi_ens* ens, double* coords, double* logp, const int* order, int n0, int k_move, double f,
+                                      const int* coord, const double* z, const double* u_acc, long long* n_accept, void* stream);
+int alabi_ens_export_gauss_draws(alabi_ens* ens, double* f, int* coord, double* z, void* stream);
 
 /* Nested sampling (dynesty's NestedSampler / DynamicNestedSampler with sample="rwalk" as driven by
  * SurrogateModel.run_dynesty, alabi/core.py:2417-2787, likelihood = surrogate_log_likelihood core.py:1446-1508, prior =
