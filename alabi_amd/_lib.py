@@ -76,6 +76,8 @@ SIGNATURES = {
     "alabi_ens_set_moves": (_i, [_vp, _i, _pi, _pd, _pd, _pd]),
     "alabi_ens_set_move_scale": (_i, [_vp, _i, _pd, _i]),
     "alabi_ens_mh_plan": (_i, [_vp, _pi]),
+    "alabi_ens_hmc_plan": (_i, [_vp, _pi]),
+    "alabi_ens_log_prob_grad": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "alabi_ens_set_stream": (_i, [_vp, _i]),
     "alabi_ens_last_path": (_i, [_vp, _pi]),
     "alabi_ens_stream_variant": (_i, [_vp, _pi]),
@@ -112,6 +114,8 @@ SIGNATURES = {
     "alabi_ens_kde_singular": (_i, [_vp, _pll]),
     "alabi_ens_step_with_randoms_gauss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp]),
     "alabi_ens_export_gauss_draws": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "alabi_ens_step_with_randoms_hmc": (_i, [_vp, _vp, _vp, _i, _d, _vp, _vp, _vp, _vp]),
+    "alabi_ens_export_hmc_draws": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp]),
     "alabi_ns_create": (_i, [_vp, _i, _pd, _ull, C.POINTER(_vp)]),
     "alabi_ns_destroy": (_i, [_vp]),
     "alabi_ns_set_logp": (_i, [_vp, _d, _d, _i]),

@@ -964,7 +964,10 @@ class SurrogateModel(object):
         Gaussian moves alone runs the walkers as independent random-walk Metropolis chains on the surrogate, any number of them,
         all steps of a call in one kernel launch; it mixes with the red-blue moves too.  ``alabi_amd.moves.MHMove(fn)`` and any
         object with a callable ``get_proposal`` (emcee's own ``MHMove`` / ``GaussianMove``) run a Python proposal function on a
-        host-driven loop, one round trip per step: slow by nature.  Any other emcee move raises ``NotImplementedError`` -- in
+        host-driven loop, one round trip per step: slow by nature.  ``alabi_amd.moves.HMCMove(cov, step_size=None, n_leapfrog=8,
+        jitter=None)`` runs Hamiltonian Monte Carlo on the surrogate's closed-form gradient (``n_leapfrog=1``: MALA), alone or as
+        a mixture of HMC moves; ``cov`` is given in the sampler's (scaled) coordinates like a ``GaussianMove``'s; it needs the
+        surrogate likelihood with a prior that fuses (none, uniform or normal) and cannot be sharded.  Any other emcee move raises ``NotImplementedError`` -- in
         particular emcee's ``DESnookerMove``, whose arithmetic is not the published rule; none of ``DEMove``, ``SnookerMove``,
         ``WalkMove``, ``KDEMove``, ``GaussianMove``, ``MHMove`` can be combined with ``"shard": True``.
 
@@ -985,6 +988,9 @@ class SurrogateModel(object):
         if kw.get("shard", False) and move_set is not None and (move_set.has_gauss or move_set.all_mh):
             raise ValueError('sampler_kwargs={"shard": True} cannot run a GaussianMove or an MHMove: a Metropolis proposal reads no '
                              'other walker, so there is nothing to exchange -- run replicas instead')
+        if kw.get("shard", False) and move_set is not None and move_set.has_hmc:
+            raise ValueError('sampler_kwargs={"shard": True} cannot run an HMCMove: the sharded form is not built -- run replicas '
+                             'instead')
         if kw.get("shard", False) and move_set is not None and move_set.multi_partner:
             raise ValueError('sampler_kwargs={"shard": True} cannot run a DEMove or a SnookerMove: the sharded ensemble links one '
                              'partner row per proposal')

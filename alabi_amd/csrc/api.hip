@@ -763,7 +763,7 @@ int alabi_ens_set_logp_map(alabi_ens* e, int kind) {
 int alabi_ens_set_moves(alabi_ens* e, int n, const int* kind, const double* cum, const double* p0, const double* p1) {
     if (!e || n < 0 || n > ALABI_MAX_MOVES || (n > 0 && (!kind || !cum || !p0 || !p1))) return ALABI_BAD_ARGUMENT;
     MoveTable mt{};
-    bool de = false, snooker = false, walk = false, kde = false, gauss = false, all_gauss = n > 0;
+    bool de = false, snooker = false, walk = false, kde = false, gauss = false, all_gauss = n > 0, hmc = false, all_hmc = n > 0;
     const int nc_min = e->W / 2, nc_max = (e->W + 1) / 2;   // the two complementary halves
     double prev = 0.0;
     for (int k = 0; k < n; ++k) {
@@ -784,16 +784,22 @@ int alabi_ens_set_moves(alabi_ens* e, int n, const int* kind, const double* cum,
             // its scale factor has been handed over for this slot (alabi_ens_set_move_scale), diagonal where one coordinate moves
             if (!((e->gauss_staged >> k) & 1) || (p1[k] != 0.0 && !((e->gauss_diag >> k) & 1))) return ALABI_BAD_ARGUMENT;
             gauss = true;
+        } else if (kind[k] == 6) {                           // HMC: p0 = step size > 0, p1 = n_leapfrog (1 ... 64) + ln jitter / 512
+            if (!(p0[k] > 0.0) || !std::isfinite(p0[k]) || !std::isfinite(p1[k]) || !(p1[k] >= 1.0) || !(p1[k] < 65.0)) return ALABI_BAD_ARGUMENT;
+            if (!((e->gauss_staged >> k) & 1)) return ALABI_BAD_ARGUMENT;   // its scale factor has been handed over for this slot
+            hmc = true;
         }
         else return ALABI_BAD_ARGUMENT;
         if (kind[k] != 5) all_gauss = false;
+        if (kind[k] != 6) all_hmc = false;
         mt.kind[k] = kind[k]; mt.cum[k] = cum[k]; mt.p0[k] = p0[k]; mt.p1[k] = p1[k];
     }
     if (n > 0 && !(prev > 0.0)) return ALABI_BAD_ARGUMENT;
-    if (e->W < 2 && !all_gauss) return ALABI_BAD_ARGUMENT;   // a red-blue move needs a complementary half
+    if (hmc && !all_hmc) return ALABI_BAD_ARGUMENT;      // an HMC move runs on ens_hmc_kernel alone: no mixture with another kind
+    if (e->W < 2 && !all_gauss && !all_hmc) return ALABI_BAD_ARGUMENT;   // a red-blue move needs a complementary half
     if (de && e->W < 4) return ALABI_BAD_ARGUMENT;       // two distinct partners in a complementary list of W / 2 walkers
     if (snooker && e->W < 6) return ALABI_BAD_ARGUMENT;  // three distinct partners
-    if (n > 0) { const int st = ensure_move_buffers(e, snooker || walk || kde || gauss, walk || kde || gauss); if (st != ALABI_OK) return st; }
+    if (n > 0 && !hmc) { const int st = ensure_move_buffers(e, snooker || walk || kde || gauss, walk || kde || gauss); if (st != ALABI_OK) return st; }
     if (kde) { const int st = ensure_kde_buffers(e); if (st != ALABI_OK) return st; }
     mt.n = n;
     e->moves = mt;
@@ -802,6 +808,7 @@ int alabi_ens_set_moves(alabi_ens* e, int n, const int* kind, const double* cum,
     e->has_wk = walk || kde || gauss;                    // proposals formed where they are used: the whole-half instantiations
     e->has_kde = kde;
     e->has_gauss = gauss; e->all_gauss = gauss && all_gauss;
+    e->all_hmc = hmc && all_hmc;
     e->gauss_staged = 0;                                 // scale factors belong to the table they were handed over for
     e->drawn_n = 0;                                      // records drawn under the old move set are not the new set's
     e->ahead_valid = false;                              // nor are those made ahead for the next stream call
@@ -845,7 +852,7 @@ int alabi_ens_set_stream(alabi_ens* e, int enabled) {
     // The switch belongs to the handle, not to the move table: it covers the persistent kernels of a red-blue table (they need
     // the version history) and ens_mh_kernel of an all-Gaussian one (it needs nothing), whichever table the next run finds.
     const bool can_stream = e->hist && e->err;
-    if (enabled && !can_stream && !e->all_gauss) return ALABI_BAD_ARGUMENT;
+    if (enabled && !can_stream && !e->all_gauss && !e->all_hmc) return ALABI_BAD_ARGUMENT;
     e->mh_ok = enabled ? 1 : 0;
     e->stream_ok = (enabled && can_stream) ? 1 : 0;
     e->settings_gen++;
@@ -1069,6 +1076,19 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
     hipStream_t s = as_stream(stream);
     int st;
     if ((st = sync_consts(e, s)) != ALABI_OK) return st;
+    // An all-HMC set: ens_hmc_kernel or nothing -- there is no launch-per-half-step form, and alabi_ens_set_stream does not apply.
+    if (e->all_hmc) {
+        const int chunk = ens_hmc_chunk(e);
+        if (chunk <= 0) return ALABI_BAD_ARGUMENT;                    // the factors and weights exceed the LDS, or no dimension bucket
+        e->last_path = 5;
+        e->last_state_ok = false;
+        for (long long done = 0; done < nsteps; done += chunk) {
+            const int K = (int)(nsteps - done < chunk ? nsteps - done : chunk);
+            if ((st = launch_ens_hmc(e, coords, logp, step0, done, K, thin_by, chain, chain_logp, n_accept, 0, 0.0, nullptr, nullptr, s)) != ALABI_OK) return st;
+        }
+        e->hmc_plan[1] = chunk;
+        return ALABI_OK;
+    }
     if (e->W < 2 && !e->all_gauss) return ALABI_BAD_ARGUMENT;         // a red-blue move needs a complementary half
     // An all-Gaussian set: W independent chains, one workgroup per walker, every step of a chunk in one launch (ens_mh_kernel).
     // The step counters travel by value; nothing is read back.
@@ -1253,6 +1273,7 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
 int alabi_ens_draw(alabi_ens* e, long long step0, int nsteps, double a, void* stream) {
     if (!e || nsteps <= 0 || nsteps > e->chunk_cap || !(a > 1.0)) return ALABI_BAD_ARGUMENT;
     if (e->W < 2 && !e->all_gauss) return ALABI_BAD_ARGUMENT;         // a red-blue record names a walker of the other half
+    if (e->all_hmc) return ALABI_BAD_ARGUMENT;                        // an HMC step has no record: its draws are made where it runs
     hipStream_t s = as_stream(stream);
     int st;
     if ((st = set_run_state(e, step0, 0, s)) != ALABI_OK) return st;
@@ -1462,6 +1483,37 @@ int alabi_ens_step_with_randoms_gauss(alabi_ens* e, double* coords, double* logp
 int alabi_ens_export_gauss_draws(alabi_ens* e, double* f, int* coord, double* z, void* stream) {
     if (!e || !f || !coord || !z || e->drawn_n < 1 || !e->mv.kind) return ALABI_BAD_ARGUMENT;
     return launch_ens_gauss_export(e, f, coord, z, as_stream(stream));
+}
+
+int alabi_ens_hmc_plan(alabi_ens* e, int* out) {
+    if (!e || !out) return ALABI_BAD_ARGUMENT;
+    for (int i = 0; i < 4; ++i) out[i] = e->hmc_plan[i];
+    return ALABI_OK;
+}
+
+int alabi_ens_log_prob_grad(alabi_ens* e, const double* coords, int M, double* logp, double* grad, void* stream) {
+    if (!e || !coords || !logp || !grad || M < 0) return ALABI_BAD_ARGUMENT;
+    if (!e->gp->computed || !e->gp->has_alpha) return ALABI_NOT_COMPUTED;
+    if (M == 0) return ALABI_OK;
+    const int st = sync_consts(e, as_stream(stream));
+    if (st != ALABI_OK) return st;
+    return launch_ens_lp_grad(e, coords, M, logp, grad, as_stream(stream));
+}
+
+int alabi_ens_step_with_randoms_hmc(alabi_ens* e, double* coords, double* logp, int k_move, double eps, const double* z,
+                                    const double* u_acc, long long* n_accept, void* stream) {
+    if (!e || !coords || !logp || !z || !u_acc || e->E != 1 || !e->all_hmc) return ALABI_BAD_ARGUMENT;
+    if (k_move < 0 || k_move >= e->moves.n || !(eps > 0.0) || !std::isfinite(eps)) return ALABI_BAD_ARGUMENT;
+    if (!e->gp->computed || !e->gp->has_alpha) return ALABI_NOT_COMPUTED;
+    hipStream_t s = as_stream(stream);
+    const int st = sync_consts(e, s);
+    if (st != ALABI_OK) return st;
+    return launch_ens_hmc(e, coords, logp, 0, 0, 1, 1, nullptr, nullptr, n_accept, k_move, eps, z, u_acc, s);
+}
+
+int alabi_ens_export_hmc_draws(alabi_ens* e, long long step, int* move, double* eps, double* z, double* u_acc, void* stream) {
+    if (!e || !move || !eps || !z || !e->all_hmc) return ALABI_BAD_ARGUMENT;
+    return launch_ens_hmc_export(e, step, move, eps, z, u_acc, as_stream(stream));
 }
 
 int alabi_ens_kde_singular(alabi_ens* e, long long* count) {

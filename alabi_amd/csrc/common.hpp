@@ -279,6 +279,10 @@ struct alabi_ens {
     bool has_gauss = false, all_gauss = false;
     int mh_ok = 1;
     int mh_plan[4] = {0};     // last ens_mh_kernel launch: threads, steps per launch, LDS bytes, tiled (alabi_ens_mh_plan)
+    // HMC moves (kind 6): their scale factors share gauss_C / gauss_staged / gauss_diag with the Gaussian moves (a table holds one
+    // kind or the other); all_hmc: every move of the table is an HMC move, the only table that holds one (ens_hmc_kernel runs it)
+    bool all_hmc = false;
+    int hmc_plan[4] = {0};    // last ens_hmc_kernel launch: threads, steps per launch, LDS bytes, tiled (alabi_ens_hmc_plan)
 };
 
 namespace alabi {
@@ -406,6 +410,12 @@ int launch_ens_half_args(alabi_ens* e, const HalfArgs& args, int nblocks, hipStr
 int launch_ens_mh(alabi_ens* e, double* coords, double* logp, long long step0, long long done0, int K, int thin_by, double* chain,
                   double* chain_logp, long long* n_accept, hipStream_t s);
 int ens_mh_chunk(const alabi_ens* e);    // steps per launch (0: the set does not run on ens_mh_kernel)
+// ens_hmc.hip: all steps of a chunk of an all-HMC set in one launch, one workgroup per walker (inj_z: one step from injected draws)
+int launch_ens_hmc(alabi_ens* e, double* coords, double* logp, long long step0, long long done0, int K, int thin_by, double* chain,
+                   double* chain_logp, long long* n_accept, int inj_k, double inj_e, const double* inj_z, const double* inj_u, hipStream_t s);
+int ens_hmc_chunk(const alabi_ens* e);   // steps per launch (0: the table does not run on ens_hmc_kernel)
+int launch_ens_lp_grad(alabi_ens* e, const double* pts, int M, double* logp, double* grad, hipStream_t s);
+int launch_ens_hmc_export(alabi_ens* e, long long step, int* move, double* e_out, double* z, double* u_acc, hipStream_t s);
 int launch_ens_lnprob(alabi_ens* e, const double* coords, int nwalkers, double* logp, int gate_box, hipStream_t s);
 int launch_ens_propose(alabi_ens* e, const HalfArgs& args, int nblocks, int gate_box, double* q, double* like, hipStream_t s);
 int launch_ens_accept(alabi_ens* e, const HalfArgs& args, int count, const double* q, const double* lp_new, hipStream_t s);

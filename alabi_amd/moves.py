@@ -29,6 +29,15 @@ Metropolis move --, alone or as a weighted mixture from which ONE move is chosen
   number of walkers, one workgroup per walker and all steps of a call in one launch (``ens_mh_kernel``).  Mixed with red-blue moves
   it runs with one launch per half step, the same rule applied to each half in turn.
 
+* ``HMCMove(cov, step_size=None, n_leapfrog=8, jitter=None)`` -- Hamiltonian Monte Carlo on the surrogate's closed-form gradient
+  (not an emcee move): the GP mean's gradient costs about two more passes over the training set, and a trajectory of ``n_leapfrog``
+  gradient steps decorrelates a walker where a random-walk proposal needs hundreds of steps (ndim = 32: see README.md).  ``cov``
+  estimates the posterior covariance as for ``GaussianMove`` -- the mass matrix is its inverse --; ``n_leapfrog=1`` is MALA.  Like
+  a Metropolis set, a set of HMC moves is ``nwalkers`` independent chains on one workgroup per walker (``ens_hmc_kernel``), any
+  ``nwalkers >= 1``; it holds HMC moves only (mixtures of several step sizes and trajectory lengths are the standard cure for
+  periodic trajectories) and needs the fused log-probability: no ``prior_fn`` / ``like_fn``, no ``shard``.  No adaptation of the
+  step size or the mass, no NUTS.
+
 ``MHMove(proposal_function, ndim=None)`` is emcee's generic Metropolis move: ``proposal_function(coords[W, d], rng) -> (q[W, d],
 log_factors[W])`` is a Python callable, so it runs on a host-driven step loop (one round trip per step: slow by nature), the
 log-probability still on the device.  A set that holds an ``MHMove`` consists of ``MHMove`` objects only.
@@ -47,11 +56,13 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["StretchMove", "DEMove", "SnookerMove", "WalkMove", "KDEMove", "GaussianMove", "MHMove", "MoveSet", "parse_moves",
-           "MAX_MOVES", "KIND_STRETCH", "KIND_DE", "KIND_SNOOKER", "KIND_WALK", "KIND_KDE", "KIND_GAUSS", "WALK_MAX_NC"]
+__all__ = ["StretchMove", "DEMove", "SnookerMove", "WalkMove", "KDEMove", "GaussianMove", "HMCMove", "MHMove", "MoveSet", "parse_moves",
+           "MAX_MOVES", "KIND_STRETCH", "KIND_DE", "KIND_SNOOKER", "KIND_WALK", "KIND_KDE", "KIND_GAUSS", "KIND_HMC", "WALK_MAX_NC",
+           "HMC_MAX_LEAPFROG"]
 
 MAX_MOVES = 8                    # ALABI_MAX_MOVES of the library: the table travels in the draw kernel's arguments
-KIND_STRETCH, KIND_DE, KIND_SNOOKER, KIND_WALK, KIND_KDE, KIND_GAUSS = 0, 1, 2, 3, 4, 5
+KIND_STRETCH, KIND_DE, KIND_SNOOKER, KIND_WALK, KIND_KDE, KIND_GAUSS, KIND_HMC = 0, 1, 2, 3, 4, 5, 6
+HMC_MAX_LEAPFROG = 64
 GAUSS_MODES = {"vector": 0, "random": 1, "sequential": 2}
 WALK_MAX_NC = 2048               # rows of a complementary half the walk move's kernel lists hold
 
@@ -193,6 +204,72 @@ class GaussianMove:
         return f"GaussianMove(cov=<{self.form}>, mode={self.mode!r}, factor={self.factor})"
 
 
+class HMCMove:
+    """Hamiltonian Monte Carlo move on the gradient of the fused log-probability (GP mean through the scalers, the y map, normal
+    priors).  ``cov`` as for ``GaussianMove``: a positive scalar, a vector of ``ndim`` positive variances or a positive definite
+    matrix, an estimate of the POSTERIOR covariance; with C C^T = cov the mass matrix is cov^-1 and one step is, in whitened
+    momentum z: z0 ~ N(0, I); z = z0 + (e / 2) C^T g; ``n_leapfrog`` times q += e C z, z += e C^T grad lnp(q) (e / 2 the last time);
+    accept iff lnp(q) - |z|^2 / 2 - lnp(x) + |z0|^2 / 2 > ln u and q lies in the open box -- only the end point is tested, in
+    between the trajectory follows the surrogate's smooth extension.  ``n_leapfrog=1`` is MALA, the
+    Metropolis-adjusted Langevin algorithm; at most 64.  ``step_size=None`` resolves to ``ndim ** -0.25``, the conventional scaling
+    of the optimal step with the dimension for a well-estimated ``cov``: it is untuned and unmeasured here, so look at the
+    acceptance fraction (0.6 - 0.9 is the usual aim) and set it.  ``jitter``: None or a number > 1 with the meaning of
+    ``GaussianMove(factor=)`` -- e = step_size exp(v), v ~ U(-ln jitter, ln jitter), one draw per step and ensemble (ln jitter is
+    rounded to a multiple of 2^-36 on its way into the library's table).  Nothing is adapted during a run."""
+
+    def __init__(self, cov, step_size=None, n_leapfrog=8, jitter=None):
+        if step_size is not None:
+            step_size = float(step_size)
+            if not (np.isfinite(step_size) and step_size > 0.0):
+                raise ValueError("HMCMove: step_size must be None or a positive, finite number")
+        self.step_size = step_size
+        if isinstance(n_leapfrog, bool) or int(n_leapfrog) != n_leapfrog or not (1 <= int(n_leapfrog) <= HMC_MAX_LEAPFROG):
+            raise ValueError(f"HMCMove: n_leapfrog must be an integer in 1 ... {HMC_MAX_LEAPFROG}")
+        self.n_leapfrog = int(n_leapfrog)
+        if jitter is not None:
+            jitter = float(jitter)
+            if not (np.isfinite(jitter) and jitter > 1.0 and np.log(jitter) < 511.0):
+                raise ValueError("HMCMove: jitter must be None or a finite number > 1")
+        self.jitter = jitter
+        try:
+            c = np.array(cov, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("Invalid proposal scale dimensions") from None
+        if c.ndim > 2 or (c.ndim == 2 and c.shape[0] != c.shape[1]) or c.size == 0:
+            raise ValueError("Invalid proposal scale dimensions")
+        if not np.all(np.isfinite(c)):
+            raise ValueError("HMCMove: cov must be finite")
+        self.cov = c
+        self.form = ("scalar", "vector", "matrix")[c.ndim]
+        if c.ndim < 2:
+            if np.any(c <= 0.0):
+                raise ValueError("HMCMove: a scalar or diagonal cov must be positive")
+            self._scale = np.sqrt(c)
+        else:
+            try:
+                self._scale = np.linalg.cholesky(c)
+            except np.linalg.LinAlgError:
+                raise ValueError("HMCMove: the covariance matrix is not positive definite") from None
+        self.ndim = None if c.ndim == 0 else int(c.shape[0])
+
+    @property
+    def diagonal(self):
+        return self.form != "matrix"
+
+    @property
+    def ln_jitter(self):
+        """ln jitter as the library's table carries it: rounded to a multiple of 2^-36, 0.0 for None."""
+        return 0.0 if self.jitter is None else float(np.round(np.log(self.jitter) * 2.0 ** 36) / 2.0 ** 36)
+
+    def resolved_step_size(self, ndim):
+        return float(ndim) ** -0.25 if self.step_size is None else self.step_size
+
+    scale_matrix = GaussianMove.scale_matrix
+
+    def __repr__(self):
+        return f"HMCMove(cov=<{self.form}>, step_size={self.step_size}, n_leapfrog={self.n_leapfrog}, jitter={self.jitter})"
+
+
 class MHMove:
     """Generic Metropolis move (emcee.moves.MHMove): ``proposal_function(coords[W, d], rng) -> (q[W, d], log_factors[W])`` with
     ``rng`` a ``numpy.random.RandomState``.  A Python callable cannot run on the device: the sampler drives such a set from the
@@ -213,6 +290,8 @@ def _table_row(m, ndim, nc=None):
     it and are NaN without."""
     if isinstance(m, GaussianMove):
         return KIND_GAUSS, 0.0 if m.factor is None else float(np.log(m.factor)), float(GAUSS_MODES[m.mode])
+    if isinstance(m, HMCMove):
+        return KIND_HMC, m.resolved_step_size(ndim), float(m.n_leapfrog) + m.ln_jitter / 512.0
     if isinstance(m, MHMove):
         return -1, 0.0, 0.0                        # not a row of the library's table: the host loop runs it
     if isinstance(m, WalkMove):
@@ -231,8 +310,8 @@ def _table_row(m, ndim, nc=None):
 class MoveSet:
     """A parsed move set: ``moves`` (this module's objects), normalised ``weights`` and the table the library takes --
     ``kind``, ``cum`` = np.cumsum(w / w.sum()), ``p0`` (a | gamma0 with its default resolved | gammas | s, 0 for all | KDE factor of
-    split 0 | ln factor, 0 for None), ``p1`` (0 | sigma | 0 | 0 | KDE factor of split 1 | mode 0 / 1 / 2).  A Gaussian move's scale
-    factor travels apart: ``scales()``.  The KDE factors depend on the number of walkers: they are NaN
+    split 0 | ln factor, 0 for None | HMC step size, resolved), ``p1`` (0 | sigma | 0 | 0 | KDE factor of split 1 | mode 0 / 1 / 2 |
+    n_leapfrog + ln jitter / 512).  A Gaussian or HMC move's scale factor travels apart: ``scales()``.  The KDE factors depend on the number of walkers: they are NaN
     until ``resolve(nwalkers)`` (called by EnsembleSampler, or pass ``nwalkers`` here)."""
 
     def __init__(self, moves, weights, ndim, nwalkers=None):
@@ -277,8 +356,18 @@ class MoveSet:
         return self
 
     def scales(self):
-        """[(k, C [ndim, ndim], diagonal)] for the Gaussian moves of the table (alabi_ens_set_move_scale, ahead of alabi_ens_set_moves)."""
-        return [(k, m.scale_matrix(self.ndim), m.diagonal) for k, m in enumerate(self.moves) if isinstance(m, GaussianMove)]
+        """[(k, C [ndim, ndim], diagonal)] for the Gaussian and HMC moves of the table (alabi_ens_set_move_scale, ahead of
+        alabi_ens_set_moves)."""
+        return [(k, m.scale_matrix(self.ndim), m.diagonal) for k, m in enumerate(self.moves) if isinstance(m, (GaussianMove, HMCMove))]
+
+    @property
+    def has_hmc(self):
+        return bool(np.any(self.kind == KIND_HMC))
+
+    @property
+    def all_hmc(self):
+        """Every member is an HMCMove: independent chains on the surrogate's gradient (ens_hmc_kernel)."""
+        return bool(len(self.moves) > 0 and np.all(self.kind == KIND_HMC))
 
     @property
     def has_gauss(self):
@@ -322,7 +411,7 @@ class MoveSet:
 
 def _as_move(obj):
     """This module's move for ``obj``: one of its own, or a foreign object recognised by class name and attributes."""
-    if isinstance(obj, (StretchMove, DEMove, SnookerMove, WalkMove, KDEMove, GaussianMove, MHMove)):
+    if isinstance(obj, (StretchMove, DEMove, SnookerMove, WalkMove, KDEMove, GaussianMove, HMCMove, MHMove)):
         return obj
     name = type(obj).__name__
     if name == "GaussianMove" and all(hasattr(obj, a) for a in ("cov", "mode", "factor")):
@@ -371,8 +460,11 @@ def parse_moves(moves, ndim):
     if any(isinstance(m, MHMove) for m in parsed) and not all(isinstance(m, MHMove) for m in parsed):
         raise ValueError("a move set that holds an MHMove must consist of MHMove objects only: its proposal function runs on the "
                          "host, every other move on the device")
+    if any(isinstance(m, HMCMove) for m in parsed) and not all(isinstance(m, HMCMove) for m in parsed):
+        raise ValueError("a move set that holds an HMCMove must consist of HMCMove objects only: mixtures of an HMCMove with other "
+                         "kinds of move are not built (ens_hmc_kernel runs a table of HMC moves alone)")
     for m in parsed:
-        if isinstance(m, GaussianMove):
+        if isinstance(m, (GaussianMove, HMCMove)):
             m.scale_matrix(int(ndim))              # emcee's ValueError("Dimension mismatch in proposal")
         elif isinstance(m, MHMove) and m.ndim is not None and m.ndim != int(ndim):
             raise ValueError("Dimension mismatch in proposal")

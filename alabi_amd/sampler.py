@@ -64,7 +64,10 @@ class EnsembleSampler:
         emcee's own Metropolis moves among them -- runs on a host-driven loop: per step the walkers travel to the host, the
         proposal function is called with a ``numpy.random.RandomState`` seeded from ``seed`` and the log-probability of the
         proposals is evaluated on the device; one round trip per step, slow by nature; ``n_ensembles == 1`` and such moves only.
-        Neither can be sharded.  Moves work with ``n_ensembles``
+        Neither can be sharded.  An ``HMCMove(cov, step_size, n_leapfrog, jitter)`` -- alone or in a weighted mixture of HMC
+        moves -- runs Hamiltonian Monte Carlo on the surrogate's closed-form gradient: independent chains again (any ``nwalkers >=
+        1``, ``last_path == "hmc"``, ``ens_hmc_kernel``); it needs the fused log-probability (no ``prior_fn`` / ``like_fn``) and
+        cannot be sharded.  Moves work with ``n_ensembles``
         > 1 and with host callables; a set holding a ``DEMove`` needs ``nwalkers >= 4``, one holding a ``SnookerMove`` ``nwalkers >=
         6``, a ``WalkMove(s)`` ``2 <= s <= nwalkers // 2``, a ``KDEMove`` ``nwalkers >= 2 ndim + 2`` (and warns below about
         ``8 (ndim + 1)``: few walkers per dimension mean few accepted proposals); each of these runs with one launch per half step
@@ -85,7 +88,7 @@ class EnsembleSampler:
             raise ValueError("ndim does not match the GP")
         if self.nwalkers < 2 * self.ndim and not live_dangerously:
             few = parse_moves(moves, self.ndim)           # looked at here only to see whether the rule applies: a set of
-            if few is None or not (few.all_metropolis or few.all_mh):   # Metropolis moves has no halves to keep populated
+            if few is None or not (few.all_metropolis or few.all_mh or few.all_hmc):   # such moves have no halves to keep populated
                 raise RuntimeError("It is unadvisable to use a red-blue move with fewer walkers than twice the "
                                    "number of dimensions.")
         self.gp = gp
@@ -111,7 +114,7 @@ class EnsembleSampler:
         if self.shard and (self.generic or self.n_ensembles != 1):
             raise ValueError("shard=True needs the fused log-probability (no host callables) and n_ensembles == 1")
         self._move_set = parse_moves(moves, self.ndim)
-        metropolis = self._move_set is not None and (self._move_set.all_metropolis or self._move_set.all_mh)
+        metropolis = self._move_set is not None and (self._move_set.all_metropolis or self._move_set.all_mh or self._move_set.all_hmc)
         if self.nwalkers < 1:
             raise ValueError("nwalkers must be at least 1")
         if self.nwalkers < 2 and not metropolis:
@@ -122,6 +125,14 @@ class EnsembleSampler:
                                  "there is nothing to exchange -- run replicas (n_ensembles, or one sampler per rank) instead")
             if self._move_set.all_mh and self.n_ensembles != 1:
                 raise ValueError("an MHMove runs on the host loop, which needs n_ensembles == 1")
+        if self._move_set is not None and self._move_set.has_hmc:
+            if self.generic:
+                raise ValueError("an HMCMove needs the gradient of the log-probability, which exists for the fused surrogate only: "
+                                 "a Python prior_fn or like_fn (the host-callback path) has none -- gradients through host "
+                                 "callables are not built")
+            if self.shard:
+                raise ValueError("shard=True cannot run an HMCMove: the sharded form is not built (a trajectory reads no other "
+                                 "walker, so there is nothing to exchange -- run replicas with n_ensembles instead)")
         self._mh_rng = None
         if self._move_set is not None and self._move_set.multi_partner:
             if self._move_set.has_de and self.nwalkers < 4:
@@ -250,6 +261,22 @@ class EnsembleSampler:
             return self._host_log_prob(c, self.surrogate(c) if self.like_fn_host is None else None)
         _lib.check(_lib.lib().alabi_ens_lnprob(self._ens, _lib.ptr(c), _lib.ptr(lp), _lib.current_stream()), "alabi_ens_lnprob")
         return lp
+
+    def log_prob_grad(self, coords):
+        """The fused log-probability and its gradient with respect to the coordinates at arbitrary points [M, d] (device
+        tensors (logp [M], grad [M, d])): what an ``HMCMove`` integrates -- GP mean through the scalers, the y map, normal priors;
+        -inf and a zero gradient outside the box.  Needs the fused log-probability (no host callables)."""
+        if self.generic:
+            raise ValueError("log_prob_grad needs the fused log-probability: host callables (prior_fn / like_fn) have no gradient")
+        self._ensure_ens()
+        c = _to_dev(coords, 2)
+        if c.ndim != 2 or c.shape[1] != self.ndim:
+            raise ValueError("coords must have shape (M, ndim)")
+        lp = torch.empty(c.shape[0], dtype=torch.float64, device=c.device)
+        g = torch.empty((c.shape[0], self.ndim), dtype=torch.float64, device=c.device)
+        _lib.check(_lib.lib().alabi_ens_log_prob_grad(self._ens, _lib.ptr(c), int(c.shape[0]), _lib.ptr(lp), _lib.ptr(g),
+                                                      _lib.current_stream()), "alabi_ens_log_prob_grad")
+        return lp, g
 
     def surrogate(self, points):
         """y_scaler^-1(GP mean) at arbitrary points [M,d] in the sampler's coordinates: no box gate, no prior (device tensor)."""
@@ -441,8 +468,8 @@ class EnsembleSampler:
         _lib.check(st, "alabi_ens_run")
         path = C.c_int(0)
         _lib.lib().alabi_ens_last_path(self._ens, C.byref(path))
-        self.last_path = {1: "stream", 3: "group", 4: "metropolis"}.get(path.value, "launch-per-half-step")
-        self.last_stream_kernel = {1: "ens_stream_kernel", 3: "ens_group_kernel", 4: "ens_mh_kernel"}.get(path.value)
+        self.last_path = {1: "stream", 3: "group", 4: "metropolis", 5: "hmc"}.get(path.value, "launch-per-half-step")
+        self.last_stream_kernel = {1: "ens_stream_kernel", 3: "ens_group_kernel", 4: "ens_mh_kernel", 5: "ens_hmc_kernel"}.get(path.value)
         variant = C.c_int(0)                                  # path 1: one workgroup per list position, or a pair of them
         _lib.lib().alabi_ens_stream_variant(self._ens, C.byref(variant))
         self.last_stream_variant = {0: "single", 1: "pair"}[variant.value] if path.value == 1 else None

@@ -270,7 +270,26 @@ int alabi_ens_set_logp_map(alabi_ens* ens, int kind);
  * results are the same -- after alabi_ens_set_stream(ens, 0), with ALABI_ENS_MH=0 in the environment, with workgroups of more
  * than 512 lanes (ALABI_ENS_THREADS=1024) or where its factors need more than 128 KB of LDS (more than four moves at d = 64).
  * ALABI_ENS_MH_CHUNK=k caps the steps of one launch at k; both variables are read at every alabi_ens_run.  Refused by the
- * sharded run. */
+ * sharded run.
+ * kind 6 HMCMove (Hamiltonian Monte Carlo on the closed-form gradient of the ensemble's log-probability; n_leapfrog = 1 is MALA):
+ * p0 = step size > 0, resolved by the caller; p1 = n_leapfrog + q / 512 with n_leapfrog in 1 ... 64 and q = ln jitter rounded to a
+ * multiple of 2^-36 (0: none; ln jitter < 512), so both parts come apart exactly.  The scale factor C (C C^T = cov, an estimate of
+ * the posterior covariance: the mass matrix is cov^-1) travels by alabi_ens_set_move_scale ahead of the table, as for kind 5, and
+ * alabi_ens_set_moves is ALABI_BAD_ARGUMENT for a kind-6 move whose slot has no factor, for a step size that is not positive and
+ * finite, for n_leapfrog outside 1 ... 64 and for a table that mixes kind 6 with another kind.  One step of walker x with
+ * lp = lnp(x), g = grad lnp(x), in whitened momentum: z0 ~ N(0, I); e = p0 f, f = 1 or exp(v), v ~ U(-ln jitter, ln jitter), ONE
+ * draw per step and ensemble; z = z0 + (e / 2) C^T g; n_leapfrog times q = q + e C z (from q = x), (lp_q, g_q) = lnp and its
+ * gradient at q, z = z + e C^T g_q (e / 2 the last time); accept iff lp_q - |z|^2 / 2 - lp + |z0|^2 / 2 > ln u' and q lies in the
+ * open box; NaN anywhere rejects.  Only the end point is tested against the box; in between the trajectory follows the GP mean's
+ * smooth extension (lnp there: GP mean through the folded scalers, the y map, the normal priors, no box gate).  Draws: Philox
+ * counter (step, global walker id, stream word S + 16 b) -- S = 11, b = k: the momentum normal z0_k at the walker (Box-Muller as
+ * stream 4); S = 12, b = 0: v = (2 u53(r0, r1) - 1) ln jitter at the ensemble's walker 0, not drawn without jitter; accept uniform
+ * and move choice are streams 2 and 3 as for every move; streams 0-10 keep their meaning.  Such a table runs on ens_hmc_kernel
+ * (path 5 of alabi_ens_last_path) and on nothing else: one workgroup per walker, every step of a chunk in one launch, any W >= 1
+ * and any n_ensembles; alabi_ens_set_stream does not move it, and alabi_ens_run is ALABI_BAD_ARGUMENT where the kernel cannot run
+ * (the factors [n][d, d | 1] and the gradient weights [Npad] exceed 128 KB of LDS together).  ALABI_ENS_HMC_CHUNK=k caps the steps
+ * of one launch at k, read at every alabi_ens_run; the chunk length changes no bit of the result.  The walker's logp is the
+ * caller's and is never recomputed.  alabi_ens_draw and the sharded run refuse such a table. */
 int alabi_ens_set_moves(alabi_ens* ens, int n, const int* kind, const double* cum, const double* p0, const double* p1);
 
 /* The scale factor of slot k (0 <= k < 8) of the move table, for the Gaussian move that the NEXT alabi_ens_set_moves puts there
@@ -282,6 +301,14 @@ int alabi_ens_set_move_scale(alabi_ens* ens, int k, const double* C /* host */, 
 /* ens_mh_kernel's last launch: out[4] = workgroup size, steps per launch, LDS bytes, 1 if the training set is streamed in tiles
  * (Npad / 2 exceeds the workgroup). */
 int alabi_ens_mh_plan(alabi_ens* ens, int* out /* host [4] */);
+/* ens_hmc_kernel's last launch: out[4] = workgroup size, steps per launch, LDS bytes, 1 if a lane takes more than one training
+ * point per pass (Npad exceeds the workgroup). */
+int alabi_ens_hmc_plan(alabi_ens* ens, int* out /* host [4] */);
+/* The ensemble's log-probability and its gradient at M arbitrary points, by the evaluation ens_hmc_kernel runs: coords [M, d],
+ * logp [M], grad [M, d] on the device.  lnp = GP mean through the folded affine scalers and the y map, plus the normal priors;
+ * grad = a T^T dmu (no map), ln10 lnp a T^T dmu (either map), minus (x_k - m_k) / s_k^2 per normal-prior coordinate.  Outside the
+ * open box logp is -inf and the gradient zero.  Works with any move table; ALABI_BAD_ARGUMENT where Npad doubles exceed 128 KB. */
+int alabi_ens_log_prob_grad(alabi_ens* ens, const double* coords, int M, double* logp, double* grad, void* stream);
 
 /* Enable / disable the persistent dataflow kernel for alabi_ens_run on this handle (default: enabled when the
  * ensemble fits one workgroup per CU).  Returns ALABI_BAD_ARGUMENT when enabling is impossible.
@@ -293,7 +320,8 @@ int alabi_ens_set_stream(alabi_ens* ens, int enabled);
 /* Which path the last alabi_ens_run took: 1 = persistent dataflow kernel with the training set in one workgroup's
  * registers (ens_stream_kernel: N <= 2048, small d), 3 = persistent group kernel (ens_group_kernel: training set
  * partitioned over groups of workgroups, kernel sums on the matrix cores; d <= 30), 4 = ens_mh_kernel (a table of Gaussian moves
- * alone: one workgroup per walker; alabi_ens_set_stream(ens, 0) sends such a table to path 0), 0 = one launch per half step. */
+ * alone: one workgroup per walker; alabi_ens_set_stream(ens, 0) sends such a table to path 0), 5 = ens_hmc_kernel (a table of HMC
+ * moves: one workgroup per walker; it has no other path), 0 = one launch per half step. */
 int alabi_ens_last_path(alabi_ens* ens, int* path /* host */);
 /* Which persistent kernel the last alabi_ens_run of path 1 launched: 0 = ens_stream_kernel (one workgroup per list position),
  * 1 = ens_pair_kernel (two per list position, which evaluate both outcomes of a pending update; chosen where 2 ceil(W/2) E
@@ -486,6 +514,16 @@ int alabi_ens_kde_singular(alabi_ens* ens, long long* count /* host */);
 int alabi_ens_step_with_randoms_gauss(alabi_ens* ens, double* coords, double* logp, const int* order, int n0, int k_move, double f,
                                       const int* coord, const double* z, const double* u_acc, long long* n_accept, void* stream);
 int alabi_ens_export_gauss_draws(alabi_ens* ens, double* f, int* coord, double* z, void* stream);
+
+/* Test entries of the HMC move (kind 6 of alabi_ens_set_moves; the table must be all HMC; all arrays on the device, keyed by
+ * WALKER id).
+ * alabi_ens_step_with_randoms_hmc (n_ensembles == 1): one step of move k_move of the table from injected draws -- e the step size
+ * actually used (jitter included), z [W, d] the momentum normals z0, u_acc [W] the accept uniform.
+ * alabi_ens_export_hmc_draws: the production draws of global step `step` -- move [E] int32 and e [E] per ensemble, z [E*W, d] and
+ * u_acc [E*W] (nullable) per walker. */
+int alabi_ens_step_with_randoms_hmc(alabi_ens* ens, double* coords, double* logp, int k_move, double e, const double* z,
+                                    const double* u_acc, long long* n_accept, void* stream);
+int alabi_ens_export_hmc_draws(alabi_ens* ens, long long step, int* move, double* e, double* z, double* u_acc, void* stream);
 
 /* Nested sampling (dynesty's NestedSampler / DynamicNestedSampler with sample="rwalk" as driven by
  * SurrogateModel.run_dynesty, alabi/core.py:2417-2787, likelihood = surrogate_log_likelihood core.py:1446-1508, prior =
