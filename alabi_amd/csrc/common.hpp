@@ -10,6 +10,7 @@
 #include "../../include/alabi_hip.h"
 #include "chol_tasks.hpp"
 #include "predict_plan.hpp"
+#include "ens_plan.hpp"
 
 #define ALABI_BLK 64  // Cholesky / TRSM block edge; matrices are padded to a multiple of it
 
@@ -187,6 +188,7 @@ struct WkInject {
 struct alabi_ens {
     alabi_gp* gp = nullptr;
     int W = 0, d = 0, E = 1;
+    int n_cu = 0;             // CUs of the device the handle was created on (device_cu_count), read by every rule of ens_plan.hip
     int threads = 1024;       // workgroup size of the half-step kernel
     double lp_scale = 1.0, lp_shift = 0.0;   // log-probability = lp_scale * GP mean + lp_shift inside the box (y scaler)
     // independent normal priors on selected coordinates (lnprior_normal): mean, 1 / std (0 = none), sum of the constants
@@ -242,7 +244,8 @@ struct alabi_ens {
     int hist_clean = 0;                  // rows 1..hist_clean hold the sentinel (left so by ens_hist_epilogue_kernel); rows beyond are filled before use
     int prop_clean = 0;                  // the same for prop, whose words the epilogue of a pair chunk resets beside those of hist
     int stream_grid = 0;                 // workgroups per ensemble of the persistent kernel
-    int last_path = 0;                   // 1 persistent kernel (ens_stream_kernel), 3 group kernel (ens_group_kernel), 0 one launch per half step
+    int last_path = 0;                   // route of the last alabi_ens_run (ens_plan.hpp: EnsRoute): 0 one launch per half step, 1 persistent kernel
+                                         // (ens_stream_kernel / ens_pair_kernel), 3 ens_group_kernel, 4 ens_mh_kernel, 5 ens_hmc_kernel
     int stream_ok = 0;                   // eligible: training set fits the lanes' registers, one workgroup per CU
     // pair variant of the persistent kernel (ens_pair_kernel)
     unsigned long long* prop = nullptr;  // [(chunk_cap+1)][E*W][d+2] published proposals, allocated on first use
@@ -346,7 +349,26 @@ int launch_utility_eval(int algo, const double* Xs, long long M, int d, const Di
                         double* u, hipStream_t s);
 int launch_argmin(const double* u, long long M, double* partial_val, long long* partial_idx,
                   int nblocks, hipStream_t s);
-// ensemble.hip
+// The shape of a handle for the rules of ens_plan.hip.  has_stream: the call was given a stream.
+inline EnsShape ens_shape(const alabi_ens* e, bool has_stream = true) {
+    EnsShape sh;
+    sh.W = e->W; sh.E = e->E; sh.d = e->d; sh.Npad = e->gp->Npad;
+    sh.generic = e->gp->kf.type != 0; sh.ymap = e->ymap;
+    sh.threads = e->threads; sh.chunk_cap = e->chunk_cap; sh.stream_grid = e->stream_grid;
+    sh.has_hist = e->hist && e->err;
+    sh.stream_ok = e->stream_ok; sh.mh_ok = e->mh_ok;
+    sh.has_de = e->has_de; sh.all_gauss = e->all_gauss; sh.all_hmc = e->all_hmc;
+    sh.factors = e->gauss_C != nullptr;
+    sh.n_moves = e->moves.n;
+    for (int k = 0; k < e->moves.n; ++k) { const int L = hmc_leapfrog_of(e->moves.p1[k]); if (L > sh.lmax) sh.lmax = L; }
+    sh.mh_lds = ens_mh_lds_bytes(e->moves.n, e->d);
+    const size_t hl = ens_hmc_lds_bytes(e->moves.n, e->d, e->gp->Npad);
+    sh.hmc_lds = hl > 0x7fffffffull ? 0x7fffffff : (int)hl;
+    sh.has_stream = has_stream;
+    return sh;
+}
+// ensemble.hip.  The entry points of ens_api.hip / ens_run.hip / ens_sharded.hip read ens_switches() once per call and hand it
+// down to the launchers that a switch concerns.
 int ens_se_prepare(alabi_gp* gp, hipStream_t s);     // Xc and ens_h of the current (inputs, alpha) for the squared-exponential half-step kernels
 struct HalfArgs {
     double* coords;              // [E*W,d] in/out
@@ -405,15 +427,13 @@ int launch_ens_prep_de(alabi_ens* e, const int* order, int n0, const int* j1, co
                        const double* u_acc, hipStream_t s);
 int launch_ens_prep_snooker(alabi_ens* e, const int* order, int n0, const int* j1, const int* j2, const int* j3, double gamma,
                             const double* u_acc, hipStream_t s);
-int launch_ens_half_args(alabi_ens* e, const HalfArgs& args, int nblocks, hipStream_t s);
+int launch_ens_half_args(alabi_ens* e, const HalfArgs& args, int nblocks, const EnsSwitches& sw, hipStream_t s);
 // ens_mh.hip: all steps of a chunk of an all-Gaussian set in one launch, one workgroup per walker
 int launch_ens_mh(alabi_ens* e, double* coords, double* logp, long long step0, long long done0, int K, int thin_by, double* chain,
                   double* chain_logp, long long* n_accept, hipStream_t s);
-int ens_mh_chunk(const alabi_ens* e);    // steps per launch (0: the set does not run on ens_mh_kernel)
 // ens_hmc.hip: all steps of a chunk of an all-HMC set in one launch, one workgroup per walker (inj_z: one step from injected draws)
 int launch_ens_hmc(alabi_ens* e, double* coords, double* logp, long long step0, long long done0, int K, int thin_by, double* chain,
                    double* chain_logp, long long* n_accept, int inj_k, double inj_e, const double* inj_z, const double* inj_u, hipStream_t s);
-int ens_hmc_chunk(const alabi_ens* e);   // steps per launch (0: the table does not run on ens_hmc_kernel)
 int launch_ens_lp_grad(alabi_ens* e, const double* pts, int M, double* logp, double* grad, hipStream_t s);
 int launch_ens_hmc_export(alabi_ens* e, long long step, int* move, double* e_out, double* z, double* u_acc, hipStream_t s);
 int launch_ens_lnprob(alabi_ens* e, const double* coords, int nwalkers, double* logp, int gate_box, hipStream_t s);
@@ -424,11 +444,14 @@ int launch_ens_advance(alabi_ens* e, long long n, hipStream_t s);
 // start state, new rows written to `out` (one row of d + 2 doubles per proposal); coords / logp are not modified
 int ens_sync_consts(alabi_ens* e, hipStream_t s);   // (inv_len, bounds, prior) on the device match the GP's hyper-parameters
 int alabi_ens_half_step_hist(alabi_ens* e, const double* coords, const double* logp, int t, int split, int part_begin, int part_end,
-                             const double* shist, double* out, hipStream_t s);
+                             const double* shist, double* out, const EnsSwitches& sw, hipStream_t s);
+// ens_api.hip: helpers of the handle that ens_run.hip uses
+bool ens_draw_ahead_ready(alabi_ens* e);            // second draw-buffer set, side stream and events exist (allocates on first use)
+DrawBuffers offset_draws(const DrawBuffers& b, size_t off);
+void set_move_args(const alabi_ens* e, HalfArgs& h, size_t t);   // further-partner arrays, move kind and pre-pass buffers of local step t
+HalfArgs base_args(alabi_ens* e, double* coords, double* logp);  // ens_run.hip
 // ens_stream.hip: the persistent kernel, the version history around a persistent launch (also the group kernel's)
-bool ens_stream_fits(const alabi_ens* e);
-int ens_stream_ppt(const alabi_ens* e);          // point pairs per compute lane of the persistent kernels (0: does not fit)
-int launch_ens_stream_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill_rows, hipStream_t s);
+int launch_ens_stream_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill_rows, const EnsSwitches& sw, hipStream_t s);
 int launch_ens_hist_fill(unsigned long long* rows, size_t words, hipStream_t s);
 int launch_ens_call_prologue(alabi_ens* e, const double* coords, const double* logp, const long long* n_accept, bool row0, hipStream_t s);
 int launch_ens_stream_epilogue(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
@@ -437,14 +460,14 @@ int launch_ens_hist_prologue(alabi_ens* e, double* coords, double* logp, int K, 
 int launch_ens_hist_epilogue(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
                              long long* n_accept, hipStream_t s);
 // ens_pair.hip: the pair variant of the persistent kernel (two workgroups per list position, both outcomes of a pending update)
-bool ens_pair_ready(alabi_ens* e);
+bool ens_pair_ready(alabi_ens* e, bool eligible);   // eligible: EnsRoute::pair of this call
 void ens_pair_release(alabi_ens* e);
-int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill_rows, int prop_fill_rows, bool placed, hipStream_t s);
-bool ens_place_ready(alabi_ens* e);      // ens_place.hip; the caller has checked ens_pair_ready
+int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill_rows, int prop_fill_rows, bool placed, const EnsSwitches& sw,
+                           hipStream_t s);
+bool ens_place_ready(alabi_ens* e, bool eligible);   // ens_place.hip; eligible: EnsRoute::place; the caller has checked ens_pair_ready
 int launch_ens_place(alabi_ens* e, DrawBuffers& set, int K, bool count, hipStream_t s);   // allocates set.packed_x / set.place on first use
 // ens_group.hip
-bool ens_group_fits(const alabi_ens* e);
-bool ens_group_buffers(alabi_ens* e, hipStream_t s);   // the group kernel's hand-off buffers exist (allocates on first use); false: take another path
+bool ens_group_buffers(alabi_ens* e, const EnsSwitches& sw, hipStream_t s);   // the group kernel's hand-off buffers exist (allocates on first use); false: take another path
 int launch_ens_group(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
-                     long long* n_accept, hipStream_t s);
+                     long long* n_accept, const EnsSwitches& sw, hipStream_t s);
 }  // namespace alabi

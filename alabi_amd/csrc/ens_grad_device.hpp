@@ -26,7 +26,7 @@ struct LpGradArgs {
     const double* alpha;         // [Npad], zero in the padding
     const double* consts;        // device [5][ALABI_MAX_DIM]: inv_len, lo, hi, prior mean, prior 1 / std
     int d, Npad, has_prior, ymap;
-    double prior_const, amp, mean;   // amp, mean: the affine map of the log-probability folded in (api.hip: base_args)
+    double prior_const, amp, mean;   // amp, mean: the affine map of the log-probability folded in (ens_run.hip: base_args)
     KernelFn kf;
 };
 
@@ -134,8 +134,7 @@ __device__ __forceinline__ double scale_transposed_times(const double* Cs, int d
 __device__ __forceinline__ double wave_total(double v) { return lane_bcast(wave_sum_dpp(v), 63); }
 
 // p1 of an HMC row of the move table: n_leapfrog + q / 512 with q = ln jitter rounded to a multiple of 2^-36 (0: no jitter; q < 512,
-// so both parts are exact in the double and come apart exactly).
-__host__ __device__ inline int hmc_leapfrog_of(double p1) { return (int)floor(p1); }
+// so both parts are exact in the double and come apart exactly).  hmc_leapfrog_of: ens_shared.hpp (the plan reads it too).
 __host__ __device__ inline double hmc_ln_jitter_of(double p1) { return (p1 - floor(p1)) * 512.0; }
 
 }  // namespace alabi

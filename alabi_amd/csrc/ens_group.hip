@@ -42,7 +42,7 @@ namespace alabi {
 
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 
-#define ALABI_GRP_NW 8                           // waves per workgroup (512 threads, two per SIMD)
+// ALABI_GRP_NW waves per workgroup (512 threads, two per SIMD): ens_shared.hpp
 // (Round 4, measured and not kept -- tools/experiments/ens_group_exp_table_2048.patch: a 2048-entry exp table (16 KB of LDS) with a
 // degree-3 polynomial, one fused multiply-add fewer per kernel evaluation (9 instead of 10 fp64 instructions, 1.93 ulp): C4 4.85 vs
 // 4.86 us per half step, C5 size 17.85 vs 17.97 -- the kernel sums are not bound by the count of vector instructions.)
@@ -131,24 +131,7 @@ ens_link_kernel(DrawBuffers b, int W, int n0, int NG, int QPAD, int G, int CW) {
     }
 }
 
-// LDS layout (units of 8 bytes), the same formula on the host.
-struct GroupLds {
-    int etab, xb, al, aop, wsum, rec, ctl, total;
-};
-__host__ __device__ inline GroupLds group_lds(int KS, int QPAD, int lds_tiles) {
-    const int S = 16 * lds_tiles;
-    GroupLds L;
-    int o = 0;
-    L.etab = o; o += 256;
-    L.xb = o; o += S * KS * 4;            // lds_tiles (= 8 waves x tiles per wave in LDS) x KS k-steps x 64 lanes
-    L.al = o; o += S;
-    L.aop = o; o += QPAD * KS * 4;
-    L.wsum = o; o += ALABI_GRP_NW * QPAD;
-    L.rec = o; o += 4 * QPAD * 6;         // ring of 4 half steps: 4 record words + 2 link words per proposal
-    L.ctl = o; o += 2;
-    L.total = o;
-    return L;
-}
+// LDS layout: GroupLds / group_lds in ens_shared.hpp, the same formula on the host (ens_plan.hip).
 
 #ifdef ALABI_GROUP_PROF
 // phase stamps (s_memrealtime, 100 MHz) of one workgroup, accumulated over the half steps of the last launch:
@@ -598,74 +581,18 @@ ens_group_kernel(GroupArgs p) {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Host side: the blocking for an ensemble, buffers, launch.
-struct GroupPlan {
-    int ok, KS, Q, QP, G, NG, RT, tpm, ltw;
-    size_t lds_bytes;
-};
-#define ALABI_GRP_RT 5                           // point tiles per wave held in registers by the G8 instantiations
-
+// (the blocking itself: GroupPlan / ens_group_plan in ens_plan.hip)
 #define ALABI_GRP_MAX_DEV 64                     // per-device caches (a process may touch several devices)
 static int group_device() {
     int dev = 0;
     (void)hipGetDevice(&dev);
     return dev >= 0 && dev < ALABI_GRP_MAX_DEV ? dev : 0;
 }
-static int group_n_cu() {
-    static int n_cu[ALABI_GRP_MAX_DEV] = {0};
-    const int dev = group_device();
-    if (n_cu[dev] == 0) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        n_cu[dev] = v;
-    }
-    return n_cu[dev];
-}
-
-// G members per group: 8 for d <= 14 (rows of <= 16 words); for wider rows 8 with four point tiles per wave in registers when the
-// rest of the slice then fits LDS, else 16; as many groups as the CUs allow, each with the smallest power-of-two number Q of
-// 16-proposal tiles that covers its share of a half step.
-static GroupPlan group_plan(const alabi_ens* e) {
-    const alabi_gp* gp = e->gp;
-    const int d = e->d;
-    GroupPlan none{};
-    if (d + 2 > 32 || e->ymap != 0 || e->W < 2) return none;
-    const int n_cu = group_n_cu();
-    if (e->E > n_cu) return none;
-    const int KS = (d + 2 + 3) / 4;
-    const int n0 = (e->W + 1) / 2;
-    const int tiles = gp->Npad / 16;
-    const char* g16 = getenv("ALABI_ENS_GROUP_G16");          // tests: the 16-member blocking where 8 members would be chosen
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        GroupPlan pl{};
-        const bool wide = KS > 4;
-        if (attempt == 0 && g16 && g16[0] == '1') continue;  // attempt 0: the instantiation with register-resident point tiles
-        const int G = (wide && attempt == 1) ? 16 : 8;
-        const int RT = (attempt == 0) ? ALABI_GRP_RT : 0;
-        const int ng_max = n_cu / e->E / G;
-        if (ng_max < 1) continue;
-        int Q = 1;
-        while (Q < 8 && (n0 + 16 * Q - 1) / (16 * Q) > ng_max) Q *= 2;
-        if ((n0 + 16 * Q - 1) / (16 * Q) > ng_max) continue;
-        if (wide && Q > 4) continue;                         // passes of the row phase: 16 Q proposals / (8 waves x 2) <= 4
-        if (!wide && RT > 0 && Q > 2) continue;              // (register budget of the narrow-row instantiations with many proposal tiles)
-        pl.KS = KS; pl.Q = Q; pl.QP = 16 * Q; pl.G = G; pl.NG = (n0 + pl.QP - 1) / pl.QP; pl.RT = RT;
-        pl.tpm = (tiles + G - 1) / G;
-        const int tpw = (pl.tpm + ALABI_GRP_NW - 1) / ALABI_GRP_NW;
-        pl.ltw = tpw > RT ? tpw - RT : 0;
-        pl.lds_bytes = (size_t)group_lds(KS, pl.QP, ALABI_GRP_NW * pl.ltw).total * 8;
-        pl.ok = pl.lds_bytes <= 160 * 1024 - 512;
-        if (pl.ok) return pl;
-    }
-    return none;
-}
-
-bool ens_group_fits(const alabi_ens* e) { return e->hist && e->err && group_plan(e).ok; }
-
 // The hand-off buffers of the group kernel (partial sums, candidate rows) for a full chunk: allocated on first use, ~0.3 GB at C4
 // and ~0.9 GB at the C5 size.  false = the blocking does not fit the 32-bit word offsets of the link records or the memory is not
 // there -- alabi_ens_run then takes another path (ens_stream_kernel or one launch per half step) instead of failing.
-bool ens_group_buffers(alabi_ens* e, hipStream_t s) {
-    const GroupPlan pl = group_plan(e);
+bool ens_group_buffers(alabi_ens* e, const EnsSwitches& sw, hipStream_t s) {
+    const GroupPlan pl = ens_group_plan(ens_shape(e), e->n_cu, sw);
     if (!pl.ok) return false;
     const int n0 = (e->W + 1) / 2, CW = 2 * e->d + 4;
     const size_t part_per_half = (size_t)e->E * pl.NG * pl.QP * pl.G, cand_per_half = (size_t)e->E * n0 * CW;
@@ -728,15 +655,15 @@ static int group_launch(const GroupArgs& a, const GroupPlan& pl, int E, hipStrea
 }
 
 int launch_ens_group(alabi_ens* e, double* coords, double* logp, int K, int thin_by, double* chain, double* chain_logp,
-                     long long* n_accept, hipStream_t s) {
+                     long long* n_accept, const EnsSwitches& sw, hipStream_t s) {
     alabi_gp* gp = e->gp;
-    const GroupPlan pl = group_plan(e);
+    const GroupPlan pl = ens_group_plan(ens_shape(e), e->n_cu, sw);
     if (!pl.ok) return ALABI_BAD_ARGUMENT;
     int st = ensure_xa(gp, s);
     if (st != ALABI_OK) return st;
     const int n0 = (e->W + 1) / 2, CW = 2 * e->d + 4;
     const size_t part_per_half = (size_t)e->E * pl.NG * pl.QP * pl.G, cand_per_half = (size_t)e->E * n0 * CW;
-    if (!ens_group_buffers(e, s)) return ALABI_BAD_ARGUMENT;   // (alabi_ens_run asks before it chooses this kernel)
+    if (!ens_group_buffers(e, sw, s)) return ALABI_BAD_ARGUMENT;   // (alabi_ens_run asks before it chooses this kernel)
     hipLaunchKernelGGL(ens_group_fill_kernel, dim3(2048), dim3(256), 0, s, e->part, 2 * K * part_per_half);
     hipLaunchKernelGGL(ens_group_fill_kernel, dim3(2048), dim3(256), 0, s, e->cand, 2 * K * cand_per_half);
     hipLaunchKernelGGL(ens_link_kernel, dim3(K, e->E), dim3(256), 0, s, e->draws, e->W, n0, pl.NG, pl.QP, pl.G, CW);
@@ -748,8 +675,7 @@ int launch_ens_group(alabi_ens* e, double* coords, double* logp, int K, int thin
     a.K = K; a.W = e->W; a.n0 = n0; a.d = e->d; a.Npad = gp->Npad;
     a.NG = pl.NG; a.QP = pl.QP; a.tpm = pl.tpm; a.ltw = pl.ltw;
     a.xcd_map = 1;                                           // measured at C4: 6.23 us per half step with it, 6.58 without (first version)
-    a.spin_limit = 1 << 20;
-    if (const char* env = getenv("ALABI_ENS_SPIN_LIMIT")) { const int v = atoi(env); if (v > 0) a.spin_limit = v - 1; }   // tests: force a time-out (1: the first miss)
+    a.spin_limit = ens_spin_limit_group(sw);                 // (ALABI_ENS_SPIN_LIMIT: tests force a time-out; 1: the first miss)
     a.has_prior = e->has_prior; a.prior_const = e->prior_const;
     a.poll_delay = 6;                                        // ~0.16 us: measured optimum at C4 (5.13 vs 5.21 us per half step at 0, 5.5 at 20)
     a.amp = e->lp_scale * exp(gp->log_amp); a.mean = fma(e->lp_scale, gp->mean, e->lp_shift); a.kf = gp->kf;

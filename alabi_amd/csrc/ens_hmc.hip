@@ -35,7 +35,7 @@
 
 namespace alabi {
 
-#define ALABI_HMC_MAX_LDS (128 * 1024)
+// ALABI_HMC_MAX_LDS: ens_shared.hpp
 #define ALABI_HMC_STREAM_Z 11u
 #define ALABI_HMC_STREAM_JITTER 12u
 
@@ -219,39 +219,9 @@ __global__ void ens_hmc_export_kernel(unsigned long long seed, long long step, i
     }
 }
 
-static size_t hmc_lds_bytes(const alabi_ens* e) {
-    return ((size_t)e->moves.n * e->d * (e->d | 1) + (size_t)e->gp->Npad) * sizeof(double);
-}
+static size_t hmc_lds_bytes(const alabi_ens* e) { return ens_hmc_lds_bytes(e->moves.n, e->d, e->gp->Npad); }
 static int hmc_threads(const alabi_ens* e) { return e->threads > 512 ? 512 : e->threads; }
-
-// Steps per launch, 0 where the table does not run on ens_hmc_kernel (not all HMC, no factors, a dimension without a bucket, more
-// than 128 KB of LDS).  As ens_mh_chunk: a launch is kept to about a tenth of a second -- a value evaluation estimated at 3 us per
-// tile of the training set, a value-and-gradient evaluation at three of those, n_leapfrog (the table's largest) of them per step,
-// times the rounds in which the E W workgroups find room -- between 16 and 16384 steps.  The step counters travel by value and
-// the gradient at the walker is a function of the walker alone: the chunk length changes no result.
-int ens_hmc_chunk(const alabi_ens* e) {
-    if (!e->all_hmc || !e->gauss_C || dim_bucket(e->d) < 0 || hmc_lds_bytes(e) > ALABI_HMC_MAX_LDS) return 0;
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-    }
-    int Lmax = 1;
-    for (int k = 0; k < e->moves.n; ++k) { const int L = hmc_leapfrog_of(e->moves.p1[k]); if (L > Lmax) Lmax = L; }
-    const int T = hmc_threads(e);
-    const long long total = (long long)e->W * e->E;
-    const long long rounds = (total + 2LL * n_cu - 1) / (2LL * n_cu);
-    const long long tiles = ((e->gp->Npad >> 1) + T - 1) / T;
-    long long chunk = 100000 / (9 * rounds * (tiles > 0 ? tiles : 1) * Lmax);
-    if (chunk > 16384) chunk = 16384;
-    if (chunk < 16) chunk = 16;
-    if (const char* env = getenv("ALABI_ENS_HMC_CHUNK")) {            // a shorter chunk (tests of the chunk boundary at few steps)
-        const long long v = atoll(env);
-        if (v >= 1 && v < chunk) chunk = v;
-    }
-    return (int)chunk;
-}
+// (steps per launch: ens_hmc_chunk in ens_plan.hip)
 
 static LpGradArgs lp_grad_args(const alabi_ens* e) {
     const alabi_gp* gp = e->gp;

@@ -24,7 +24,7 @@
 
 namespace alabi {
 
-#define ALABI_MH_MAX_LDS (128 * 1024)
+// ALABI_MH_MAX_LDS: ens_shared.hpp
 
 struct MhArgs {
     double* coords;              // [E*W, d] in/out
@@ -159,33 +159,7 @@ ens_mh_kernel(MhArgs p) {
     }
 }
 
-static int mh_lds_bytes(const alabi_ens* e) { return e->moves.n * e->d * e->d * (int)sizeof(double); }
-
-// Steps per launch, 0 where the set does not run on this kernel.  A launch is kept to about a tenth of a second so that other
-// work on the device gets its turn: a step is estimated at 3 us per tile of the training set (measured: 3.1 us for the resident
-// share of ns_walk_kernel at N = 2000) times the rounds in which the E W workgroups find room (two per CU at a time), and the
-// chunk is 1e5 us over that, between 64 and 16384 steps.  The step counters travel by value: the chunk length changes no result.
-int ens_mh_chunk(const alabi_ens* e) {
-    if (!e->all_gauss || !e->gauss_C || e->threads > 512 || dim_bucket(e->d) < 0 || mh_lds_bytes(e) > ALABI_MH_MAX_LDS) return 0;
-    if (const char* env = getenv("ALABI_ENS_MH")) { if (env[0] == '0') return 0; }
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-    }
-    const long long total = (long long)e->W * e->E;
-    const long long rounds = (total + 2LL * n_cu - 1) / (2LL * n_cu);
-    const long long tiles = ((e->gp->Npad >> 1) + e->threads - 1) / e->threads;
-    long long chunk = 100000 / (3 * rounds * (tiles > 0 ? tiles : 1));
-    if (chunk > 16384) chunk = 16384;
-    if (chunk < 64) chunk = 64;
-    if (const char* env = getenv("ALABI_ENS_MH_CHUNK")) {             // a shorter chunk (tests of the chunk boundary at few steps)
-        const long long v = atoll(env);
-        if (v >= 1 && v < chunk) chunk = v;
-    }
-    return (int)chunk;
-}
+// (steps per launch: ens_mh_chunk in ens_plan.hip)
 
 template <int D, bool GENERIC>
 static int launch_mh_inst(const MhArgs& a, int grid, int T, size_t lds, hipStream_t s) {
@@ -217,7 +191,7 @@ int launch_ens_mh(alabi_ens* e, double* coords, double* logp, long long step0, l
     a.mt = e->moves;
     if (!a.Xsrc || !a.Asrc || (se && !a.centre)) return ALABI_NOT_COMPUTED;
     const int grid = e->W * e->E, T = e->threads;
-    const size_t lds = (size_t)mh_lds_bytes(e);
+    const size_t lds = (size_t)ens_mh_lds_bytes(e->moves.n, e->d);
     e->mh_plan[0] = T; e->mh_plan[1] = K; e->mh_plan[2] = (int)lds; e->mh_plan[3] = (gp->Npad >> 1) > T ? 1 : 0;
     int st = ALABI_OK;
     ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(gp->kf.type, st = (launch_mh_inst<D, GENERIC>(a, grid, T, lds, s))));

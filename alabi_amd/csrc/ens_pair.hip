@@ -377,18 +377,14 @@ extern "C" int alabi_debug_pair_prof(long long* out) {
 }
 #endif
 
-// The pair variant can run this handle: prop allocated (lazily, here), one workgroup per CU for 2 ceil(W/2) E workgroups, not
-// switched off by ALABI_ENS_PAIR=0 or by an earlier time-out of this handle.  The caller has checked ens_stream_fits and the moves.
-bool ens_pair_ready(alabi_ens* e) {
+// The pair variant can run this handle: the route finds it eligible (ens_plan.hip: one workgroup per CU for 2 ceil(W/2) E
+// workgroups, not switched off by ALABI_ENS_PAIR=0), prop allocated (lazily, here), no earlier time-out of this handle.  Decided at
+// the first call that asks and kept.  The caller has checked that the route is the persistent kernel.
+bool ens_pair_ready(alabi_ens* e, bool eligible) {
     if (e->pair_state < 0) return false;
     if (e->pair_state == 0) {
         e->pair_state = -1;
-        const char* env = getenv("ALABI_ENS_PAIR");
-        if (env && env[0] == '0') return false;
-        int dev = 0, n_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-        const long long wgs = 2LL * ((e->W + 1) / 2) * e->E;
-        if (e->d < 1 || wgs > n_cu) return false;
+        if (!eligible) return false;
         const size_t WT = (size_t)e->W * e->E, row = e->d + 2;
         const size_t words = ((size_t)e->chunk_cap + 1) * WT * row;
         if (hipMalloc(&e->prop, words * sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); e->prop = nullptr; return false; }
@@ -408,7 +404,8 @@ void ens_pair_release(alabi_ens* e) {
 // One chunk of K steps on the pair kernel; the arguments of launch_ens_stream_kernel, and prop_fill_rows > 0: rows
 // 1..prop_fill_rows of prop cannot be trusted to hold the sentinel and are refilled (the chunk's epilogue puts it back, as in hist).
 // placed: ens_place_kernel has run on this chunk's records; the kernel then reads rec.packed_x under the XCD map.
-int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill_rows, int prop_fill_rows, bool placed, hipStream_t s) {
+int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill_rows, int prop_fill_rows, bool placed, const EnsSwitches& sw,
+                           hipStream_t s) {
     const int n0 = (e->W + 1) / 2;
     const size_t WT = (size_t)e->W * e->E, row = e->d + 2;
     int st;
@@ -421,7 +418,7 @@ int launch_ens_pair_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill
         e->boundary_stats[2]++;
     }
     PairArgs a{};
-    a.s = ens_stream_args(e, rec, K);
+    a.s = ens_stream_args(e, rec, K, sw);
     a.prop = e->prop; a.stats = e->pair_stats;
     if (placed) { a.s.rec.packed = rec.packed_x; a.xmap = 1; }
     e->last_path = 1;

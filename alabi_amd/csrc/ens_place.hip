@@ -129,14 +129,13 @@ ens_place_kernel(DrawBuffers b, int K, int W, int n0, unsigned long long* stats)
     }
 }
 
-// Placement is on for this handle: both halves of a step have n0 items, n0 % 8 == 0 (whole classes), at most 128 pairs, not
-// switched off by ALABI_ENS_PLACE=0.  The caller has checked ens_pair_ready.
-bool ens_place_ready(alabi_ens* e) {
+// Placement is on for this handle: the route finds it eligible (ens_plan.hip: both halves of a step have n0 items, n0 % 8 == 0,
+// at most 128 pairs, not switched off by ALABI_ENS_PLACE=0) and the counters could be had.  Decided at the first call that asks
+// and kept.  The caller has checked ens_pair_ready.
+bool ens_place_ready(alabi_ens* e, bool eligible) {
     if (e->place_state == 0) {
         e->place_state = -1;
-        const char* env = getenv("ALABI_ENS_PLACE");
-        const int n0 = (e->W + 1) / 2;
-        if ((env && env[0] == '0') || e->W != 2 * n0 || n0 % 8 != 0 || n0 > 128) return false;
+        if (!eligible) return false;
         if (hipMalloc(&e->place_stats, 2 * sizeof(unsigned long long)) != hipSuccess ||
             hipMemset(e->place_stats, 0, 2 * sizeof(unsigned long long)) != hipSuccess) {
             (void)hipGetLastError();

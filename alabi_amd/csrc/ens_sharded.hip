@@ -219,7 +219,7 @@ int alabi_dist_comm_destroy(alabi_comm* c) {
 // the enqueues of one chunk of K steps whose records are in the draw buffers: link records, 2 K x (half-step kernel on this
 // rank's slice + in-place all-gather), the gather of chain / counters / final state
 static int enqueue_sharded_chunk(alabi_ens* e, alabi_comm* c, double* coords, double* logp, int K, int thin_by, long long done0,
-                                 double* chain, double* chain_logp, long long* n_accept, hipStream_t s) {
+                                 double* chain, double* chain_logp, long long* n_accept, const EnsSwitches& sw, hipStream_t s) {
     const int W = e->W, d = e->d, n0 = (W + 1) / 2, row = d + 2;
     const int per = (n0 + c->nranks - 1) / c->nranks;
     const size_t block = (size_t)c->nranks * per * row;                 // doubles per half step
@@ -233,7 +233,7 @@ static int enqueue_sharded_chunk(alabi_ens* e, alabi_comm* c, double* coords, do
             slice_bounds(nS, c->nranks, c->rank, &b, &en);
             double* blk = c->shist + (size_t)(2 * t + split) * block;
             double* mine = blk + (size_t)c->rank * per * row;
-            if (en > b && (st = alabi_ens_half_step_hist(e, coords, logp, t, split, b, en, c->shist, mine, s)) != ALABI_OK) return st;
+            if (en > b && (st = alabi_ens_half_step_hist(e, coords, logp, t, split, b, en, c->shist, mine, sw, s)) != ALABI_OK) return st;
             if ((c->nranks > 1 || c->nccl) && (st = all_gather(c, mine, blk, (size_t)per * row, s)) != ALABI_OK) return st;
         }
     hipLaunchKernelGGL(shard_chain_kernel, dim3((unsigned)(((long long)K * W + 255) / 256)), dim3(256), 0, s, e->draws.pos_of, c->shist, K, W,
@@ -263,8 +263,8 @@ static int run_sharded(alabi_ens* e, alabi_comm* c, double* coords, double* logp
     // the null stream, which cannot capture): replaying the ~4000 nodes of a chunk is SLOWER than enqueueing them -- one rank, C3
     // 6.27 vs 5.83 us per half step, C4 11.7 vs 10.5-11.2 (profiles/r04_sharded_one_rank.txt): the half-step kernel runs 5-10 us, so
     // the host is never the bound and the graph only adds its per-node cost.
-    const char* genv = getenv("ALABI_ENS_SHARD_GRAPH");
-    const bool want_graph = s != nullptr && !c->fn && genv && genv[0] == '1';
+    const EnsSwitches sw = ens_switches();
+    const bool want_graph = s != nullptr && !c->fn && ens_shard_graph_on(sw);
     if ((st = ens_sync_consts(e, s)) != ALABI_OK) return st;      // (a host copy + synchronisation: not inside a capture)
     long long done = 0;
     while (done < nsteps) {
@@ -282,7 +282,7 @@ static int run_sharded(alabi_ens* e, alabi_comm* c, double* coords, double* logp
                 if (c->graph) { (void)hipGraphExecDestroy(c->graph); c->graph = nullptr; }
                 hipGraph_t g = nullptr;
                 ALABI_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                st = enqueue_sharded_chunk(e, c, coords, logp, K, 1, 0, nullptr, nullptr, nullptr, s);
+                st = enqueue_sharded_chunk(e, c, coords, logp, K, 1, 0, nullptr, nullptr, nullptr, sw, s);
                 const hipError_t ce = hipStreamEndCapture(s, &g);
                 if (st != ALABI_OK || ce != hipSuccess) {
                     if (g) (void)hipGraphDestroy(g);
@@ -308,7 +308,7 @@ static int run_sharded(alabi_ens* e, alabi_comm* c, double* coords, double* logp
                 continue;
             }
         }
-        if ((st = enqueue_sharded_chunk(e, c, coords, logp, K, thin_by, done, chain, chain_logp, n_accept, s)) != ALABI_OK) return st;
+        if ((st = enqueue_sharded_chunk(e, c, coords, logp, K, thin_by, done, chain, chain_logp, n_accept, sw, s)) != ALABI_OK) return st;
         c->n_eager++;
         done += K;
     }

@@ -1,5 +1,5 @@
 // Persistent ensemble kernel ("stream" kernel) for gfx950: ens_stream_kernel, the version history's prologue and epilogue
-// kernels, the fit rule and the launches.  The draws, the records and the launch-per-half-step kernels are in ensemble.hip, the
+// kernels and the launches (the fit rule: ens_stream_ppt in ens_plan.hip).  The draws, the records and the launch-per-half-step kernels are in ensemble.hip, the
 // pair variant of this kernel in ens_pair.hip, what the two share in ens_stream.hpp.
 #include <cstdlib>
 #include "ens_stream.hpp"
@@ -342,17 +342,6 @@ ens_hist_epilogue_kernel(unsigned long long* __restrict__ hist, int K, int WT, i
     if (k == d + 1 && n_accept && nacc) atomicAdd(n_accept + w, nacc);
 }
 
-// Point pairs per compute lane of the persistent kernels for this handle, 0: they do not fit (ens_stream_max_db).
-int ens_stream_ppt(const alabi_ens* e) {
-    const int T = e->threads, half = e->gp->Npad / 2, db = dim_bucket(e->d);
-    if (e->d > 61 || db < 0) return 0;
-    if (e->ymap != 0) return 0;   // non-affine y scalers (pow) run on the launch-per-half-step path: this kernel has no VGPR to spare
-    const int ppt = (half + T - 1) / T;
-    return db <= ens_stream_max_db(T, ppt, e->gp->kf.type != 0) ? ppt : 0;
-}
-
-bool ens_stream_fits(const alabi_ens* e) { return ens_stream_ppt(e) > 0; }
-
 // Version history around a persistent launch of K steps: rows 1..K <- sentinel (`fill`: when the rows are polled), row 0 <- (coords, logp) before it;
 // (coords, logp) <- row K, chain / counters <- rows 1..K after it.  Shared by ens_stream_kernel and ens_group_kernel.
 int launch_ens_hist_prologue(alabi_ens* e, double* coords, double* logp, int K, bool fill, hipStream_t s) {
@@ -392,14 +381,14 @@ int launch_ens_call_prologue(alabi_ens* e, const double* coords, const double* l
     return ALABI_OK;
 }
 
-StreamArgs ens_stream_args(alabi_ens* e, const DrawBuffers& rec, int K) {
+StreamArgs ens_stream_args(alabi_ens* e, const DrawBuffers& rec, int K, const EnsSwitches& sw) {
     alabi_gp* gp = e->gp;
     StreamArgs a{};
     a.hist = e->hist; a.err = e->err; a.rec = rec; a.consts = e->consts;
     const bool se = gp->kf.type == 0;                 // squared exponential: centred inputs and h (se_pair_terms), built by ens_se_prepare
     a.Xt = se ? gp->Xc : gp->Xt; a.alpha = se ? gp->ens_h : gp->alpha; a.centre = gp->xa_centre;
-    a.K = K; a.W = e->W; a.n0 = (e->W + 1) / 2; a.d = e->d; a.Npad = gp->Npad; a.spin_limit = 1 << 20;
-    if (const char* env = getenv("ALABI_ENS_SPIN_LIMIT")) { const int v = atoi(env); if (v > 0) a.spin_limit = v; }   // tests: force a time-out
+    a.K = K; a.W = e->W; a.n0 = (e->W + 1) / 2; a.d = e->d; a.Npad = gp->Npad;
+    a.spin_limit = ens_spin_limit_stream(sw);         // (ALABI_ENS_SPIN_LIMIT: tests force a time-out)
     a.amp = e->lp_scale * exp(gp->log_amp); a.mean = fma(e->lp_scale, gp->mean, e->lp_shift); a.kf = gp->kf;
     a.has_prior = e->has_prior; a.prior_const = e->prior_const;
     return a;
@@ -408,14 +397,14 @@ StreamArgs ens_stream_args(alabi_ens* e, const DrawBuffers& rec, int K) {
 // One chunk of K steps on the persistent kernel, proposal records from `rec`.  Row 0 of the history holds the walkers (from
 // ens_call_prologue_kernel or the previous chunk's epilogue); fill_rows > 0: rows 1..fill_rows cannot be trusted to hold the
 // sentinel (first use of the handle, after a time-out or the group kernel) and are refilled.
-int launch_ens_stream_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill_rows, hipStream_t s) {
+int launch_ens_stream_kernel(alabi_ens* e, const DrawBuffers& rec, int K, int fill_rows, const EnsSwitches& sw, hipStream_t s) {
     int st;
     if (fill_rows > 0) {
         const size_t WT = (size_t)e->W * e->E, row = e->d + 2;
         if ((st = launch_ens_hist_fill(e->hist + WT * row, (size_t)fill_rows * WT * row, s)) != ALABI_OK) return st;
         e->boundary_stats[3]++;
     }
-    const StreamArgs a = ens_stream_args(e, rec, K);
+    const StreamArgs a = ens_stream_args(e, rec, K, sw);
     e->last_path = 1;
     st = ens_stream_dispatch(e, [&](auto D, auto PPT, auto TMAX, auto GENERIC) {
         hipLaunchKernelGGL((ens_stream_kernel<D(), PPT(), TMAX(), GENERIC()>), dim3(e->stream_grid, e->E), dim3(TMAX()), 0, s, a);

@@ -24,7 +24,7 @@ struct StreamArgs {
     KernelFn kf;
 };
 
-StreamArgs ens_stream_args(alabi_ens* e, const DrawBuffers& rec, int K);   // ens_stream.hip: the arguments of one chunk of K steps
+StreamArgs ens_stream_args(alabi_ens* e, const DrawBuffers& rec, int K, const EnsSwitches& sw);   // ens_stream.hip: the arguments of one chunk of K steps
 
 __device__ inline unsigned long long ld_sc1(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -198,15 +198,8 @@ __device__ __forceinline__ void stream_compute_loop(const StreamArgs& p, const S
 }
 
 // ---- launch table (host) ----------------------------------------------------------------------------------------------
-// T compute lanes (+ the hand-off wave and the record wave), PPT point pairs per lane.  The fit rule: the largest dimension
-// bucket of a (T, PPT, kernel family) row that compiles without VGPR spills (hipcc -Rpass-analysis=kernel-resource-usage;
-// 256 VGPRs at 384 threads, 168 at 640); 0: no such row.  ens_stream_ppt and the dispatch both read it, so an instantiation
-// that can never be chosen is not compiled.
-constexpr int ens_stream_max_db(int T, int ppt, bool generic) {
-    if (T == 512) return ppt == 1 ? (generic ? 12 : 16) : ppt == 2 ? (generic ? 6 : 10) : 0;
-    if (T == 256) return ppt == 1 ? 16 : ppt == 2 ? (generic ? 12 : 16) : ppt == 3 ? (generic ? 8 : 12) : ppt == 4 ? (generic ? 6 : 10) : 0;
-    return 0;
-}
+// The fit rule of a (T, PPT, kernel family) row is ens_stream_max_db (ens_shared.hpp): ens_stream_ppt and the dispatch both read
+// it, so an instantiation that can never be chosen is not compiled.
 
 // One (T, PPT) row of the table: dimension bucket x kernel family.  launch(D, PPT, TMAX, GENERIC) gets the instantiation's
 // template arguments as integral constants.
@@ -220,13 +213,13 @@ int ens_stream_dispatch_row(int db, int kernel_type, Launch& launch) {
     return ALABI_OK;
 }
 
-// Calls `launch` for the instantiation of this handle; ALABI_BAD_ARGUMENT when the handle does not fit (ens_stream_ppt(e) == 0).
+// Calls `launch` for the instantiation of this handle; ALABI_BAD_ARGUMENT when the handle does not fit (ens_stream_ppt == 0).
 // Lanes x pairs-per-lane cover Npad/2 point pairs; the launch-per-half-step kernel's lane -> point map (and so its summation
 // order) is reproduced exactly because both run with e->threads compute lanes.
 template <class Launch>
 int ens_stream_dispatch(const alabi_ens* e, Launch launch) {
     const int db = dim_bucket(e->d), kt = e->gp->kf.type;
-    const int T = e->threads, ppt = ens_stream_ppt(e);
+    const int T = e->threads, ppt = ens_stream_ppt(ens_shape(e));
     if (T == 256 && ppt == 1) return ens_stream_dispatch_row<256, 1>(db, kt, launch);
     if (T == 256 && ppt == 2) return ens_stream_dispatch_row<256, 2>(db, kt, launch);
     if (T == 256 && ppt == 3) return ens_stream_dispatch_row<256, 3>(db, kt, launch);

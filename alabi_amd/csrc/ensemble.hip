@@ -1280,28 +1280,14 @@ int launch_ens_kde_prepass(alabi_ens* e, const HalfArgs& args, hipStream_t s) {
     return ALABI_OK;
 }
 
-int launch_ens_half_args(alabi_ens* e, const HalfArgs& args_in, int nblocks, hipStream_t s) {
+int launch_ens_half_args(alabi_ens* e, const HalfArgs& args_in, int nblocks, const EnsSwitches& sw, hipStream_t s) {
     if (nblocks <= 0) return ALABI_OK;
     const int db = dim_bucket(e->d);
     const int threads = e->threads;
     HalfArgs args = args_in;
     args.count = nblocks;
     // more proposals than CUs: NP per workgroup share one pass over the training set (same block size: same bits)
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-    }
-    const long long total = (long long)nblocks * e->E;
-    const char* env = getenv("ALABI_ENS_MULTI");
-    int np = 1;
-    if (threads <= 512 && db <= 24 && !(env && env[0] == '0') && !args.shist) {
-        if (total > 3LL * n_cu && db <= 16) np = 4; else if (total > n_cu) np = 2;   // q[NP][D] lives in registers
-        if (env && env[0] == '4' && db <= 16) np = 4;
-        if (env && env[0] == '2') np = 2;
-        if (env && env[0] == '1') np = 1;
-    }
+    const int np = ens_half_np(threads, e->d, (long long)nblocks * e->E, args.shist != nullptr, e->n_cu, sw);
     if (args.mvkind) {                                // a set with a walk or KDE move: one proposal per workgroup
         if (args.shist || !args.cw2 || !args.cw3 || !args.mvpar) return ALABI_BAD_ARGUMENT;
         ALABI_DISPATCH_DIM(db, ALABI_DISPATCH_KERNEL(e->gp->kf.type, hipLaunchKernelGGL((ens_half_wk_kernel<D, GENERIC>), dim3(nblocks, e->E), dim3(threads), 0, s, args)));

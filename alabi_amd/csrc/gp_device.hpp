@@ -4,14 +4,7 @@
 
 namespace alabi {
 
-// Compile-time dimension buckets: a GP of dimension d runs the instantiation for the
-// smallest bucket >= d; Xt rows beyond d are zero and so contribute nothing to r^2.
-__host__ __device__ inline int dim_bucket(int d) {
-    const int b[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 24, 32, 48, 64};
-    for (int i = 0; i < 15; ++i)
-        if (d <= b[i]) return b[i];
-    return -1;
-}
+// dim_bucket(d), the compile-time dimension buckets: ens_shared.hpp (through common.hpp), shared with the host-only ensemble plan.
 
 // ALABI_DISPATCH_DIM16: the buckets up to 16 only, for kernels that keep whole proposals per lane in registers (the persistent
 // ensemble kernels, four proposals per workgroup in ens_half_multi_kernel); a larger bucket is ALABI_BAD_ARGUMENT.
