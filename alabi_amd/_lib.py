@@ -78,6 +78,9 @@ SIGNATURES = {
     "alabi_ens_mh_plan": (_i, [_vp, _pi]),
     "alabi_ens_hmc_plan": (_i, [_vp, _pi]),
     "alabi_ens_log_prob_grad": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "alabi_ens_maximize": (_i, [_vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "alabi_ens_log_prob_hessian": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "alabi_ens_map_plan": (_i, [_vp, _pi]),
     "alabi_ens_set_stream": (_i, [_vp, _i]),
     "alabi_ens_last_path": (_i, [_vp, _pi]),
     "alabi_ens_stream_variant": (_i, [_vp, _pi]),

@@ -125,6 +125,8 @@ class SurrogateModel(object):
     def __getstate__(self):
         state = self.__dict__.copy()
         state["pool"] = None
+        state.pop("_map_sampler", None)                       # find_map(method="bfgs-gpu")'s device handle and its plan (closures):
+        state.pop("_map_plan", None)                          # working state of one call, rebuilt by the next
         if state.get("_emcee_full_src") is not None:          # the saved model carries the array itself, as the reference's does
             state["_emcee_full"] = self.emcee_samples_full
             state["_emcee_full_src"] = None
@@ -865,7 +867,17 @@ class SurrogateModel(object):
         -lnprob from the best points of a batched scan of the posterior (surrogate evaluated on the GPU, 4096 prior
         draws) and from ``theta0`` if given.  Sets ``self.map_theta`` / ``self.map_lnprob`` and returns the walker start
         positions run_emcee passes to the sampler: [nwalkers, ndim] in a ball of 1e-3 of the box width around the MAP,
-        clipped into the open box."""
+        clipped into the open box.
+
+        ``method="bfgs-gpu"`` (opt-in) runs every restart at once on the device instead: the starts -- the best ``nRestarts``
+        points of the same scan, and ``theta0`` -- go to ``EnsembleSampler.maximize``, a projected BFGS ascent on the fused
+        log-probability's closed-form gradient, one workgroup per start and all of it in one launch; the best converged result
+        is taken (the best of any status, with a warning, if none converged).  It needs the fused log-probability of
+        ``run_emcee`` (surrogate likelihood, box or shipped normal prior, foldable scalers) and raises ``ValueError`` naming what
+        does not fuse otherwise.  ``options``: ``maxiter`` (200) and ``gtol`` (1e-8).  Sets ``map_status`` (0 converged, 1
+        ``maxiter``, 2 no ascent) and ``map_evaluations`` (log-probability evaluations over all starts) as well."""
+        if str(method).lower() == "bfgs-gpu":
+            return self._find_map_gpu(theta0, prior_fn, nRestarts, options)
         prior_fn = prior_fn if prior_fn is not None else getattr(self, "prior_fn", None)
         if prior_fn is None:
             prior_fn = partial(ut.lnprior_uniform, bounds=self.bounds)
@@ -905,6 +917,99 @@ class SurrogateModel(object):
         nw = int(getattr(self, "nwalkers", 10 * self.ndim))
         ball = best_x + 1e-3 * (hi - lo) * self._rng.standard_normal((nw, self.ndim))
         return np.minimum(np.maximum(ball, lo + 1e-9 * (hi - lo)), hi - 1e-9 * (hi - lo))
+
+    def _find_map_gpu(self, theta0, prior_fn, nRestarts, options):
+        """find_map(method="bfgs-gpu"): see there.  Leaves the sampler and its plan in ``_map_sampler`` / ``_map_plan`` and the
+        maximum in the sampler's coordinates in ``_map_coords`` for ``laplace_approximation``."""
+        if not hasattr(self, "gp"):
+            raise NameError("GP has not been trained")
+        like_fn = getattr(self, "like_fn", None) or self.surrogate_log_likelihood
+        like_host = None if like_fn == self.surrogate_log_likelihood else like_fn
+        prior_fn = prior_fn if prior_fn is not None else getattr(self, "prior_fn", None)
+        plan = post.plan_ensemble(like_host, self.surrogate_log_likelihood, prior_fn, self.bounds,
+                                  getattr(self, "theta_scaler", None), getattr(self, "y_scaler", None), getattr(self, "_y", None))
+        if not plan.fused:
+            why = []
+            if plan.host_like is not None:
+                why.append("the likelihood runs on the host (like_fn is not the surrogate, or a scaler cannot be folded into the kernels)")
+            if plan.host_prior is not None:
+                why.append("prior_fn is a host callable (only the box and the shipped lnprior_normal fuse)")
+            raise ValueError('find_map(method="bfgs-gpu") needs the fused log-probability: host callables (prior_fn / like_fn) have no '
+                             "gradient -- " + "; ".join(why))
+        opts = dict(options or {})
+        lo, hi = self.bounds[:, 0].astype(float), self.bounds[:, 1].astype(float)
+        cand = ut.prior_sampler(bounds=self.bounds, nsample=4096, sampler="uniform", random_state=self._seed())
+        post_c = np.asarray(self.surrogate_log_likelihood(cand), dtype=np.float64).reshape(-1)
+        if prior_fn is not None and plan.normal_prior is not None:   # (the box prior is 0 at every draw)
+            post_c = post_c + post.host_rows(prior_fn, (1, -1))(cand)
+        post_c = np.where(np.isfinite(post_c), post_c, -np.inf)
+        starts = [cand[i] for i in np.argsort(-post_c)[:max(int(nRestarts), 1)]]
+        if theta0 is not None:
+            starts.insert(0, np.asarray(theta0, dtype=np.float64).reshape(-1))
+        gp_obj, y_obj = self._handle_owner()
+        sampler = EnsembleSampler(2, self.ndim, gp_obj, y_obj, plan.box, logp_affine=plan.logp_affine, normal_prior=plan.normal_prior,
+                                  logp_map=plan.logp_map, live_dangerously=True, seed=0)
+        res = sampler.maximize(np.asarray(starts) * plan.t_mult + plan.t_add, maxiter=int(opts.get("maxiter", 200)),
+                               gtol=float(opts.get("gtol", 1e-8)))
+        status, lp, x = res.status.cpu().numpy(), res.log_prob.cpu().numpy(), res.x.cpu().numpy()
+        usable = np.isfinite(lp) & (status != 3)
+        if not usable.any():
+            raise RuntimeError('find_map(method="bfgs-gpu"): no start lies inside the prior box with a finite log-probability')
+        pick = usable & (status == 0)
+        if not pick.any():
+            warnings.warn('find_map(method="bfgs-gpu"): no restart converged (statuses %s); taking the best point reached'
+                          % sorted(set(status[usable].tolist())), UserWarning, stacklevel=3)
+            pick = usable
+        best = int(np.flatnonzero(pick)[np.argmax(lp[pick])])
+        self._map_sampler, self._map_plan, self._map_coords = sampler, plan, x[best].copy()
+        self.map_theta = np.asarray(plan.to_theta(x[best][None, :]), dtype=np.float64).reshape(-1)
+        self.map_lnprob = float(lp[best])
+        self.map_status = int(status[best])
+        self.map_evaluations = int(res.evaluations.sum().item())
+        nw = int(getattr(self, "nwalkers", 10 * self.ndim))
+        ball = self.map_theta + 1e-3 * (hi - lo) * self._rng.standard_normal((nw, self.ndim))
+        return np.minimum(np.maximum(ball, lo + 1e-9 * (hi - lo)), hi - 1e-9 * (hi - lo))
+
+    def laplace_approximation(self, theta0=None, nRestarts=64, prior_fn=None):
+        """The Laplace approximation of the surrogate posterior: ``find_map(method="bfgs-gpu")`` from ``nRestarts`` starts (and
+        ``theta0``), then ONE closed-form Hessian of the fused log-probability at the maximum
+        (``EnsembleSampler.log_prob_hessian``), then ``alabi_amd.laplace``.  Sets
+
+        * ``map_theta``, ``map_lnprob``, ``map_status``, ``map_evaluations`` as ``find_map`` does;
+        * ``map_hessian`` [d, d] in theta, ``map_cov`` = (-map_hessian)^-1 in theta, and ``map_cov_scaled``, the same covariance
+          in the sampler's coordinates -- the form ``GaussianMove`` / ``HMCMove`` take:
+          ``sm.run_emcee(sampler_kwargs={"moves": HMCMove(sm.map_cov_scaled, n_leapfrog=4)})``;
+        * ``laplace_logz`` = lp + (d / 2) ln 2 pi - ln det(-H) / 2 - sum ln width over the coordinates under the uniform prior
+          (``lnprior_uniform`` is 0 in the box, ``run_dynesty``'s prior transform is normalised): a cross-check of
+          ``run_dynesty``'s log Z in a few milliseconds (NOTES.md "MAP and Laplace");
+        * ``map_on_bound``, a boolean mask of the coordinates the maximum holds on a wall of the box.
+
+        Where a coordinate is held on a bound, or -H is not positive definite there, the covariances and ``laplace_logz`` are
+        None and a ``UserWarning`` says which: a Gaussian at a wall is not a Laplace approximation.  Returns ``laplace_logz``."""
+        from . import laplace as lap
+        self.find_map(theta0=theta0, prior_fn=prior_fn, method="bfgs-gpu", nRestarts=nRestarts)
+        plan, xc = self._map_plan, self._map_coords
+        H = self._map_sampler.log_prob_hessian(xc[None, :])[0].cpu().numpy()
+        w = plan.box[:, 1] - plan.box[:, 0]
+        self.map_on_bound = (xc <= plan.box[:, 0] + 1e-9 * w) | (xc >= plan.box[:, 1] - 1e-9 * w)
+        self.map_hessian = lap.hessian_to_theta(H, plan.t_mult)
+        self.map_cov = self.map_cov_scaled = self.laplace_logz = None
+        if self.map_on_bound.any():
+            warnings.warn("laplace_approximation: the maximum holds coordinate(s) %s on a wall of the prior box; no covariance and no "
+                          "evidence estimate are set" % np.flatnonzero(self.map_on_bound).tolist(), UserWarning, stacklevel=2)
+            return None
+        cov = lap.laplace_covariance(H)
+        if cov is None:
+            warnings.warn("laplace_approximation: minus the Hessian at the point found is not positive definite (status %d: not a "
+                          "maximum); no covariance and no evidence estimate are set" % self.map_status, UserWarning, stacklevel=2)
+            return None
+        uniform = np.ones(self.ndim, dtype=bool) if plan.normal_prior is None else \
+            ~(np.isfinite(plan.normal_prior[0]) & np.isfinite(plan.normal_prior[1]) & (plan.normal_prior[1] > 0))
+        widths = (plan.theta_box[:, 1] - plan.theta_box[:, 0])[uniform]
+        self.map_cov_scaled = cov
+        self.map_cov = lap.covariance_to_theta(cov, plan.t_mult)
+        self.laplace_logz = lap.laplace_log_evidence(self.map_lnprob, self.map_hessian, widths)
+        return self.laplace_logz
 
     # ---- what run_emcee and run_dynesty share
     def _handle_owner(self):
@@ -960,7 +1065,8 @@ class SurrogateModel(object):
         complementary half: a KDE move hops between modes in one step, ``[(KDEMove(), 0.3), (DEMove(), 0.7)]``, and wants many
         walkers per dimension (``nwalkers >= 2 ndim + 2`` at the least; a warning below ``8 (ndim + 1)``).
         ``alabi_amd.moves.GaussianMove(cov, mode="vector", factor=None)`` is emcee's Gaussian Metropolis move -- ``cov`` a scalar, a
-        vector of variances or a matrix, e.g. the inverse Hessian at ``find_map()`` or the covariance of an earlier chain: a set of
+        vector of variances or a matrix, e.g. ``map_cov_scaled`` of ``laplace_approximation()`` (the inverse Hessian at the MAP:
+        ``run_emcee(sampler_kwargs={"moves": HMCMove(sm.map_cov_scaled, n_leapfrog=4)})``) or the covariance of an earlier chain: a set of
         Gaussian moves alone runs the walkers as independent random-walk Metropolis chains on the surrogate, any number of them,
         all steps of a call in one kernel launch; it mixes with the red-blue moves too.  ``alabi_amd.moves.MHMove(fn)`` and any
         object with a callable ``get_proposal`` (emcee's own ``MHMove`` / ``GaussianMove``) run a Python proposal function on a

@@ -435,6 +435,11 @@ int launch_ens_mh(alabi_ens* e, double* coords, double* logp, long long step0, l
 int launch_ens_hmc(alabi_ens* e, double* coords, double* logp, long long step0, long long done0, int K, int thin_by, double* chain,
                    double* chain_logp, long long* n_accept, int inj_k, double inj_e, const double* inj_z, const double* inj_u, hipStream_t s);
 int launch_ens_lp_grad(alabi_ens* e, const double* pts, int M, double* logp, double* grad, hipStream_t s);
+// ens_map.hip: the multi-start BFGS ascent, the Hessian at arbitrary points, and the launch shape of the former
+int launch_ens_map(alabi_ens* e, const double* starts, int S, int maxiter, double gtol, double* x_out, double* lp_out, int* iters_out,
+                   int* status_out, double* gnorm_out, double* trace, int ntrace, hipStream_t s);
+int launch_ens_lp_hess(alabi_ens* e, const double* pts, int M, double* hess, hipStream_t s);
+void ens_map_plan(const alabi_ens* e, int* out);
 int launch_ens_hmc_export(alabi_ens* e, long long step, int* move, double* e_out, double* z, double* u_acc, hipStream_t s);
 int launch_ens_lnprob(alabi_ens* e, const double* coords, int nwalkers, double* logp, int gate_box, hipStream_t s);
 int launch_ens_propose(alabi_ens* e, const HalfArgs& args, int nblocks, int gate_box, double* q, double* like, hipStream_t s);

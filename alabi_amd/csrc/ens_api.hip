@@ -701,6 +701,33 @@ int alabi_ens_log_prob_grad(alabi_ens* e, const double* coords, int M, double* l
     return launch_ens_lp_grad(e, coords, M, logp, grad, as_stream(stream));
 }
 
+int alabi_ens_maximize(alabi_ens* e, const double* starts, int S, int maxiter, double gtol, double* x_out, double* lp_out, int* iters_out,
+                       int* status_out, double* gnorm_out, double* trace, int ntrace, void* stream) {
+    if (!e || !starts || !x_out || !lp_out || !iters_out || !status_out || !gnorm_out || S < 0 || maxiter < 0 || ntrace < 0 ||
+        (ntrace > 0 && !trace) || !(gtol >= 0.0))
+        return ALABI_BAD_ARGUMENT;
+    if (!e->gp->computed || !e->gp->has_alpha) return ALABI_NOT_COMPUTED;
+    if (S == 0) return ALABI_OK;
+    const int st = ens_sync_consts(e, as_stream(stream));
+    if (st != ALABI_OK) return st;
+    return launch_ens_map(e, starts, S, maxiter, gtol, x_out, lp_out, iters_out, status_out, gnorm_out, trace, ntrace, as_stream(stream));
+}
+
+int alabi_ens_log_prob_hessian(alabi_ens* e, const double* coords, int M, double* hess, void* stream) {
+    if (!e || !coords || !hess || M < 0) return ALABI_BAD_ARGUMENT;
+    if (!e->gp->computed || !e->gp->has_alpha) return ALABI_NOT_COMPUTED;
+    if (M == 0) return ALABI_OK;
+    const int st = ens_sync_consts(e, as_stream(stream));
+    if (st != ALABI_OK) return st;
+    return launch_ens_lp_hess(e, coords, M, hess, as_stream(stream));
+}
+
+int alabi_ens_map_plan(alabi_ens* e, int* out) {
+    if (!e || !out) return ALABI_BAD_ARGUMENT;
+    ens_map_plan(e, out);
+    return ALABI_OK;
+}
+
 int alabi_ens_step_with_randoms_hmc(alabi_ens* e, double* coords, double* logp, int k_move, double eps, const double* z,
                                     const double* u_acc, long long* n_accept, void* stream) {
     if (!e || !coords || !logp || !z || !u_acc || e->E != 1 || !e->all_hmc) return ALABI_BAD_ARGUMENT;

@@ -23,7 +23,7 @@ from .gp import HipGP, _dev, _to_dev
 from .mcmc_utils import integrated_time
 from .moves import parse_moves
 
-__all__ = ["EnsembleSampler", "State"]
+__all__ = ["EnsembleSampler", "MaximizeResult", "State"]
 
 
 class State:
@@ -35,6 +35,15 @@ class State:
 
     def __iter__(self):
         return iter((self.coords, self.log_prob, self.random_state))
+
+
+class MaximizeResult:
+    """What ``EnsembleSampler.maximize`` returns: device tensors ``x``, ``log_prob``, ``iterations``, ``evaluations``, ``status``,
+    ``grad_norm`` and, with ``trace=n``, ``trace`` -- the raw [S, n, 4] doubles of ``alabi_ens_maximize`` (lp, step length, the held
+    set's bits, update flag; NaN rows beyond the last iteration) -- and its columns decoded: ``trace_log_prob``, ``trace_step``,
+    ``trace_held`` (int64), ``trace_updated`` (bool)."""
+    x = log_prob = iterations = evaluations = status = grad_norm = None
+    trace = trace_log_prob = trace_step = trace_held = trace_updated = None
 
 
 class EnsembleSampler:
@@ -277,6 +286,63 @@ class EnsembleSampler:
         _lib.check(_lib.lib().alabi_ens_log_prob_grad(self._ens, _lib.ptr(c), int(c.shape[0]), _lib.ptr(lp), _lib.ptr(g),
                                                       _lib.current_stream()), "alabi_ens_log_prob_grad")
         return lp, g
+
+    def maximize(self, starts, maxiter=200, gtol=1e-8, trace=0):
+        """Maxima of the fused log-probability inside the box from ``starts`` [S, d] (any S >= 1, no relation to ``nwalkers``):
+        a projected BFGS ascent on the closed-form gradient, one workgroup per start and every iteration of every search in ONE
+        launch (``ens_map_kernel``).  Returns a ``MaximizeResult`` of device tensors: ``x`` [S, d], ``log_prob`` [S],
+        ``iterations`` / ``evaluations`` / ``status`` [S] (int32) and ``grad_norm`` [S], the largest component of the projected
+        gradient.  status 0: ``grad_norm <= gtol``; 1: ``maxiter`` iterations taken; 2: no ascent at the smallest step (the best
+        point is kept); 3: the start lies outside the open box or the log-probability is not finite there (NaN outputs).  The
+        search runs on the box shrunk by 1e-9 of its width; a coordinate held on a bound ends exactly on that shrunk wall.  The
+        result is never worse than the start.  ``trace=n`` adds ``trace`` (the raw [S, n, 4] record) and its columns ``trace_log_prob``, ``trace_step`` [S, n] (NaN beyond the last
+        iteration), ``trace_held`` (int64 bit masks) and ``trace_updated`` (bool) of the first n accepted iterations.  Needs the
+        fused log-probability (no host callables)."""
+        if self.generic:
+            raise ValueError("maximize needs the fused log-probability: host callables (prior_fn / like_fn) have no gradient")
+        self._ensure_ens()
+        c = _to_dev(starts, 2)
+        if c.ndim != 2 or c.shape[1] != self.ndim or c.shape[0] < 1:
+            raise ValueError("starts must have shape (S, ndim) with S >= 1")
+        maxiter, ntrace, gtol = int(maxiter), int(trace), float(gtol)
+        if maxiter < 0 or ntrace < 0 or not gtol >= 0.0:
+            raise ValueError("maxiter and trace must not be negative, nor gtol")
+        S, dev = int(c.shape[0]), c.device
+        res = MaximizeResult()
+        res.x = torch.empty((S, self.ndim), dtype=torch.float64, device=dev)
+        res.log_prob = torch.empty(S, dtype=torch.float64, device=dev)
+        res.grad_norm = torch.empty(S, dtype=torch.float64, device=dev)
+        res.status = torch.empty(S, dtype=torch.int32, device=dev)
+        iters = torch.empty((S, 2), dtype=torch.int32, device=dev)
+        tr = torch.full((S, ntrace, 4), float("nan"), dtype=torch.float64, device=dev) if ntrace else None
+        _lib.check(_lib.lib().alabi_ens_maximize(self._ens, _lib.ptr(c), S, maxiter, gtol, _lib.ptr(res.x), _lib.ptr(res.log_prob),
+                                                 _lib.ptr(iters), _lib.ptr(res.status), _lib.ptr(res.grad_norm), _lib.ptr(tr), ntrace,
+                                                 _lib.current_stream()), "alabi_ens_maximize")
+        res.iterations, res.evaluations = iters[:, 0], iters[:, 1]
+        if ntrace:
+            res.trace = tr
+            done = ~torch.isnan(tr[:, :, 1])
+            res.trace_log_prob, res.trace_step = tr[:, :, 0], tr[:, :, 1]
+            res.trace_held = torch.where(done, tr[:, :, 2].contiguous().view(torch.int64), torch.zeros_like(done, dtype=torch.int64))
+            res.trace_updated = done & (tr[:, :, 3] == 1.0)
+        return res
+
+    def log_prob_hessian(self, coords):
+        """The Hessian of the fused log-probability with respect to the coordinates at arbitrary points [M, d]: a device tensor
+        [M, d, d], symmetric to the bit, closed form (the second derivatives of the GP mean through the scalers, the y map's
+        chain rule, minus 1 / s_k^2 per normal-prior coordinate); NaN outside the open box.  At ``maximize``'s optimum, minus its
+        inverse is the covariance an ``HMCMove`` or ``GaussianMove`` wants (``alabi_amd.laplace``).  Needs the fused
+        log-probability (no host callables)."""
+        if self.generic:
+            raise ValueError("log_prob_hessian needs the fused log-probability: host callables (prior_fn / like_fn) have no gradient")
+        self._ensure_ens()
+        c = _to_dev(coords, 2)
+        if c.ndim != 2 or c.shape[1] != self.ndim:
+            raise ValueError("coords must have shape (M, ndim)")
+        H = torch.empty((c.shape[0], self.ndim, self.ndim), dtype=torch.float64, device=c.device)
+        _lib.check(_lib.lib().alabi_ens_log_prob_hessian(self._ens, _lib.ptr(c), int(c.shape[0]), _lib.ptr(H), _lib.current_stream()),
+                   "alabi_ens_log_prob_hessian")
+        return H
 
     def surrogate(self, points):
         """y_scaler^-1(GP mean) at arbitrary points [M,d] in the sampler's coordinates: no box gate, no prior (device tensor)."""

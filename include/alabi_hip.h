@@ -309,6 +309,28 @@ int alabi_ens_hmc_plan(alabi_ens* ens, int* out /* host [4] */);
  * grad = a T^T dmu (no map), ln10 lnp a T^T dmu (either map), minus (x_k - m_k) / s_k^2 per normal-prior coordinate.  Outside the
  * open box logp is -inf and the gradient zero.  Works with any move table; ALABI_BAD_ARGUMENT where Npad doubles exceed 128 KB. */
 int alabi_ens_log_prob_grad(alabi_ens* ens, const double* coords, int M, double* logp, double* grad, void* stream);
+/* The maximum of the same log-probability inside the box, by a projected BFGS ascent from S starts at once (ens_map_kernel: one
+ * workgroup per start, every iteration in one launch; tests/map_numpy.py states the rule).  starts [S, d], x_out [S, d], lp_out [S],
+ * iters_out [S, 2] (iterations, evaluations; int), status_out [S] (int), gnorm_out [S] on the device.  status: 0 = the projected
+ * gradient's largest component is at most gtol, 1 = maxiter iterations taken, 2 = no ascent at the smallest step (the best point is
+ * kept), 3 = the start lies outside the open box or the log-probability is not finite there (x, lp and gnorm are NaN).  The result
+ * is never worse than the start.  The search runs on the box shrunk by 1e-9 of its width, so a coordinate held on a bound sits at
+ * lo + 1e-9 (hi - lo) or hi - 1e-9 (hi - lo).  trace (or null with ntrace = 0): device [S, ntrace, 4] doubles, per accepted
+ * iteration the new lp, the step length t, the held set (the bits of a 64-bit integer, bit k = coordinate k) and 1 where the BFGS
+ * update was applied; rows beyond the last iteration are left as they were.  The bits of a start's result do not depend on S or
+ * on its place in the batch.  Works with any move table; ALABI_BAD_ARGUMENT where B [d][d | 1] and the gradient weights [Npad]
+ * exceed 128 KB of LDS together. */
+int alabi_ens_maximize(alabi_ens* ens, const double* starts, int S, int maxiter, double gtol, double* x_out, double* lp_out,
+                       int* iters_out /* [S, 2] */, int* status_out, double* gnorm_out, double* trace /* or null */, int ntrace,
+                       void* stream);
+/* The Hessian of the same log-probability with respect to the coordinates at M arbitrary points: coords [M, d], hess_out [M, d, d]
+ * on the device, symmetric to the bit.  No map: a T^T (d2 mu) T; either y map L = -+10^Mu: ln10 L d2 Mu + ln10^2 L dMu dMu^T; minus
+ * 1 / s_k^2 on the diagonal per normal-prior coordinate.  Outside the open box every entry is NaN.  ALABI_BAD_ARGUMENT where
+ * 2 Npad doubles exceed 128 KB. */
+int alabi_ens_log_prob_hessian(alabi_ens* ens, const double* coords, int M, double* hess_out, void* stream);
+/* How alabi_ens_maximize launches on this handle: out[4] = workgroup size, LDS bytes, 1 if a lane takes more than one training
+ * point per pass (Npad exceeds the workgroup), dimension bucket. */
+int alabi_ens_map_plan(alabi_ens* ens, int* out /* host [4] */);
 
 /* Enable / disable the persistent dataflow kernel for alabi_ens_run on this handle (default: enabled when the
  * ensemble fits one workgroup per CU).  Returns ALABI_BAD_ARGUMENT when enabling is impossible.
