@@ -77,6 +77,7 @@ SIGNATURES = {
     "alabi_ens_set_move_scale": (_i, [_vp, _i, _pd, _i]),
     "alabi_ens_mh_plan": (_i, [_vp, _pi]),
     "alabi_ens_hmc_plan": (_i, [_vp, _pi]),
+    "alabi_ens_hmc_adapt": (_i, [_vp, _vp, _vp, _ll, _ll, _i, _vp, _pd, _vp, _vp, _vp, _vp, _vp]),
     "alabi_ens_log_prob_grad": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "alabi_ens_maximize": (_i, [_vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "alabi_ens_log_prob_hessian": (_i, [_vp, _vp, _i, _vp, _vp]),

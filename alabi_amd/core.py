@@ -1073,7 +1073,10 @@ class SurrogateModel(object):
         host-driven loop, one round trip per step: slow by nature.  ``alabi_amd.moves.HMCMove(cov, step_size=None, n_leapfrog=8,
         jitter=None)`` runs Hamiltonian Monte Carlo on the surrogate's closed-form gradient (``n_leapfrog=1``: MALA), alone or as
         a mixture of HMC moves; ``cov`` is given in the sampler's (scaled) coordinates like a ``GaussianMove``'s; it needs the
-        surrogate likelihood with a prior that fuses (none, uniform or normal) and cannot be sharded.  Any other emcee move raises ``NotImplementedError`` -- in
+        surrogate likelihood with a prior that fuses (none, uniform or normal) and cannot be sharded.  With a single ``HMCMove``,
+        ``sampler_kwargs["hmc_warmup"] = n`` (optionally ``"hmc_target_accept"``, default 0.8, and ``"hmc_metric"``: "diag", "dense" or
+        None) runs ``EnsembleSampler.tune_hmc`` for n steps in front of the run -- Stan-style warm-up of the step size and the mass
+        matrix; what it found is ``sm.hmc_tuning`` --; with any other move set these keys raise ``ValueError``.  Any other emcee move raises ``NotImplementedError`` -- in
         particular emcee's ``DESnookerMove``, whose arithmetic is not the published rule; none of ``DEMove``, ``SnookerMove``,
         ``WalkMove``, ``KDEMove``, ``GaussianMove``, ``MHMove`` can be combined with ``"shard": True``.
 
@@ -1091,6 +1094,16 @@ class SurrogateModel(object):
         rank, world = adist.world_info()
         kw = dict(sampler_kwargs)
         move_set = parse_moves(kw.get("moves"), self.ndim)       # unsupported moves fail here, before anything runs
+        # HMC warm-up (EnsembleSampler.tune_hmc) in front of every run: popped here, the sampler's constructor does not know them
+        hmc_warmup = kw.pop("hmc_warmup", None)
+        hmc_tune_kw = {name: kw.pop(key) for key, name in (("hmc_target_accept", "target_accept"), ("hmc_metric", "metric")) if key in kw}
+        if hmc_warmup is not None or hmc_tune_kw:
+            if move_set is None or len(move_set) != 1 or not move_set.all_hmc:
+                raise ValueError('sampler_kwargs "hmc_warmup", "hmc_target_accept" and "hmc_metric" need sampler_kwargs["moves"] to be '
+                                 'a single HMCMove: its step size and mass matrix are what the warm-up adapts')
+            if hmc_warmup is None or int(hmc_warmup) < 1:
+                raise ValueError('sampler_kwargs["hmc_warmup"] must be a positive number of warm-up steps')
+            hmc_warmup = int(hmc_warmup)
         if kw.get("shard", False) and move_set is not None and (move_set.has_gauss or move_set.all_mh):
             raise ValueError('sampler_kwargs={"shard": True} cannot run a GaussianMove or an MHMove: a Metropolis proposal reads no '
                              'other walker, so there is nothing to exchange -- run replicas instead')
@@ -1152,6 +1165,9 @@ class SurrogateModel(object):
             t0 = time.time()
             self.emcee_sampler = EnsembleSampler(self.nwalkers, self.ndim, gp_obj, y_obj, plan.box, logp_affine=plan.logp_affine,
                                                  normal_prior=plan.normal_prior, logp_map=plan.logp_map, **sampler_extra, **kw)
+            if hmc_warmup is not None:
+                start = self.emcee_sampler.tune_hmc(start, nwarmup=hmc_warmup, **hmc_tune_kw).coords
+                self.hmc_tuning = self.emcee_sampler.hmc_tuning
             self.emcee_sampler.run_mcmc(start, self.nsteps, **run_kwargs)
             self.emcee_runtime += time.time() - t0
             self.iburn, self.ithin = mcmc_utils.estimate_burnin(self.emcee_sampler, verbose=self.verbose)

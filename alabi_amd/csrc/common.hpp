@@ -435,6 +435,9 @@ int launch_ens_mh(alabi_ens* e, double* coords, double* logp, long long step0, l
 int launch_ens_hmc(alabi_ens* e, double* coords, double* logp, long long step0, long long done0, int K, int thin_by, double* chain,
                    double* chain_logp, long long* n_accept, int inj_k, double inj_e, const double* inj_z, const double* inj_u, hipStream_t s);
 int launch_ens_lp_grad(alabi_ens* e, const double* pts, int M, double* logp, double* grad, hipStream_t s);
+// ens_hmc_adapt.hip: the same with a dual-averaged step size per walker (da_state [E*W, 5] in/out; par: delta, gamma, t0, kappa)
+int launch_ens_hmc_adapt(alabi_ens* e, double* coords, double* logp, long long step0, long long done0, int K, int thin_by, double* chain,
+                         double* chain_logp, long long* n_accept, double* da_state, const double* par, double* accept_stat, hipStream_t s);
 // ens_map.hip: the multi-start BFGS ascent, the Hessian at arbitrary points, and the launch shape of the former
 int launch_ens_map(alabi_ens* e, const double* starts, int S, int maxiter, double gtol, double* x_out, double* lp_out, int* iters_out,
                    int* status_out, double* gnorm_out, double* trace, int ntrace, hipStream_t s);

@@ -27,146 +27,27 @@
 // families), two waves per SIMD throughout (__launch_bounds__(512) leaves 256 VGPRs per lane):
 //   D = 1: 180 / 0 | 187 / 0     D = 5: 182 / 0 | 196 / 0     D = 10: 187 / 0 | 206 / 0     D = 16: 199 / 0 | 218 / 0
 //   D = 20: 207 / 0 | 226 / 0    D = 24: 215 / 0 | 234 / 0    D = 32: 231 / 0 | 250 / 0
-//   D = 48: 256 / 28 | 255 / 84  D = 64: 256 / 112 | 256 / 208
+//   D = 48: 256 / 28 | 256 / 84  D = 64: 256 / 112 | 256 / 208
 // The floor of about 180 is the move table (8 rows by value) and the unrolled point loop, not the dimension; the query point costs
 // 2 D of them, and from the D = 48 bucket on a part of it lives in scratch.
+// (With the body in ens_hmc_device.hpp every figure is what it was before, but D = 48 of the other families: 255 -> 256 VGPRs.)
+// adapt: ens_hmc_adapt_kernel (ens_hmc_adapt.hip), the same body with the dual-averaging state in wave 0: 12 to 14 VGPRs more,
+//   D = 1: 194 / 0 | 200 / 0     D = 5: 194 / 0 | 209 / 0     D = 10: 200 / 0 | 219 / 0     D = 16: 212 / 0 | 231 / 0
+//   D = 20: 220 / 0 | 239 / 0    D = 24: 228 / 0 | 247 / 0    D = 32: 244 / 0 | 255 / 36
+//   D = 48: 256 / 52 | 256 / 136 D = 64: 256 / 168 | 256 / 280
 #include <cstdlib>
-#include "ens_grad_device.hpp"
+#include "ens_hmc_device.hpp"
 
 namespace alabi {
 
-// ALABI_HMC_MAX_LDS: ens_shared.hpp
-#define ALABI_HMC_STREAM_Z 11u
-#define ALABI_HMC_STREAM_JITTER 12u
-
-struct HmcArgs {
-    double* coords;              // [E*W, d] in/out
-    double* logp;                // [E*W] in/out
-    LpGradArgs lg;
-    double* chain;               // [nstore, E*W, d] or null
-    double* chain_logp;          // [nstore, E*W] or null
-    long long* n_accept;         // [E*W] or null
-    const double* scale_C;       // [n][d, d] scale factors of the table's moves
-    long long step0;             // global step index of local step 0
-    long long done0;             // steps of the call done before this launch (chain slots)
-    unsigned long long seed;
-    int K, W, thin_by, scale_diag;
-    MoveTable mt;
-    // test entry (alabi_ens_step_with_randoms_hmc): inj_z set -> one step of move inj_k with e = inj_e, z0 = inj_z [W, d], u' = inj_u [W]
-    const double* inj_z;
-    const double* inj_u;
-    double inj_e;
-    int inj_k;
-};
-
-// the step's move, as ens_draw_kernel chooses it (the table is read with constant indices only); every thread of the workgroup
-__device__ __forceinline__ int hmc_step_move(const MoveTable& mt, uint32_t s_lo, uint32_t s_hi, uint32_t g0, uint32_t k0, uint32_t k1) {
-    int mi = 0;
-    if (mt.n > 1) {
-        uint32_t r[4];
-        philox4x32_10(s_lo, s_hi, g0, 3u, k0, k1, r);
-        const double um = u53(r[0], r[1]);
-#pragma unroll
-        for (int k = 0; k < ALABI_MAX_MOVES; ++k) mi += (k < mt.n && mt.cum[k] <= um) ? 1 : 0;
-        if (mi > mt.n - 1) mi = mt.n - 1;
-    }
-    return mi;
-}
-__device__ __forceinline__ void hmc_move_params(const MoveTable& mt, int mi, double& mp0, double& mp1) {
-    mp0 = mt.p0[0]; mp1 = mt.p1[0];
-#pragma unroll
-    for (int k = 1; k < ALABI_MAX_MOVES; ++k)
-        if (k == mi) { mp0 = mt.p0[k]; mp1 = mt.p1[k]; }
-}
-// e = step_size f of the step (one draw per step and ensemble, at its walker 0)
-__device__ __forceinline__ double hmc_step_size(double eps, double ln_jitter, uint32_t s_lo, uint32_t s_hi, uint32_t g0, uint32_t k0, uint32_t k1) {
-    if (ln_jitter == 0.0) return eps;
-    uint32_t r[4];
-    philox4x32_10(s_lo, s_hi, g0, ALABI_HMC_STREAM_JITTER, k0, k1, r);
-    return eps * exp((2.0 * u53(r[0], r[1]) - 1.0) * ln_jitter);
-}
-
+// (HmcArgs, the draws' helpers and the steps of a walker: ens_hmc_device.hpp, shared with ens_hmc_adapt_kernel)
 template <int D, bool GENERIC>
 __global__ void __launch_bounds__(512)
 ens_hmc_kernel(HmcArgs p) {
     extern __shared__ __attribute__((aligned(16))) double hmc_lds[];   // [n][d, ld] scale factors | [Npad] weights
     __shared__ double qs_s[ALABI_MAX_DIM], g_s[ALABI_MAX_DIM];
     __shared__ double scratch[16];
-    const int tid = threadIdx.x, T = blockDim.x, d = p.lg.d, ld = d | 1;
-    const int w = blockIdx.x;                                       // global walker id
-    const uint32_t g0 = (uint32_t)((w / p.W) * p.W);                // global id of the ensemble's walker 0
-    double* w_s = hmc_lds + (size_t)p.mt.n * d * ld;
-    for (int idx = tid; idx < p.mt.n * d * d; idx += T) {
-        const int m = idx / (d * d), rc = idx - m * d * d;
-        hmc_lds[(size_t)m * d * ld + (rc / d) * ld + (rc % d)] = p.scale_C[idx];
-    }
-    const bool in = tid < d;                                        // wave 0 keeps the walker: lane k its coordinate k
-    double xv = 0.0, inv_len = 0.0, lo = 0.0, hi = 0.0;
-    if (in) {
-        xv = p.coords[(size_t)w * d + tid];
-        inv_len = p.lg.consts[tid];
-        lo = p.lg.consts[ALABI_MAX_DIM + tid];
-        hi = p.lg.consts[2 * ALABI_MAX_DIM + tid];
-    }
-    double lp_old = p.logp[w];
-    long long nacc = 0;
-    const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
-    const size_t WT = (size_t)gridDim.x;
-    double gx, lp_unused;
-    lp_grad_eval<D, GENERIC>(p.lg, w_s, qs_s, g_s, scratch, xv, inv_len, lp_unused, gx);   // its first barrier covers the factors
-    for (int t = 0; t < p.K; ++t) {
-        const long long step = p.step0 + t;
-        const uint32_t s_lo = (uint32_t)step, s_hi = (uint32_t)((unsigned long long)step >> 32);
-        const int mi = p.inj_z ? p.inj_k : hmc_step_move(p.mt, s_lo, s_hi, g0, k0, k1);   // workgroup-uniform
-        double mp0, mp1;
-        hmc_move_params(p.mt, mi, mp0, mp1);
-        const int L = hmc_leapfrog_of(mp1);
-        const double* Cs = hmc_lds + (size_t)mi * d * ld;
-        const int diagonal = (p.scale_diag >> mi) & 1;
-        double e = 0.0, z0 = 0.0, z = 0.0, lnu = 0.0, q = xv, gq = gx, lpq = lp_old;
-        if (tid < 64) {
-            if (p.inj_z) {
-                e = p.inj_e;
-                z0 = in ? p.inj_z[(size_t)w * d + tid] : 0.0;
-                lnu = log(p.inj_u[w]);
-            } else {
-                e = hmc_step_size(mp0, hmc_ln_jitter_of(mp1), s_lo, s_hi, g0, k0, k1);
-                z0 = in ? philox_normal(s_lo, s_hi, (uint32_t)w, ALABI_HMC_STREAM_Z + 16u * (uint32_t)tid, k0, k1) : 0.0;
-                uint32_t r[4];
-                philox4x32_10(s_lo, s_hi, (uint32_t)w, 2u, k0, k1, r);
-                lnu = log(u53(r[0], r[1]));
-            }
-            z = fma(0.5 * e, scale_transposed_times(Cs, diagonal, d, ld, tid, gx), z0);
-        }
-        for (int l = 0; l < L; ++l) {   // workgroup-uniform trip count
-            if (tid < 64) q = fma(e, scale_times(Cs, diagonal, d, ld, tid, z), q);
-            lp_grad_eval<D, GENERIC>(p.lg, w_s, qs_s, g_s, scratch, q, inv_len, lpq, gq);
-            if (tid < 64) z = fma(l == L - 1 ? 0.5 * e : e, scale_transposed_times(Cs, diagonal, d, ld, tid, gq), z);
-        }
-        if (tid >= 64) continue;
-        const bool out = in && !((q > lo) && (q < hi));             // NaN is outside
-        const bool inb = __ballot(out) == 0ull;
-        const double ke0 = 0.5 * wave_total(z0 * z0), ke1 = 0.5 * wave_total(z * z);
-        const double dh = lpq - ke1 - lp_old + ke0;
-        if (inb && dh > lnu) {                                      // false for NaN
-            xv = q; lp_old = lpq; gx = gq;
-            ++nacc;
-        }
-        if (p.chain || p.chain_logp) {
-            const long long done = p.done0 + t + 1;
-            if (done % p.thin_by == 0) {
-                const size_t slot = (size_t)(done / p.thin_by - 1);
-                if (p.chain && in) __builtin_nontemporal_store(xv, &p.chain[(slot * WT + w) * d + tid]);
-                if (p.chain_logp && tid == 0) __builtin_nontemporal_store(lp_old, &p.chain_logp[slot * WT + w]);
-            }
-        }
-    }
-    if (tid >= 64) return;
-    if (in) p.coords[(size_t)w * d + tid] = xv;
-    if (tid == 0) {
-        p.logp[w] = lp_old;
-        if (p.n_accept) p.n_accept[w] += nacc;
-    }
+    hmc_walker_steps<D, GENERIC, false>(p, HmcAdaptArgs{}, hmc_lds, qs_s, g_s, scratch);
 }
 
 // lnp and its gradient at M arbitrary points, one workgroup per point: the kernel's evaluation behind the box gate
@@ -219,20 +100,6 @@ __global__ void ens_hmc_export_kernel(unsigned long long seed, long long step, i
     }
 }
 
-static size_t hmc_lds_bytes(const alabi_ens* e) { return ens_hmc_lds_bytes(e->moves.n, e->d, e->gp->Npad); }
-static int hmc_threads(const alabi_ens* e) { return e->threads > 512 ? 512 : e->threads; }
-// (steps per launch: ens_hmc_chunk in ens_plan.hip)
-
-static LpGradArgs lp_grad_args(const alabi_ens* e) {
-    const alabi_gp* gp = e->gp;
-    LpGradArgs a{};
-    a.Xt = gp->Xt; a.alpha = gp->alpha; a.consts = e->consts;
-    a.d = e->d; a.Npad = gp->Npad; a.has_prior = e->has_prior; a.ymap = e->ymap;
-    a.prior_const = e->prior_const;
-    a.amp = e->lp_scale * std::exp(gp->log_amp); a.mean = std::fma(e->lp_scale, gp->mean, e->lp_shift); a.kf = gp->kf;
-    return a;
-}
-
 template <int D, bool GENERIC>
 static int launch_hmc_inst(const HmcArgs& a, int grid, int T, size_t lds, hipStream_t s) {
     if (lds > 32 * 1024) {
@@ -251,13 +118,7 @@ int launch_ens_hmc(alabi_ens* e, double* coords, double* logp, long long step0, 
     const int db = dim_bucket(e->d);
     const size_t lds = hmc_lds_bytes(e);
     if (!e->all_hmc || !e->gauss_C || db < 0 || lds > ALABI_HMC_MAX_LDS) return ALABI_BAD_ARGUMENT;
-    HmcArgs a{};
-    a.coords = coords; a.logp = logp; a.lg = lp_grad_args(e);
-    a.chain = chain; a.chain_logp = chain_logp; a.n_accept = n_accept;
-    a.scale_C = e->gauss_C;
-    a.step0 = step0 + done0; a.done0 = done0; a.seed = e->seed;
-    a.K = K; a.W = e->W; a.thin_by = thin_by; a.scale_diag = e->gauss_diag;
-    a.mt = e->moves;
+    HmcArgs a = hmc_args(e, coords, logp, step0, done0, K, thin_by, chain, chain_logp, n_accept);
     a.inj_z = inj_z; a.inj_u = inj_u; a.inj_e = inj_e; a.inj_k = inj_k;
     if (!a.lg.Xt || !a.lg.alpha) return ALABI_NOT_COMPUTED;
     const int grid = e->W * e->E, T = hmc_threads(e);

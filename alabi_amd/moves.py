@@ -35,8 +35,8 @@ Metropolis move --, alone or as a weighted mixture from which ONE move is chosen
   estimates the posterior covariance as for ``GaussianMove`` -- the mass matrix is its inverse --; ``n_leapfrog=1`` is MALA.  Like
   a Metropolis set, a set of HMC moves is ``nwalkers`` independent chains on one workgroup per walker (``ens_hmc_kernel``), any
   ``nwalkers >= 1``; it holds HMC moves only (mixtures of several step sizes and trajectory lengths are the standard cure for
-  periodic trajectories) and needs the fused log-probability: no ``prior_fn`` / ``like_fn``, no ``shard``.  No adaptation of the
-  step size or the mass, no NUTS.
+  periodic trajectories) and needs the fused log-probability: no ``prior_fn`` / ``like_fn``, no ``shard``.  The step size and the
+  mass are adapted by a warm-up phase, ``EnsembleSampler.tune_hmc`` (one ``HMCMove``); no NUTS.
 
 ``MHMove(proposal_function, ndim=None)`` is emcee's generic Metropolis move: ``proposal_function(coords[W, d], rng) -> (q[W, d],
 log_factors[W])`` is a Python callable, so it runs on a host-driven step loop (one round trip per step: slow by nature), the
@@ -212,10 +212,12 @@ class HMCMove:
     accept iff lnp(q) - |z|^2 / 2 - lnp(x) + |z0|^2 / 2 > ln u and q lies in the open box -- only the end point is tested, in
     between the trajectory follows the surrogate's smooth extension.  ``n_leapfrog=1`` is MALA, the
     Metropolis-adjusted Langevin algorithm; at most 64.  ``step_size=None`` resolves to ``ndim ** -0.25``, the conventional scaling
-    of the optimal step with the dimension for a well-estimated ``cov``: it is untuned and unmeasured here, so look at the
-    acceptance fraction (0.6 - 0.9 is the usual aim) and set it.  ``jitter``: None or a number > 1 with the meaning of
+    of the optimal step with the dimension for a well-estimated ``cov``: a starting point only -- ``EnsembleSampler.tune_hmc``
+    (``run_emcee``'s ``sampler_kwargs["hmc_warmup"]``) adapts the step size by dual averaging and, from the walkers' positions,
+    ``cov`` itself, Stan-style; without it look at the acceptance fraction (0.6 - 0.9 is the usual aim) and set the step.  ``jitter``: None or a number > 1 with the meaning of
     ``GaussianMove(factor=)`` -- e = step_size exp(v), v ~ U(-ln jitter, ln jitter), one draw per step and ensemble (ln jitter is
-    rounded to a multiple of 2^-36 on its way into the library's table).  Nothing is adapted during a run."""
+    rounded to a multiple of 2^-36 on its way into the library's table).  Nothing is adapted during a run: adaptation is the
+    warm-up phase ``tune_hmc``, after which the sampler's move is a new ``HMCMove`` with the step size and ``cov`` it found."""
 
     def __init__(self, cov, step_size=None, n_leapfrog=8, jitter=None):
         if step_size is not None:

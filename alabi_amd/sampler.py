@@ -241,6 +241,7 @@ class EnsembleSampler:
         st["group"] = None
         st["prior_fn_host"] = None      # host callables (often closures) are not part of the saved state
         st["like_fn_host"] = None
+        st["_last_window_chain"] = None    # tune_hmc's scratch chain of its last window (device)
         for k in ("_coords", "_logp", "_naccept"):
             st[k] = None if st[k] is None else st[k].cpu()
         st["_chains"] = [c.cpu() for c in self._chains]
@@ -560,6 +561,93 @@ class EnsembleSampler:
             _lib.check(_lib.lib().alabi_ens_last_state(self._ens, C.c_void_p(c.ctypes.data), C.c_void_p(lp.ctypes.data)),
                        "alabi_ens_last_state")
             return State(c, lp)
+        return State(self._coords.cpu().numpy(), self._logp.cpu().numpy())
+
+    def _hmc_adapt(self, nsteps, state, par, chain=None, accept_stat=None):
+        """``nsteps`` warm-up steps of the walkers on ens_hmc_adapt_kernel (alabi_ens_hmc_adapt) from the draw counter, which
+        advances; ``state`` [E W, 5] is the dual-averaging state (device, in / out), ``par`` (delta, gamma, t0, kappa)."""
+        _lib.check(_lib.lib().alabi_ens_hmc_adapt(self._ens, _lib.ptr(self._coords), _lib.ptr(self._logp), self._rng_step, int(nsteps), 1,
+                                                  _lib.ptr(state), _lib.host_doubles(par), _lib.ptr(chain), None, None,
+                                                  _lib.ptr(accept_stat), _lib.current_stream()), "alabi_ens_hmc_adapt")
+        self._rng_step += int(nsteps)
+
+    def tune_hmc(self, initial_state, nwarmup=500, target_accept=0.8, metric="diag", gamma=0.05, t0=10, kappa=0.75):
+        """Stan-style warm-up of the sampler's one ``HMCMove``: the step size by dual averaging per walker (Hoffman & Gelman 2014,
+        algorithm 5, towards a mean acceptance statistic of ``target_accept``) on ``ens_hmc_adapt_kernel``, and, with ``metric``
+        "diag" or "dense", the mass matrix from the pooled covariance of the walkers' positions in Stan's doubling windows
+        (``alabi_amd.hmc_adapt``: an initial buffer, the windows, a terminal buffer; every one of them is ONE library call).
+        ``metric=None`` adapts the step size only.  Dual averaging starts at the move's resolved step size e with mu = ln(10 e); at
+        a window's end the new factor is installed and every walker restarts at the pooled step size.  Afterwards the sampler's move
+        is ``HMCMove(cov, step_size)`` with what was found (``n_leapfrog`` and ``jitter`` kept), the library's table holds it, and
+        ``hmc_tuning`` says what happened: ``step_size``, ``cov`` (None where the mass was not adapted), ``window_ends``,
+        ``step_sizes`` (the pooled step size at every window's end), ``mean_accept_stat`` of the terminal buffer and ``last_path ==
+        "hmc-adapt"``.  The warm-up steps consume the draw counter like ``run_mcmc``'s but are no part of the chain, of ``iteration``
+        or of the acceptance counts.  Returns the ``State`` to continue from (``run_mcmc(None, n)`` continues there too).  A set
+        that is not exactly one ``HMCMove``, host callables and ``shard=True`` raise ``ValueError``."""
+        from . import hmc_adapt as ha
+        from .moves import HMCMove
+        if self.generic:
+            raise ValueError("tune_hmc needs the gradient of the log-probability, which exists for the fused surrogate only: a Python "
+                             "prior_fn or like_fn (the host-callback path) has none")
+        if self.shard:
+            raise ValueError("tune_hmc cannot run with shard=True: the sharded form of an HMCMove is not built")
+        ms = self._move_set
+        if ms is None or len(ms) != 1 or not isinstance(ms.moves[0], HMCMove):
+            raise ValueError("tune_hmc adapts the step size and the mass matrix of exactly one HMCMove: mixtures of HMC moves under "
+                             "adaptation are not built, and no other move has a step size to adapt")
+        if metric not in (None, "diag", "dense"):
+            raise ValueError("metric must be None, 'diag' or 'dense'")
+        nwarmup = int(nwarmup)
+        par = (float(target_accept), float(gamma), float(t0), float(kappa))
+        if nwarmup < 1 or not (0.0 < par[0] < 1.0) or not par[1] > 0.0 or not par[2] >= 0.0 or not (0.5 < par[3] <= 1.0):
+            raise ValueError("tune_hmc needs nwarmup >= 1, 0 < target_accept < 1, gamma > 0, t0 >= 0 and 0.5 < kappa <= 1")
+        move = ms.moves[0]
+        t_start = time.perf_counter()
+        coords = initial_state.coords if isinstance(initial_state, State) else initial_state
+        coords = _to_dev(coords, 2).clone()
+        if coords.shape != (self.total_walkers, self.ndim):
+            raise ValueError("incompatible input dimensions: initial state must be (nwalkers * n_ensembles, ndim)")
+        self._coords = coords
+        self._logp = self.compute_log_prob(coords)
+        if torch.isnan(self._logp).any():
+            raise ValueError("The initial log_prob was NaN")
+        self._ensure_ens()
+        dev, WT = coords.device, self.total_walkers
+        state = torch.as_tensor(ha.initial_state(WT, move.resolved_step_size(self.ndim)), device=dev)
+        segments = ha.warmup_segments(nwarmup, windows=metric is not None)
+        cov, step_sizes, window_ends, stat = None, [], [], None
+        for k, (first, end, is_window) in enumerate(segments):
+            n = end - first
+            scratch = torch.empty((n, WT, self.ndim), dtype=torch.float64, device=dev) if is_window else None
+            last = k == len(segments) - 1
+            stat = torch.zeros(WT, dtype=torch.float64, device=dev) if last else None
+            self._hmc_adapt(n, state, par, chain=scratch, accept_stat=stat)
+            if is_window:
+                torch.cuda.current_stream().synchronize()
+                cov = ha.regularised_covariance(scratch.reshape(-1, self.ndim), metric)
+                move = HMCMove(cov, step_size=move.resolved_step_size(self.ndim), n_leapfrog=move.n_leapfrog, jitter=move.jitter)
+                _lib.check(_lib.lib().alabi_ens_set_move_scale(self._ens, 0, _lib.host_doubles(move.scale_matrix(self.ndim).ravel()),
+                                                               int(move.diagonal)), "alabi_ens_set_move_scale")
+                pooled = ha.pooled_step_size(state[:, 3])
+                step_sizes.append(pooled); window_ends.append(end)
+                self._last_window_chain = scratch
+                if not last:
+                    state.copy_(torch.as_tensor(ha.restart_state(WT, pooled), device=dev))
+        torch.cuda.current_stream().synchronize()
+        eps = ha.pooled_step_size(state[:, 3])
+        move = HMCMove(move.cov, step_size=eps, n_leapfrog=move.n_leapfrog, jitter=move.jitter)
+        self._move_set = parse_moves(move, self.ndim)
+        m = self._move_set
+        _lib.check(_lib.lib().alabi_ens_set_move_scale(self._ens, 0, _lib.host_doubles(move.scale_matrix(self.ndim).ravel()),
+                                                       int(move.diagonal)), "alabi_ens_set_move_scale")
+        _lib.check(_lib.lib().alabi_ens_set_moves(self._ens, 1, (C.c_int * 1)(int(m.kind[0])), _lib.host_doubles(m.cum),
+                                                  _lib.host_doubles(m.p0), _lib.host_doubles(m.p1)), "alabi_ens_set_moves")
+        n_last = segments[-1][1] - segments[-1][0]
+        self.hmc_tuning = dict(step_size=eps, cov=None if cov is None else np.array(cov, copy=True), window_ends=window_ends,
+                               step_sizes=step_sizes, mean_accept_stat=float(stat.mean().item()) / n_last, nwarmup=nwarmup,
+                               metric=metric, seconds=time.perf_counter() - t_start, last_path="hmc-adapt")
+        self.last_path = "hmc-adapt"
+        self.last_stream_kernel = "ens_hmc_adapt_kernel"
         return State(self._coords.cpu().numpy(), self._logp.cpu().numpy())
 
     def reset(self):

@@ -304,6 +304,22 @@ int alabi_ens_mh_plan(alabi_ens* ens, int* out /* host [4] */);
 /* ens_hmc_kernel's last launch: out[4] = workgroup size, steps per launch, LDS bytes, 1 if a lane takes more than one training
  * point per pass (Npad exceeds the workgroup). */
 int alabi_ens_hmc_plan(alabi_ens* ens, int* out /* host [4] */);
+/* HMC warm-up: nsteps steps of a table of exactly ONE kind-6 move on ens_hmc_adapt_kernel -- ens_hmc_kernel's launch shape,
+ * arithmetic, draws and accept rule -- with a step size per walker adapted by dual averaging (Hoffman & Gelman 2014, algorithm 5;
+ * tests/hmc_adapt_numpy.py states it).  da_state device [E*W, 5] doubles in/out: m (steps since the last restart), H-bar, ln e,
+ * ln e-bar, mu.  A step of walker w runs with e = exp(ln e_w) f, f the step's jitter factor as alabi_ens_run draws it (1 without
+ * jitter; the table's p0 is not read).  With dh the left-hand side of the accept test, a = min(1, exp(dh)), 0 where the end point
+ * is outside the open box or dh is NaN; then m <- m + 1, H-bar <- (1 - 1 / (m + t0)) H-bar + (delta - a) / (m + t0),
+ * ln e <- mu - (sqrt(m) / gamma) H-bar, ln e-bar <- m^-kappa ln e + (1 - m^-kappa) ln e-bar.  da_par host [4]: delta in (0, 1),
+ * gamma > 0 (+inf allowed: ln e stays at mu), t0 >= 0, kappa in (0.5, 1]; Stan's defaults are 0.8, 0.05, 10, 0.75.  The call
+ * consumes the global steps step0 ... step0 + nsteps - 1 exactly as alabi_ens_run does (a run after warm-up continues at
+ * step0 + nsteps), with coords, logp, thin_by, chain, chain_logp and n_accept as there; accept_stat device [E*W] or null: the
+ * sum of a over the call's steps is added.  The state is read when a launch starts and written when it ends, so chunking
+ * (ALABI_ENS_HMC_CHUNK) and splitting the call change no bit.  Reports through alabi_ens_hmc_plan.  ALABI_BAD_ARGUMENT: the table
+ * is not exactly one kind-6 move, a parameter is out of range, or the factor and the gradient weights exceed 128 KB of LDS. */
+int alabi_ens_hmc_adapt(alabi_ens* ens, double* coords, double* logp, long long step0, long long nsteps, int thin_by,
+                        double* da_state /* device [E*W, 5] in/out */, const double* da_par /* host [4]: delta, gamma, t0, kappa */,
+                        double* chain, double* chain_logp, long long* n_accept, double* accept_stat /* or null */, void* stream);
 /* The ensemble's log-probability and its gradient at M arbitrary points, by the evaluation ens_hmc_kernel runs: coords [M, d],
  * logp [M], grad [M, d] on the device.  lnp = GP mean through the folded affine scalers and the y map, plus the normal priors;
  * grad = a T^T dmu (no map), ln10 lnp a T^T dmu (either map), minus (x_k - m_k) / s_k^2 per normal-prior coordinate.  Outside the
