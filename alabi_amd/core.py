@@ -460,10 +460,13 @@ class SurrogateModel(object):
                 def grad_nll(p_opt):
                     """-d logL/dp from the device's analytic gradient (+ the regulariser's), assembled exactly as the
                     reference does (core.py:1255-1277): with uniform_scales the shared length-scale entry receives the MEAN
-                    of the per-dimension gradients."""
+                    of the per-dimension gradients.  Zeros, without the regulariser's part, where the objective is the constant
+                    1e25 (K not positive definite)."""
                     p = self.expand_hyperparameter_vector(p_opt)
                     self.set_hyperparameter_vector(gp, p_opt)
                     try:
+                        if not gp.recompute(quiet=True):
+                            return np.zeros(len(p_opt))      # K not positive definite: nll is the constant 1e25 there
                         grad_lnlike = -gp.grad_log_likelihood(_y, quiet=True)
                     except (np.linalg.LinAlgError, RuntimeError):
                         return np.zeros(len(p_opt))
