@@ -77,6 +77,8 @@ SIGNATURES = {
     "alabi_ens_set_move_scale": (_i, [_vp, _i, _pd, _i]),
     "alabi_ens_mh_plan": (_i, [_vp, _pi]),
     "alabi_ens_hmc_plan": (_i, [_vp, _pi]),
+    "alabi_ens_nuts_plan": (_i, [_vp, _pi]),
+    "alabi_ens_nuts_stats": (_i, [_vp, _vp, _vp, _i]),
     "alabi_ens_hmc_adapt": (_i, [_vp, _vp, _vp, _ll, _ll, _i, _vp, _pd, _vp, _vp, _vp, _vp, _vp]),
     "alabi_ens_log_prob_grad": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "alabi_ens_maximize": (_i, [_vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -120,6 +122,8 @@ SIGNATURES = {
     "alabi_ens_export_gauss_draws": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "alabi_ens_step_with_randoms_hmc": (_i, [_vp, _vp, _vp, _i, _d, _vp, _vp, _vp, _vp]),
     "alabi_ens_export_hmc_draws": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp]),
+    "alabi_ens_step_with_randoms_nuts": (_i, [_vp, _vp, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "alabi_ens_export_nuts_draws": (_i, [_vp, _ll, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "alabi_ns_create": (_i, [_vp, _i, _pd, _ull, C.POINTER(_vp)]),
     "alabi_ns_destroy": (_i, [_vp]),
     "alabi_ns_set_logp": (_i, [_vp, _d, _d, _i]),

@@ -1079,7 +1079,10 @@ class SurrogateModel(object):
         surrogate likelihood with a prior that fuses (none, uniform or normal) and cannot be sharded.  With a single ``HMCMove``,
         ``sampler_kwargs["hmc_warmup"] = n`` (optionally ``"hmc_target_accept"``, default 0.8, and ``"hmc_metric"``: "diag", "dense" or
         None) runs ``EnsembleSampler.tune_hmc`` for n steps in front of the run -- Stan-style warm-up of the step size and the mass
-        matrix; what it found is ``sm.hmc_tuning`` --; with any other move set these keys raise ``ValueError``.  Any other emcee move raises ``NotImplementedError`` -- in
+        matrix; what it found is ``sm.hmc_tuning`` --; with any other move set these keys raise ``ValueError``.  ``alabi_amd.moves.NUTSMove(cov,
+        step_size=None, max_depth=8, jitter=None)`` is the No-U-Turn sampler on the same gradient under the same restrictions: the
+        trajectory length is chosen per transition; ``sm.nuts_stats`` says afterwards how deep the trees went (tune an ``HMCMove``
+        first and pass ``NUTSMove(sm.hmc_tuning["cov"], step_size=sm.hmc_tuning["step_size"])``).  Any other emcee move raises ``NotImplementedError`` -- in
         particular emcee's ``DESnookerMove``, whose arithmetic is not the published rule; none of ``DEMove``, ``SnookerMove``,
         ``WalkMove``, ``KDEMove``, ``GaussianMove``, ``MHMove`` can be combined with ``"shard": True``.
 
@@ -1101,6 +1104,10 @@ class SurrogateModel(object):
         hmc_warmup = kw.pop("hmc_warmup", None)
         hmc_tune_kw = {name: kw.pop(key) for key, name in (("hmc_target_accept", "target_accept"), ("hmc_metric", "metric")) if key in kw}
         if hmc_warmup is not None or hmc_tune_kw:
+            if move_set is not None and move_set.has_nuts:
+                raise ValueError('sampler_kwargs "hmc_warmup", "hmc_target_accept" and "hmc_metric" adapt an HMCMove, not a NUTSMove (a '
+                                 'NUTS warm-up is not built): tune an HMCMove first, then pass NUTSMove(sm.hmc_tuning["cov"], '
+                                 'step_size=sm.hmc_tuning["step_size"])')
             if move_set is None or len(move_set) != 1 or not move_set.all_hmc:
                 raise ValueError('sampler_kwargs "hmc_warmup", "hmc_target_accept" and "hmc_metric" need sampler_kwargs["moves"] to be '
                                  'a single HMCMove: its step size and mass matrix are what the warm-up adapts')
@@ -1110,9 +1117,9 @@ class SurrogateModel(object):
         if kw.get("shard", False) and move_set is not None and (move_set.has_gauss or move_set.all_mh):
             raise ValueError('sampler_kwargs={"shard": True} cannot run a GaussianMove or an MHMove: a Metropolis proposal reads no '
                              'other walker, so there is nothing to exchange -- run replicas instead')
-        if kw.get("shard", False) and move_set is not None and move_set.has_hmc:
-            raise ValueError('sampler_kwargs={"shard": True} cannot run an HMCMove: the sharded form is not built -- run replicas '
-                             'instead')
+        if kw.get("shard", False) and move_set is not None and (move_set.has_hmc or move_set.has_nuts):
+            raise ValueError('sampler_kwargs={"shard": True} cannot run an HMCMove or a NUTSMove: the sharded form is not built -- run '
+                             'replicas instead')
         if kw.get("shard", False) and move_set is not None and move_set.multi_partner:
             raise ValueError('sampler_kwargs={"shard": True} cannot run a DEMove or a SnookerMove: the sharded ensemble links one '
                              'partner row per proposal')
@@ -1172,6 +1179,7 @@ class SurrogateModel(object):
                 start = self.emcee_sampler.tune_hmc(start, nwarmup=hmc_warmup, **hmc_tune_kw).coords
                 self.hmc_tuning = self.emcee_sampler.hmc_tuning
             self.emcee_sampler.run_mcmc(start, self.nsteps, **run_kwargs)
+            self.nuts_stats = getattr(self.emcee_sampler, "nuts_stats", None)      # None without a NUTSMove
             self.emcee_runtime += time.time() - t0
             self.iburn, self.ithin = mcmc_utils.estimate_burnin(self.emcee_sampler, verbose=self.verbose)
             self.burn = burn if burn is not None else self.iburn

@@ -245,7 +245,7 @@ struct alabi_ens {
     int prop_clean = 0;                  // the same for prop, whose words the epilogue of a pair chunk resets beside those of hist
     int stream_grid = 0;                 // workgroups per ensemble of the persistent kernel
     int last_path = 0;                   // route of the last alabi_ens_run (ens_plan.hpp: EnsRoute): 0 one launch per half step, 1 persistent kernel
-                                         // (ens_stream_kernel / ens_pair_kernel), 3 ens_group_kernel, 4 ens_mh_kernel, 5 ens_hmc_kernel
+                                         // (ens_stream_kernel / ens_pair_kernel), 3 ens_group_kernel, 4 ens_mh_kernel, 5 ens_hmc_kernel, 6 ens_nuts_kernel
     int stream_ok = 0;                   // eligible: training set fits the lanes' registers, one workgroup per CU
     // pair variant of the persistent kernel (ens_pair_kernel)
     unsigned long long* prop = nullptr;  // [(chunk_cap+1)][E*W][d+2] published proposals, allocated on first use
@@ -286,6 +286,12 @@ struct alabi_ens {
     // kind or the other); all_hmc: every move of the table is an HMC move, the only table that holds one (ens_hmc_kernel runs it)
     bool all_hmc = false;
     int hmc_plan[4] = {0};    // last ens_hmc_kernel launch: threads, steps per launch, LDS bytes, tiled (alabi_ens_hmc_plan)
+    // NUTS moves (kind 7): factors as kind 6; all_nuts: every move of the table is a NUTS move, the only table that holds one
+    // (ens_nuts_kernel runs it).  The per-walker sums since the last reset (alabi_ens_nuts_stats), allocated with the first such table
+    bool all_nuts = false;
+    int nuts_plan[4] = {0};   // last ens_nuts_kernel launch: threads, transitions per launch, LDS bytes, tiled (alabi_ens_nuts_plan)
+    long long* nuts_counts = nullptr;   // [E*W, 3] leaves, depths reached, divergent transitions
+    double* nuts_accept = nullptr;      // [E*W] sum of the leaves' acceptance statistics
 };
 
 namespace alabi {
@@ -365,6 +371,9 @@ inline EnsShape ens_shape(const alabi_ens* e, bool has_stream = true) {
     const size_t hl = ens_hmc_lds_bytes(e->moves.n, e->d, e->gp->Npad);
     sh.hmc_lds = hl > 0x7fffffffull ? 0x7fffffff : (int)hl;
     sh.has_stream = has_stream;
+    sh.all_nuts = e->all_nuts;
+    const size_t nl = ens_nuts_lds_bytes(e->moves.n, e->d, e->gp->Npad);
+    sh.nuts_lds = nl > 0x7fffffffull ? 0x7fffffff : (int)nl;
     return sh;
 }
 // ensemble.hip.  The entry points of ens_api.hip / ens_run.hip / ens_sharded.hip read ens_switches() once per call and hand it
@@ -444,6 +453,17 @@ int launch_ens_map(alabi_ens* e, const double* starts, int S, int maxiter, doubl
 int launch_ens_lp_hess(alabi_ens* e, const double* pts, int M, double* hess, hipStream_t s);
 void ens_map_plan(const alabi_ens* e, int* out);
 int launch_ens_hmc_export(alabi_ens* e, long long step, int* move, double* e_out, double* z, double* u_acc, hipStream_t s);
+// ens_nuts.hip: all transitions of a chunk of an all-NUTS set in one launch, one workgroup per walker (inj: one transition of move
+// inj->k from injected draws, with its trace)
+struct NutsInject {
+    int k; double e;
+    const double* z0; const unsigned* dir; const double* u_leaf; const double* u_tree;
+    int* trace;
+};
+int launch_ens_nuts(alabi_ens* e, double* coords, double* logp, long long step0, long long done0, int K, int thin_by, double* chain,
+                    double* chain_logp, long long* n_accept, const NutsInject* inj, hipStream_t s);
+int launch_ens_nuts_export(alabi_ens* e, long long step, int depth, int* move, double* e_out, double* z, unsigned* dir, double* u_leaf,
+                           double* u_tree, hipStream_t s);
 int launch_ens_lnprob(alabi_ens* e, const double* coords, int nwalkers, double* logp, int gate_box, hipStream_t s);
 int launch_ens_propose(alabi_ens* e, const HalfArgs& args, int nblocks, int gate_box, double* q, double* like, hipStream_t s);
 int launch_ens_accept(alabi_ens* e, const HalfArgs& args, int count, const double* q, const double* lp_new, hipStream_t s);

@@ -240,6 +240,8 @@ int alabi_ens_destroy(alabi_ens* e) {
     free_move_buffers(e->mv);
     free_kde_buffers(e->kde);
     if (e->gauss_C) (void)hipFree(e->gauss_C);
+    if (e->nuts_counts) (void)hipFree(e->nuts_counts);
+    if (e->nuts_accept) (void)hipFree(e->nuts_accept);
     if (e->side_stream) (void)hipStreamDestroy(e->side_stream);
     if (e->ev_free) (void)hipEventDestroy(e->ev_free);
     if (e->ev_drawn) (void)hipEventDestroy(e->ev_drawn);
@@ -293,7 +295,7 @@ int alabi_ens_set_logp_map(alabi_ens* e, int kind) {
 int alabi_ens_set_moves(alabi_ens* e, int n, const int* kind, const double* cum, const double* p0, const double* p1) {
     if (!e || n < 0 || n > ALABI_MAX_MOVES || (n > 0 && (!kind || !cum || !p0 || !p1))) return ALABI_BAD_ARGUMENT;
     MoveTable mt{};
-    bool de = false, snooker = false, walk = false, kde = false, gauss = false, all_gauss = n > 0, hmc = false, all_hmc = n > 0;
+    bool de = false, snooker = false, walk = false, kde = false, gauss = false, all_gauss = n > 0, hmc = false, all_hmc = n > 0, nuts = false, all_nuts = n > 0;
     const int nc_min = e->W / 2, nc_max = (e->W + 1) / 2;   // the two complementary halves
     double prev = 0.0;
     for (int k = 0; k < n; ++k) {
@@ -318,18 +320,32 @@ int alabi_ens_set_moves(alabi_ens* e, int n, const int* kind, const double* cum,
             if (!(p0[k] > 0.0) || !std::isfinite(p0[k]) || !std::isfinite(p1[k]) || !(p1[k] >= 1.0) || !(p1[k] < 65.0)) return ALABI_BAD_ARGUMENT;
             if (!((e->gauss_staged >> k) & 1)) return ALABI_BAD_ARGUMENT;   // its scale factor has been handed over for this slot
             hmc = true;
+        } else if (kind[k] == 7) {                           // NUTS: p0 = step size > 0, p1 = max_depth (1 ... 10) + ln jitter / 512
+            if (!(p0[k] > 0.0) || !std::isfinite(p0[k]) || !std::isfinite(p1[k]) || !(p1[k] >= 1.0) || !(p1[k] < ALABI_NUTS_MAX_DEPTH + 1.0))
+                return ALABI_BAD_ARGUMENT;
+            if (!((e->gauss_staged >> k) & 1)) return ALABI_BAD_ARGUMENT;   // its scale factor has been handed over for this slot
+            nuts = true;
         }
         else return ALABI_BAD_ARGUMENT;
         if (kind[k] != 5) all_gauss = false;
         if (kind[k] != 6) all_hmc = false;
+        if (kind[k] != 7) all_nuts = false;
         mt.kind[k] = kind[k]; mt.cum[k] = cum[k]; mt.p0[k] = p0[k]; mt.p1[k] = p1[k];
     }
     if (n > 0 && !(prev > 0.0)) return ALABI_BAD_ARGUMENT;
     if (hmc && !all_hmc) return ALABI_BAD_ARGUMENT;      // an HMC move runs on ens_hmc_kernel alone: no mixture with another kind
-    if (e->W < 2 && !all_gauss && !all_hmc) return ALABI_BAD_ARGUMENT;   // a red-blue move needs a complementary half
+    if (nuts && !all_nuts) return ALABI_BAD_ARGUMENT;    // nor does a NUTS move: ens_nuts_kernel alone
+    if (e->W < 2 && !all_gauss && !all_hmc && !all_nuts) return ALABI_BAD_ARGUMENT;   // a red-blue move needs a complementary half
     if (de && e->W < 4) return ALABI_BAD_ARGUMENT;       // two distinct partners in a complementary list of W / 2 walkers
     if (snooker && e->W < 6) return ALABI_BAD_ARGUMENT;  // three distinct partners
-    if (n > 0 && !hmc) { const int st = ensure_move_buffers(e, snooker || walk || kde || gauss, walk || kde || gauss); if (st != ALABI_OK) return st; }
+    if (nuts && !e->nuts_counts) {                       // the per-walker sums of alabi_ens_nuts_stats, zero from here
+        const size_t WT = (size_t)e->W * e->E;
+        ALABI_HIP_CHECK(hipMalloc(&e->nuts_counts, WT * 3 * sizeof(long long)));
+        ALABI_HIP_CHECK(hipMemset(e->nuts_counts, 0, WT * 3 * sizeof(long long)));
+        ALABI_HIP_CHECK(hipMalloc(&e->nuts_accept, WT * sizeof(double)));
+        ALABI_HIP_CHECK(hipMemset(e->nuts_accept, 0, WT * sizeof(double)));
+    }
+    if (n > 0 && !hmc && !nuts) { const int st = ensure_move_buffers(e, snooker || walk || kde || gauss, walk || kde || gauss); if (st != ALABI_OK) return st; }
     if (kde) { const int st = ensure_kde_buffers(e); if (st != ALABI_OK) return st; }
     mt.n = n;
     e->moves = mt;
@@ -339,6 +355,7 @@ int alabi_ens_set_moves(alabi_ens* e, int n, const int* kind, const double* cum,
     e->has_kde = kde;
     e->has_gauss = gauss; e->all_gauss = gauss && all_gauss;
     e->all_hmc = hmc && all_hmc;
+    e->all_nuts = nuts && all_nuts;
     e->gauss_staged = 0;                                 // scale factors belong to the table they were handed over for
     e->drawn_n = 0;                                      // records drawn under the old move set are not the new set's
     e->ahead_valid = false;                              // nor are those made ahead for the next stream call
@@ -382,7 +399,7 @@ int alabi_ens_set_stream(alabi_ens* e, int enabled) {
     // The switch belongs to the handle, not to the move table: it covers the persistent kernels of a red-blue table (they need
     // the version history) and ens_mh_kernel of an all-Gaussian one (it needs nothing), whichever table the next run finds.
     const bool can_stream = e->hist && e->err;
-    if (enabled && !can_stream && !e->all_gauss && !e->all_hmc) return ALABI_BAD_ARGUMENT;
+    if (enabled && !can_stream && !e->all_gauss && !e->all_hmc && !e->all_nuts) return ALABI_BAD_ARGUMENT;
     e->mh_ok = enabled ? 1 : 0;
     e->stream_ok = (enabled && can_stream) ? 1 : 0;
     e->settings_gen++;
@@ -742,6 +759,50 @@ int alabi_ens_step_with_randoms_hmc(alabi_ens* e, double* coords, double* logp, 
 int alabi_ens_export_hmc_draws(alabi_ens* e, long long step, int* move, double* eps, double* z, double* u_acc, void* stream) {
     if (!e || !move || !eps || !z || !e->all_hmc) return ALABI_BAD_ARGUMENT;
     return launch_ens_hmc_export(e, step, move, eps, z, u_acc, as_stream(stream));
+}
+
+int alabi_ens_nuts_plan(alabi_ens* e, int* out) {
+    if (!e || !out) return ALABI_BAD_ARGUMENT;
+    for (int i = 0; i < 4; ++i) out[i] = e->nuts_plan[i];
+    return ALABI_OK;
+}
+
+int alabi_ens_nuts_stats(alabi_ens* e, long long* counts_host, double* accept_host, int reset) {
+    if (!e || !counts_host || !accept_host) return ALABI_BAD_ARGUMENT;
+    const size_t WT = (size_t)e->W * e->E;
+    if (!e->nuts_counts || !e->nuts_accept) {            // no NUTS table yet: nothing has been summed
+        for (size_t i = 0; i < WT * 3; ++i) counts_host[i] = 0;
+        for (size_t i = 0; i < WT; ++i) accept_host[i] = 0.0;
+        return ALABI_OK;
+    }
+    ALABI_HIP_CHECK(hipDeviceSynchronize());
+    ALABI_HIP_CHECK(hipMemcpy(counts_host, e->nuts_counts, WT * 3 * sizeof(long long), hipMemcpyDeviceToHost));
+    ALABI_HIP_CHECK(hipMemcpy(accept_host, e->nuts_accept, WT * sizeof(double), hipMemcpyDeviceToHost));
+    if (reset) {
+        ALABI_HIP_CHECK(hipMemset(e->nuts_counts, 0, WT * 3 * sizeof(long long)));
+        ALABI_HIP_CHECK(hipMemset(e->nuts_accept, 0, WT * sizeof(double)));
+    }
+    return ALABI_OK;
+}
+
+int alabi_ens_step_with_randoms_nuts(alabi_ens* e, double* coords, double* logp, int k_move, double eps, const double* z0,
+                                     const unsigned* dir, const double* u_leaf, const double* u_tree, int* trace, long long* n_accept,
+                                     void* stream) {
+    if (!e || !coords || !logp || !z0 || !dir || !u_leaf || !u_tree || e->E != 1 || !e->all_nuts) return ALABI_BAD_ARGUMENT;
+    if (k_move < 0 || k_move >= e->moves.n || !(eps > 0.0) || !std::isfinite(eps)) return ALABI_BAD_ARGUMENT;
+    if (!e->gp->computed || !e->gp->has_alpha) return ALABI_NOT_COMPUTED;
+    hipStream_t s = as_stream(stream);
+    const int st = ens_sync_consts(e, s);
+    if (st != ALABI_OK) return st;
+    const NutsInject inj{k_move, eps, z0, dir, u_leaf, u_tree, trace};
+    return launch_ens_nuts(e, coords, logp, 0, 0, 1, 1, nullptr, nullptr, n_accept, &inj, s);
+}
+
+int alabi_ens_export_nuts_draws(alabi_ens* e, long long step, int max_depth, int* move, double* eps, double* z0, unsigned* dir,
+                                double* u_leaf, double* u_tree, void* stream) {
+    if (!e || !move || !eps || !z0 || !dir || !u_leaf || !u_tree || !e->all_nuts || max_depth < 1 || max_depth > ALABI_NUTS_MAX_DEPTH)
+        return ALABI_BAD_ARGUMENT;
+    return launch_ens_nuts_export(e, step, max_depth, move, eps, z0, dir, u_leaf, u_tree, as_stream(stream));
 }
 
 int alabi_ens_kde_singular(alabi_ens* e, long long* count) {

@@ -16,12 +16,12 @@ namespace alabi {
 // launch-per-half-step path outside a graph used to make one per half-step launch.  As with getenv, the first entry of a name counts.
 EnsSwitches ens_switches() {
     EnsSwitches sw;
-    enum { NFLAG = 9, NINT = 3, NALL = 15 };
+    enum { NFLAG = 9, NINT = 3, NALL = 16 };
     static const char* const names[NALL] = {"STREAM", "GROUP", "GROUP_G16", "GRAPH", "MH", "MULTI", "PAIR", "PLACE", "SHARD_GRAPH",
-                                            "THREADS", "GRAPH_STEPS", "SPIN_LIMIT", "CHUNK", "MH_CHUNK", "HMC_CHUNK"};
+                                            "THREADS", "GRAPH_STEPS", "SPIN_LIMIT", "CHUNK", "MH_CHUNK", "HMC_CHUNK", "NUTS_CHUNK"};
     int* const flags[NFLAG] = {&sw.stream, &sw.group, &sw.group_g16, &sw.graph, &sw.mh, &sw.multi, &sw.pair, &sw.place, &sw.shard_graph};
     int* const ints[NINT] = {&sw.threads, &sw.graph_steps, &sw.spin_limit};
-    long long* const longs[NALL - NFLAG - NINT] = {&sw.chunk, &sw.mh_chunk, &sw.hmc_chunk};
+    long long* const longs[NALL - NFLAG - NINT] = {&sw.chunk, &sw.mh_chunk, &sw.hmc_chunk, &sw.nuts_chunk};
     unsigned seen = 0;
     for (char** e = environ; e && *e; ++e) {
         if ((*e)[0] != 'A' || strncmp(*e, "ALABI_ENS_", 10) != 0) continue;
@@ -142,6 +142,25 @@ int ens_hmc_chunk(const EnsShape& sh, int n_cu, const EnsSwitches& sw) {
     return (int)chunk;
 }
 
+// Transitions per launch, 0 where the table does not run on ens_nuts_kernel (not all NUTS, no factors, a dimension without a bucket,
+// more than 128 KB of LDS).  ens_hmc_chunk's estimate with the deepest tree's 2^max_depth - 1 leaves in place of n_leapfrog -- an
+// estimate, not a measurement: most trees stop far short of it -- between 4 and 16384 transitions.  The counters travel by value,
+// the gradient at the walker is a function of the walker alone and the per-walker sums grow transition by transition: the chunk
+// length changes no result.
+int ens_nuts_chunk(const EnsShape& sh, int n_cu, const EnsSwitches& sw) {
+    if (!sh.all_nuts || !sh.factors || dim_bucket(sh.d) < 0 || sh.nuts_lds > ALABI_HMC_MAX_LDS) return 0;
+    if (sh.lmax < 1 || sh.lmax > ALABI_NUTS_MAX_DEPTH) return 0;
+    const int T = sh.threads > 512 ? 512 : sh.threads;
+    const long long total = (long long)sh.W * sh.E;
+    const long long rounds = (total + 2LL * n_cu - 1) / (2LL * n_cu);
+    const long long tiles = ((sh.Npad >> 1) + T - 1) / T;
+    long long chunk = 100000 / (9 * rounds * (tiles > 0 ? tiles : 1) * ((1LL << sh.lmax) - 1));
+    if (chunk > 16384) chunk = 16384;
+    if (chunk < 4) chunk = 4;
+    if (sw.nuts_chunk >= 1 && sw.nuts_chunk < chunk) chunk = sw.nuts_chunk;   // a shorter chunk (tests of the chunk boundary at few steps)
+    return (int)chunk;
+}
+
 // more proposals than CUs: NP per workgroup share one pass over the training set (same block size: same bits)
 int ens_half_np(int threads, int d, long long total, bool hist_mode, int n_cu, const EnsSwitches& sw) {
     const int db = dim_bucket(d);
@@ -161,6 +180,12 @@ EnsRoute ens_route(const EnsShape& sh, int n_cu, const EnsSwitches& sw, bool gro
     if (sh.all_hmc) {
         r.chunk = ens_hmc_chunk(sh, n_cu, sw);
         r.path = r.chunk > 0 ? 5 : -1;                      // the factors and weights exceed the LDS, or no dimension bucket
+        return r;
+    }
+    // An all-NUTS set: ens_nuts_kernel or nothing, as for HMC.
+    if (sh.all_nuts) {
+        r.chunk = ens_nuts_chunk(sh, n_cu, sw);
+        r.path = r.chunk > 0 ? 6 : -1;
         return r;
     }
     if (sh.W < 2 && !sh.all_gauss) { r.path = -1; return r; }   // a red-blue move needs a complementary half
@@ -201,19 +226,19 @@ EnsRoute ens_route(const EnsShape& sh, int n_cu, const EnsSwitches& sw, bool gro
 // ---- host-only debug hook (tests/test_ens_plan_host.py, tools/ens_plan_walk.cpp): the plan of a shape under the current
 // environment as integers; returns their count.  shape: the fields of EnsShape in declaration order (W, E, d, Npad, generic, ymap,
 // threads, chunk_cap, stream_grid, has_hist, stream_ok, mh_ok, has_de, all_gauss, all_hmc, factors, n_moves, lmax, mh_lds, hmc_lds,
-// has_stream), missing ones as a new handle has them.  threads <= 0: the creation plan's; chunk_cap <= 0: a handle as ens_create
+// has_stream, all_nuts, nuts_lds), missing ones as a new handle has them.  threads <= 0: the creation plan's; chunk_cap <= 0: a handle as ens_create
 // leaves it -- chunk_cap and stream_grid from the creation plan, history buffers where stream_grid > 0, stream_ok only with them.
 // out: [0, 3) creation plan (threads, chunk_cap, stream_grid), [3] point pairs per lane, [4, 13) group blocking (ok, Q, G, NG, RT,
 // tpm, ltw, KS, LDS bytes), [13] MH chunk, [14] HMC chunk, [15, 17) proposals per workgroup of the two half-step launches of a
 // step, [17, 23) route (path, chunk, pair, place, graph, graph steps), [23] path when the group kernel's buffers cannot be had,
 // [24, 26) spin limit of ens_stream_kernel / ens_pair_kernel and of ens_group_kernel, [26] graph replay of the sharded run.
 extern "C" int alabi_debug_ens_plan(const int* shape, int n_shape, int n_cu, long long* out, int cap) {
-    enum { NSHAPE = 21, NOUT = 27 };
+    enum { NSHAPE = 23, NOUT = 27 };
     EnsShape sh;
     sh.stream_ok = sh.mh_ok = sh.has_stream = 1;
     int* const f[NSHAPE] = {&sh.W, &sh.E, &sh.d, &sh.Npad, &sh.generic, &sh.ymap, &sh.threads, &sh.chunk_cap, &sh.stream_grid, &sh.has_hist,
                             &sh.stream_ok, &sh.mh_ok, &sh.has_de, &sh.all_gauss, &sh.all_hmc, &sh.factors, &sh.n_moves, &sh.lmax, &sh.mh_lds,
-                            &sh.hmc_lds, &sh.has_stream};
+                            &sh.hmc_lds, &sh.has_stream, &sh.all_nuts, &sh.nuts_lds};
     for (int i = 0; shape && i < n_shape && i < NSHAPE; ++i) *f[i] = shape[i];
     if (sh.W < 1 || sh.E < 1 || sh.d < 1 || sh.Npad < 1 || n_cu < 1) return 0;
     const EnsSwitches sw = ens_switches();

@@ -15,7 +15,7 @@ namespace alabi {
 //
 // When a switch takes effect:
 //   handle creation (alabi_ens_create*)           THREADS, CHUNK, STREAM
-//   every alabi_ens_run                           GROUP, GROUP_G16, GRAPH, GRAPH_STEPS, MH, MH_CHUNK, HMC_CHUNK, SPIN_LIMIT, MULTI
+//   every alabi_ens_run                           GROUP, GROUP_G16, GRAPH, GRAPH_STEPS, MH, MH_CHUNK, HMC_CHUNK, NUTS_CHUNK, SPIN_LIMIT, MULTI
 //   every other entry that launches a half step   MULTI (alabi_ens_half_step*, alabi_ens_step_with_randoms*, the sharded run)
 //   once per handle, latched                      PAIR, PLACE: at the first run that considers the pair kernel / the placement,
 //                                                 from the switches of that call (alabi_ens::pair_state, ::place_state)
@@ -40,6 +40,7 @@ struct EnsSwitches {
     long long chunk = 0;          // ALABI_ENS_CHUNK: a shorter chunk, 2 ... (tests of the chunk boundary at few steps)
     long long mh_chunk = 0;       // ALABI_ENS_MH_CHUNK: a shorter ens_mh_kernel launch, 1 ...
     long long hmc_chunk = 0;      // ALABI_ENS_HMC_CHUNK: a shorter ens_hmc_kernel launch, 1 ...
+    long long nuts_chunk = 0;     // ALABI_ENS_NUTS_CHUNK: a shorter ens_nuts_kernel launch, 1 ...
 };
 EnsSwitches ens_switches();
 
@@ -71,9 +72,15 @@ struct EnsShape {
     int lmax = 1;           // largest leapfrog count of the table (HMC)
     int mh_lds = 0, hmc_lds = 0;                         // dynamic LDS bytes of ens_mh_kernel / ens_hmc_kernel for this table
     int has_stream = 0;     // the call was given a stream (the null stream cannot capture, and is kept off the persistent kernels)
+    int all_nuts = 0;       // every move of the table is a NUTS move (kind 7); lmax is then the table's largest max_depth
+    int nuts_lds = 0;       // dynamic LDS bytes of ens_nuts_kernel for this table
 };
 inline int ens_mh_lds_bytes(int n_moves, int d) { return n_moves * d * d * (int)sizeof(double); }
 inline size_t ens_hmc_lds_bytes(int n_moves, int d, int Npad) { return ((size_t)n_moves * d * (d | 1) + (size_t)Npad) * sizeof(double); }
+// ens_nuts_kernel: the same plus the U-turn checkpoints of a subtree, [2][ALABI_NUTS_MAX_DEPTH][64] doubles
+inline size_t ens_nuts_lds_bytes(int n_moves, int d, int Npad) {
+    return ens_hmc_lds_bytes(n_moves, d, Npad) + (size_t)2 * ALABI_NUTS_MAX_DEPTH * 64 * sizeof(double);
+}
 
 // ---- creation: workgroup size of the half-step kernels, steps the draw buffers hold, workgroups per ensemble of the persistent
 // kernel (0: no persistent-kernel buffers -- more ensembles than CUs, or ALABI_ENS_STREAM=0)
@@ -92,9 +99,10 @@ struct GroupPlan {
 };
 GroupPlan ens_group_plan(const EnsShape& sh, int n_cu, const EnsSwitches& sw);
 
-// Steps per launch of ens_mh_kernel / ens_hmc_kernel, 0: the table does not run on that kernel
+// Steps per launch of ens_mh_kernel / ens_hmc_kernel / ens_nuts_kernel, 0: the table does not run on that kernel
 int ens_mh_chunk(const EnsShape& sh, int n_cu, const EnsSwitches& sw);
 int ens_hmc_chunk(const EnsShape& sh, int n_cu, const EnsSwitches& sw);
+int ens_nuts_chunk(const EnsShape& sh, int n_cu, const EnsSwitches& sw);
 
 // Proposals per workgroup (1, 2, 4) of a half-step launch of `total` proposals over all ensembles; hist_mode: the sharded
 // run's history mode, always 1
@@ -105,7 +113,8 @@ int ens_half_np(int threads, int d, long long total, bool hist_mode, int n_cu, c
 //        1  persistent kernel: ens_stream_kernel, or ens_pair_kernel where `pair` holds and the launcher could allocate
 //        3  ens_group_kernel
 //        4  ens_mh_kernel, `chunk` steps per launch        5  ens_hmc_kernel, `chunk` steps per launch
-//       -1  refused (ALABI_BAD_ARGUMENT): an HMC table that does not fit, or a red-blue table on one walker
+//        6  ens_nuts_kernel, `chunk` transitions per launch
+//       -1  refused (ALABI_BAD_ARGUMENT): an HMC or NUTS table that does not fit, or a red-blue table on one walker
 // The plan says what is wanted; a launcher that allocates says whether it could be had.  The group kernel's hand-off buffers
 // (ens_group_buffers): when they cannot be had the caller asks again with group_allowed = false.  The pair kernel's proposals
 // (ens_pair_ready) and the placement counters (ens_place_ready): `pair` and `place` are the rules alone, each latched by its
@@ -113,7 +122,7 @@ int ens_half_np(int threads, int d, long long total, bool hist_mode, int n_cu, c
 // side stream (ens_draw_ahead_ready) are no route: the persistent run draws ahead where they exist.
 struct EnsRoute {
     int path;
-    int chunk;          // paths 4, 5
+    int chunk;          // paths 4, 5, 6
     bool pair, place;   // path 1
     bool graph;         // path 0
     int graph_steps;

@@ -1,5 +1,5 @@
 // Running a chain on an ensemble handle: alabi_ens_run dispatches on the route of ens_plan.hip to one function per way of
-// running (HMC chunks, MH chunks, persistent kernel, one launch per half step with graph replay); alabi_ens_draw and
+// running (HMC and NUTS chunks, MH chunks, persistent kernel, one launch per half step with graph replay); alabi_ens_draw and
 // alabi_ens_half_step* drive single half steps, alabi_ens_restore / alabi_ens_last_state hand back what a persistent call kept.
 #include <cmath>
 #include <cstring>
@@ -98,6 +98,17 @@ int run_hmc_chunks(alabi_ens* e, const RunCall& c, int chunk) {
         if ((st = launch_ens_hmc(e, c.coords, c.logp, c.step0, done, K, c.thin_by, c.chain, c.chain_logp, c.n_accept, 0, 0.0, nullptr, nullptr, c.s)) != ALABI_OK) return st;
     }
     e->hmc_plan[1] = chunk;
+    return ALABI_OK;
+}
+
+// ---- path 6.  An all-NUTS set: every transition of a chunk in one launch of ens_nuts_kernel.
+int run_nuts_chunks(alabi_ens* e, const RunCall& c, int chunk) {
+    int st;
+    for (long long done = 0; done < c.nsteps; done += chunk) {
+        const int K = (int)(c.nsteps - done < chunk ? c.nsteps - done : chunk);
+        if ((st = launch_ens_nuts(e, c.coords, c.logp, c.step0, done, K, c.thin_by, c.chain, c.chain_logp, c.n_accept, nullptr, c.s)) != ALABI_OK) return st;
+    }
+    e->nuts_plan[1] = chunk;
     return ALABI_OK;
 }
 
@@ -331,6 +342,7 @@ int alabi_ens_run(alabi_ens* e, double* coords, double* logp, long long step0, l
     e->last_path = route.path;
     e->last_state_ok = false;
     switch (route.path) {
+        case 6: return run_nuts_chunks(e, c, route.chunk);
         case 5: return run_hmc_chunks(e, c, route.chunk);
         case 4: return run_mh_chunks(e, c, route.chunk);
         case 3: return run_persistent(e, c, true, false, route, sw);
@@ -371,8 +383,8 @@ int alabi_ens_hmc_adapt(alabi_ens* e, double* coords, double* logp, long long st
 
 int alabi_ens_draw(alabi_ens* e, long long step0, int nsteps, double a, void* stream) {
     if (!e || nsteps <= 0 || nsteps > e->chunk_cap || !(a > 1.0)) return ALABI_BAD_ARGUMENT;
-    if (e->W < 2 && !e->all_gauss) return ALABI_BAD_ARGUMENT;         // a red-blue record names a walker of the other half
-    if (e->all_hmc) return ALABI_BAD_ARGUMENT;                        // an HMC step has no record: its draws are made where it runs
+    if (e->W < 2 && !e->all_gauss && !e->all_nuts) return ALABI_BAD_ARGUMENT;   // a red-blue record names a walker of the other half
+    if (e->all_hmc || e->all_nuts) return ALABI_BAD_ARGUMENT;         // an HMC or NUTS step has no record: its draws are made where it runs
     hipStream_t s = as_stream(stream);
     int st;
     if ((st = set_run_state(e, step0, 0, s)) != ALABI_OK) return st;

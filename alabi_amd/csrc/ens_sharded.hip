@@ -318,7 +318,7 @@ static int run_sharded(alabi_ens* e, alabi_comm* c, double* coords, double* logp
 int alabi_ens_run_sharded(alabi_ens* e, alabi_comm* c, double* coords, double* logp, long long step0, long long nsteps,
                           int thin_by, double a, double* chain, double* chain_logp, long long* n_accept, void* stream) {
     if (!e || !c || !coords || !logp || nsteps < 0 || thin_by < 1 || !(a > 1.0) || e->E != 1) return ALABI_BAD_ARGUMENT;
-    if (e->all_hmc) return ALABI_BAD_ARGUMENT;        // an HMC move neither: one workgroup integrates a walker's whole trajectory
+    if (e->all_hmc || e->all_nuts) return ALABI_BAD_ARGUMENT;        // an HMC move neither: one workgroup integrates a walker's whole trajectory
     if (e->has_gauss) return ALABI_BAD_ARGUMENT;      // a Gaussian Metropolis move has no half to share: run replicas instead
     if (!e->gp->computed || !e->gp->has_alpha) return ALABI_NOT_COMPUTED;
     if (c->failed) { g_last_error = "this communicator failed in an earlier sharded run (a peer may still be inside the collective)"; return ALABI_HIP_ERROR; }

@@ -60,5 +60,8 @@ ALABI_HD inline GroupLds group_lds(int KS, int QPAD, int lds_tiles) {
 #define ALABI_HMC_MAX_LDS (128 * 1024)
 // p1 of an HMC row of the move table is n_leapfrog + ln jitter / 512 (ens_grad_device.hpp: hmc_ln_jitter_of)
 ALABI_HD inline int hmc_leapfrog_of(double p1) { return (int)floor(p1); }
+// ---- NUTS kernel (ens_nuts.hip): p1 of a kind-7 row is max_depth + ln jitter / 512, read by the same two functions; the deepest
+// tree has 2^10 - 1 leaves, and the U-turn checkpoints of a subtree [2][ALABI_NUTS_MAX_DEPTH][64] doubles lie in dynamic LDS
+#define ALABI_NUTS_MAX_DEPTH 10
 
 }  // namespace alabi

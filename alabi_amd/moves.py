@@ -36,7 +36,13 @@ Metropolis move --, alone or as a weighted mixture from which ONE move is chosen
   a Metropolis set, a set of HMC moves is ``nwalkers`` independent chains on one workgroup per walker (``ens_hmc_kernel``), any
   ``nwalkers >= 1``; it holds HMC moves only (mixtures of several step sizes and trajectory lengths are the standard cure for
   periodic trajectories) and needs the fused log-probability: no ``prior_fn`` / ``like_fn``, no ``shard``.  The step size and the
-  mass are adapted by a warm-up phase, ``EnsembleSampler.tune_hmc`` (one ``HMCMove``); no NUTS.
+  mass are adapted by a warm-up phase, ``EnsembleSampler.tune_hmc`` (one ``HMCMove``).
+
+* ``NUTSMove(cov, step_size=None, max_depth=8, jitter=None)`` -- the No-U-Turn sampler (multinomial NUTS, Betancourt 2017, as in
+  Stan) on the same gradient and mass matrix: the trajectory length is chosen per transition by doubling a tree of leapfrog steps
+  until it turns back on itself, at most ``2 ** max_depth - 1`` gradient evaluations.  A set of NUTS moves runs on
+  ``ens_nuts_kernel`` under HMC's restrictions; it holds NUTS moves only.  It has no warm-up of its own: tune an ``HMCMove`` and
+  pass what ``tune_hmc`` found.
 
 ``MHMove(proposal_function, ndim=None)`` is emcee's generic Metropolis move: ``proposal_function(coords[W, d], rng) -> (q[W, d],
 log_factors[W])`` is a Python callable, so it runs on a host-driven step loop (one round trip per step: slow by nature), the
@@ -56,13 +62,14 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["StretchMove", "DEMove", "SnookerMove", "WalkMove", "KDEMove", "GaussianMove", "HMCMove", "MHMove", "MoveSet", "parse_moves",
-           "MAX_MOVES", "KIND_STRETCH", "KIND_DE", "KIND_SNOOKER", "KIND_WALK", "KIND_KDE", "KIND_GAUSS", "KIND_HMC", "WALK_MAX_NC",
-           "HMC_MAX_LEAPFROG"]
+__all__ = ["StretchMove", "DEMove", "SnookerMove", "WalkMove", "KDEMove", "GaussianMove", "HMCMove", "NUTSMove", "MHMove", "MoveSet", "parse_moves",
+           "MAX_MOVES", "KIND_STRETCH", "KIND_DE", "KIND_SNOOKER", "KIND_WALK", "KIND_KDE", "KIND_GAUSS", "KIND_HMC", "KIND_NUTS", "WALK_MAX_NC",
+           "HMC_MAX_LEAPFROG", "NUTS_MAX_DEPTH"]
 
 MAX_MOVES = 8                    # ALABI_MAX_MOVES of the library: the table travels in the draw kernel's arguments
-KIND_STRETCH, KIND_DE, KIND_SNOOKER, KIND_WALK, KIND_KDE, KIND_GAUSS, KIND_HMC = 0, 1, 2, 3, 4, 5, 6
+KIND_STRETCH, KIND_DE, KIND_SNOOKER, KIND_WALK, KIND_KDE, KIND_GAUSS, KIND_HMC, KIND_NUTS = 0, 1, 2, 3, 4, 5, 6, 7
 HMC_MAX_LEAPFROG = 64
+NUTS_MAX_DEPTH = 10              # ALABI_NUTS_MAX_DEPTH of the library
 GAUSS_MODES = {"vector": 0, "random": 1, "sequential": 2}
 WALK_MAX_NC = 2048               # rows of a complementary half the walk move's kernel lists hold
 
@@ -272,6 +279,36 @@ class HMCMove:
         return f"HMCMove(cov=<{self.form}>, step_size={self.step_size}, n_leapfrog={self.n_leapfrog}, jitter={self.jitter})"
 
 
+class NUTSMove:
+    """No-U-Turn sampler move: multinomial NUTS (Betancourt 2017, as in Stan) on the gradient of the fused log-probability, in
+    ``HMCMove``'s whitened momentum -- ``cov``, ``step_size`` and ``jitter`` mean what they mean there and are validated alike.  One
+    transition doubles a tree of leapfrog steps, forward or backward by a drawn bit, until the tree turns back on itself (rho . z
+    <= 0 at either end, rho the sum of the tree's momenta), a new subtree turns inside or diverges (energy error beyond 1000; both
+    drop that subtree), or ``max_depth`` doublings (1 ... 10) are done: at most ``2 ** max_depth - 1`` gradient evaluations.  The
+    next state is drawn from the tree's points with weights exp(-energy error), biased towards the newer half; a point outside the
+    open box has weight 0 -- the orbit itself follows the surrogate's smooth extension.  Stan's extra U-turn
+    checks across subtree joints are not built.  There is no warm-up for this move: tune an ``HMCMove`` with
+    ``EnsembleSampler.tune_hmc`` and pass ``NUTSMove(tuning["cov"], step_size=tuning["step_size"])``."""
+
+    def __init__(self, cov, step_size=None, max_depth=8, jitter=None):
+        if isinstance(max_depth, bool) or int(max_depth) != max_depth or not (1 <= int(max_depth) <= NUTS_MAX_DEPTH):
+            raise ValueError(f"NUTSMove: max_depth must be an integer in 1 ... {NUTS_MAX_DEPTH}")
+        self.max_depth = int(max_depth)
+        try:
+            h = HMCMove(cov, step_size=step_size, n_leapfrog=1, jitter=jitter)     # its validation is HMCMove's
+        except ValueError as err:
+            raise ValueError(str(err).replace("HMCMove", "NUTSMove")) from None
+        self.step_size, self.jitter, self.cov, self.form, self._scale, self.ndim = h.step_size, h.jitter, h.cov, h.form, h._scale, h.ndim
+
+    diagonal = HMCMove.diagonal
+    ln_jitter = HMCMove.ln_jitter
+    resolved_step_size = HMCMove.resolved_step_size
+    scale_matrix = GaussianMove.scale_matrix
+
+    def __repr__(self):
+        return f"NUTSMove(cov=<{self.form}>, step_size={self.step_size}, max_depth={self.max_depth}, jitter={self.jitter})"
+
+
 class MHMove:
     """Generic Metropolis move (emcee.moves.MHMove): ``proposal_function(coords[W, d], rng) -> (q[W, d], log_factors[W])`` with
     ``rng`` a ``numpy.random.RandomState``.  A Python callable cannot run on the device: the sampler drives such a set from the
@@ -294,6 +331,8 @@ def _table_row(m, ndim, nc=None):
         return KIND_GAUSS, 0.0 if m.factor is None else float(np.log(m.factor)), float(GAUSS_MODES[m.mode])
     if isinstance(m, HMCMove):
         return KIND_HMC, m.resolved_step_size(ndim), float(m.n_leapfrog) + m.ln_jitter / 512.0
+    if isinstance(m, NUTSMove):
+        return KIND_NUTS, m.resolved_step_size(ndim), float(m.max_depth) + m.ln_jitter / 512.0
     if isinstance(m, MHMove):
         return -1, 0.0, 0.0                        # not a row of the library's table: the host loop runs it
     if isinstance(m, WalkMove):
@@ -313,7 +352,7 @@ class MoveSet:
     """A parsed move set: ``moves`` (this module's objects), normalised ``weights`` and the table the library takes --
     ``kind``, ``cum`` = np.cumsum(w / w.sum()), ``p0`` (a | gamma0 with its default resolved | gammas | s, 0 for all | KDE factor of
     split 0 | ln factor, 0 for None | HMC step size, resolved), ``p1`` (0 | sigma | 0 | 0 | KDE factor of split 1 | mode 0 / 1 / 2 |
-    n_leapfrog + ln jitter / 512).  A Gaussian or HMC move's scale factor travels apart: ``scales()``.  The KDE factors depend on the number of walkers: they are NaN
+    n_leapfrog + ln jitter / 512; a NUTS move: step size and max_depth + ln jitter / 512).  A Gaussian, HMC or NUTS move's scale factor travels apart: ``scales()``.  The KDE factors depend on the number of walkers: they are NaN
     until ``resolve(nwalkers)`` (called by EnsembleSampler, or pass ``nwalkers`` here)."""
 
     def __init__(self, moves, weights, ndim, nwalkers=None):
@@ -358,9 +397,9 @@ class MoveSet:
         return self
 
     def scales(self):
-        """[(k, C [ndim, ndim], diagonal)] for the Gaussian and HMC moves of the table (alabi_ens_set_move_scale, ahead of
+        """[(k, C [ndim, ndim], diagonal)] for the Gaussian, HMC and NUTS moves of the table (alabi_ens_set_move_scale, ahead of
         alabi_ens_set_moves)."""
-        return [(k, m.scale_matrix(self.ndim), m.diagonal) for k, m in enumerate(self.moves) if isinstance(m, (GaussianMove, HMCMove))]
+        return [(k, m.scale_matrix(self.ndim), m.diagonal) for k, m in enumerate(self.moves) if isinstance(m, (GaussianMove, HMCMove, NUTSMove))]
 
     @property
     def has_hmc(self):
@@ -370,6 +409,15 @@ class MoveSet:
     def all_hmc(self):
         """Every member is an HMCMove: independent chains on the surrogate's gradient (ens_hmc_kernel)."""
         return bool(len(self.moves) > 0 and np.all(self.kind == KIND_HMC))
+
+    @property
+    def has_nuts(self):
+        return bool(np.any(self.kind == KIND_NUTS))
+
+    @property
+    def all_nuts(self):
+        """Every member is a NUTSMove: independent chains on the surrogate's gradient (ens_nuts_kernel)."""
+        return bool(len(self.moves) > 0 and np.all(self.kind == KIND_NUTS))
 
     @property
     def has_gauss(self):
@@ -413,7 +461,7 @@ class MoveSet:
 
 def _as_move(obj):
     """This module's move for ``obj``: one of its own, or a foreign object recognised by class name and attributes."""
-    if isinstance(obj, (StretchMove, DEMove, SnookerMove, WalkMove, KDEMove, GaussianMove, HMCMove, MHMove)):
+    if isinstance(obj, (StretchMove, DEMove, SnookerMove, WalkMove, KDEMove, GaussianMove, HMCMove, NUTSMove, MHMove)):
         return obj
     name = type(obj).__name__
     if name == "GaussianMove" and all(hasattr(obj, a) for a in ("cov", "mode", "factor")):
@@ -465,8 +513,11 @@ def parse_moves(moves, ndim):
     if any(isinstance(m, HMCMove) for m in parsed) and not all(isinstance(m, HMCMove) for m in parsed):
         raise ValueError("a move set that holds an HMCMove must consist of HMCMove objects only: mixtures of an HMCMove with other "
                          "kinds of move are not built (ens_hmc_kernel runs a table of HMC moves alone)")
+    if any(isinstance(m, NUTSMove) for m in parsed) and not all(isinstance(m, NUTSMove) for m in parsed):
+        raise ValueError("a move set that holds a NUTSMove must consist of NUTSMove objects only: mixtures of a NUTSMove with other "
+                         "kinds of move are not built (ens_nuts_kernel runs a table of NUTS moves alone)")
     for m in parsed:
-        if isinstance(m, (GaussianMove, HMCMove)):
+        if isinstance(m, (GaussianMove, HMCMove, NUTSMove)):
             m.scale_matrix(int(ndim))              # emcee's ValueError("Dimension mismatch in proposal")
         elif isinstance(m, MHMove) and m.ndim is not None and m.ndim != int(ndim):
             raise ValueError("Dimension mismatch in proposal")

@@ -76,7 +76,9 @@ class EnsembleSampler:
         Neither can be sharded.  An ``HMCMove(cov, step_size, n_leapfrog, jitter)`` -- alone or in a weighted mixture of HMC
         moves -- runs Hamiltonian Monte Carlo on the surrogate's closed-form gradient: independent chains again (any ``nwalkers >=
         1``, ``last_path == "hmc"``, ``ens_hmc_kernel``); it needs the fused log-probability (no ``prior_fn`` / ``like_fn``) and
-        cannot be sharded.  Moves work with ``n_ensembles``
+        cannot be sharded.  A ``NUTSMove(cov, step_size, max_depth, jitter)`` -- alone or in a mixture of NUTS moves -- is the
+        No-U-Turn sampler on the same gradient under the same restrictions (``last_path == "nuts"``, ``ens_nuts_kernel``);
+        ``nuts_stats`` reports its trees.  Moves work with ``n_ensembles``
         > 1 and with host callables; a set holding a ``DEMove`` needs ``nwalkers >= 4``, one holding a ``SnookerMove`` ``nwalkers >=
         6``, a ``WalkMove(s)`` ``2 <= s <= nwalkers // 2``, a ``KDEMove`` ``nwalkers >= 2 ndim + 2`` (and warns below about
         ``8 (ndim + 1)``: few walkers per dimension mean few accepted proposals); each of these runs with one launch per half step
@@ -97,7 +99,7 @@ class EnsembleSampler:
             raise ValueError("ndim does not match the GP")
         if self.nwalkers < 2 * self.ndim and not live_dangerously:
             few = parse_moves(moves, self.ndim)           # looked at here only to see whether the rule applies: a set of
-            if few is None or not (few.all_metropolis or few.all_mh or few.all_hmc):   # such moves have no halves to keep populated
+            if few is None or not (few.all_metropolis or few.all_mh or few.all_hmc or few.all_nuts):   # such moves have no halves to keep populated
                 raise RuntimeError("It is unadvisable to use a red-blue move with fewer walkers than twice the "
                                    "number of dimensions.")
         self.gp = gp
@@ -123,7 +125,8 @@ class EnsembleSampler:
         if self.shard and (self.generic or self.n_ensembles != 1):
             raise ValueError("shard=True needs the fused log-probability (no host callables) and n_ensembles == 1")
         self._move_set = parse_moves(moves, self.ndim)
-        metropolis = self._move_set is not None and (self._move_set.all_metropolis or self._move_set.all_mh or self._move_set.all_hmc)
+        metropolis = self._move_set is not None and (self._move_set.all_metropolis or self._move_set.all_mh or self._move_set.all_hmc or
+                                                     self._move_set.all_nuts)
         if self.nwalkers < 1:
             raise ValueError("nwalkers must be at least 1")
         if self.nwalkers < 2 and not metropolis:
@@ -142,6 +145,13 @@ class EnsembleSampler:
             if self.shard:
                 raise ValueError("shard=True cannot run an HMCMove: the sharded form is not built (a trajectory reads no other "
                                  "walker, so there is nothing to exchange -- run replicas with n_ensembles instead)")
+        if self._move_set is not None and self._move_set.has_nuts:
+            if self.generic:
+                raise ValueError("a NUTSMove needs the gradient of the log-probability, which exists for the fused surrogate only: "
+                                 "a Python prior_fn or like_fn (the host-callback path) has none")
+            if self.shard:
+                raise ValueError("shard=True cannot run a NUTSMove: the sharded form is not built (a tree reads no other walker, so "
+                                 "there is nothing to exchange -- run replicas with n_ensembles instead)")
         self._mh_rng = None
         if self._move_set is not None and self._move_set.multi_partner:
             if self._move_set.has_de and self.nwalkers < 4:
@@ -204,6 +214,7 @@ class EnsembleSampler:
                        "alabi_ens_set_moves")
         self._ens = e
         self._ens_gp_handle = C.c_void_p(h.value)
+        self._nuts_transitions = 0                        # a new handle's NUTS sums start at zero
 
     @property
     def moves(self):
@@ -222,6 +233,31 @@ class EnsembleSampler:
         n = C.c_longlong(0)
         _lib.check(_lib.lib().alabi_ens_kde_singular(self._ens, C.byref(n)), "alabi_ens_kde_singular")
         return int(n.value)
+
+    def nuts_counts(self, reset=False):
+        """alabi_ens_nuts_stats: (counts [E W, 3] int64 -- leaves, depths reached, divergent transitions --, the sum of the leaves'
+        acceptance statistics [E W]) per walker since the handle's last reset."""
+        counts = np.zeros((self.total_walkers, 3), dtype=np.int64)
+        acc = np.zeros(self.total_walkers, dtype=np.float64)
+        if getattr(self, "_ens", None) is not None:
+            _lib.check(_lib.lib().alabi_ens_nuts_stats(self._ens, C.c_void_p(counts.ctypes.data), C.c_void_p(acc.ctypes.data), int(bool(reset))),
+                       "alabi_ens_nuts_stats")
+        if reset:
+            self._nuts_transitions = 0
+        return counts, acc
+
+    @property
+    def nuts_stats(self):
+        """What the NUTS transitions of this sampler's handle did since its last reset (None without a ``NUTSMove``):
+        ``transitions``, ``mean_depth`` (completed doublings per transition), ``leaves_per_transition`` (gradient evaluations),
+        ``divergences`` and ``mean_accept_stat`` (the mean over all leaves of min(1, exp(-energy error)), 0 outside the box)."""
+        if self._move_set is None or not self._move_set.all_nuts:
+            return None
+        counts, acc = self.nuts_counts()
+        n = int(getattr(self, "_nuts_transitions", 0))
+        leaves = int(counts[:, 0].sum())
+        return dict(transitions=n, mean_depth=float(counts[:, 1].sum()) / max(n, 1), leaves_per_transition=leaves / max(n, 1),
+                    divergences=int(counts[:, 2].sum()), mean_accept_stat=float(acc.sum()) / max(leaves, 1))
 
     def _release(self):
         _lib.destroy(getattr(self, "_ens", None), "alabi_ens_destroy", sync=True)
@@ -535,8 +571,11 @@ class EnsembleSampler:
         _lib.check(st, "alabi_ens_run")
         path = C.c_int(0)
         _lib.lib().alabi_ens_last_path(self._ens, C.byref(path))
-        self.last_path = {1: "stream", 3: "group", 4: "metropolis", 5: "hmc"}.get(path.value, "launch-per-half-step")
-        self.last_stream_kernel = {1: "ens_stream_kernel", 3: "ens_group_kernel", 4: "ens_mh_kernel", 5: "ens_hmc_kernel"}.get(path.value)
+        self.last_path = {1: "stream", 3: "group", 4: "metropolis", 5: "hmc", 6: "nuts"}.get(path.value, "launch-per-half-step")
+        self.last_stream_kernel = {1: "ens_stream_kernel", 3: "ens_group_kernel", 4: "ens_mh_kernel", 5: "ens_hmc_kernel",
+                                   6: "ens_nuts_kernel"}.get(path.value)
+        if path.value == 6:
+            self._nuts_transitions = getattr(self, "_nuts_transitions", 0) + nsteps * self.total_walkers
         variant = C.c_int(0)                                  # path 1: one workgroup per list position, or a pair of them
         _lib.lib().alabi_ens_stream_variant(self._ens, C.byref(variant))
         self.last_stream_variant = {0: "single", 1: "pair"}[variant.value] if path.value == 1 else None
@@ -586,6 +625,10 @@ class EnsembleSampler:
         that is not exactly one ``HMCMove``, host callables and ``shard=True`` raise ``ValueError``."""
         from . import hmc_adapt as ha
         from .moves import HMCMove
+        if self._move_set is not None and self._move_set.has_nuts:
+            raise ValueError("tune_hmc adapts an HMCMove, not a NUTSMove (a NUTS warm-up is not built): tune an HMCMove with the same "
+                             'cov, then pass NUTSMove(sm.hmc_tuning["cov"], step_size=sm.hmc_tuning["step_size"]) (hmc_tuning of the sampler, or of '
+                             "the SurrogateModel after run_emcee with hmc_warmup)")
         if self.generic:
             raise ValueError("tune_hmc needs the gradient of the log-probability, which exists for the fused surrogate only: a Python "
                              "prior_fn or like_fn (the host-callback path) has none")

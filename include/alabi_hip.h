@@ -289,7 +289,32 @@ int alabi_ens_set_logp_map(alabi_ens* ens, int kind);
  * and any n_ensembles; alabi_ens_set_stream does not move it, and alabi_ens_run is ALABI_BAD_ARGUMENT where the kernel cannot run
  * (the factors [n][d, d | 1] and the gradient weights [Npad] exceed 128 KB of LDS together).  ALABI_ENS_HMC_CHUNK=k caps the steps
  * of one launch at k, read at every alabi_ens_run; the chunk length changes no bit of the result.  The walker's logp is the
- * caller's and is never recomputed.  alabi_ens_draw and the sharded run refuse such a table. */
+ * caller's and is never recomputed.  alabi_ens_draw and the sharded run refuse such a table.
+ * kind 7 NUTSMove (multinomial No-U-Turn sampler, Betancourt 2017 as in Stan, on the same gradient and in the same whitened
+ * momentum): p0 = step size > 0; p1 = max_depth + q / 512 with max_depth in 1 ... 10 and q as for kind 6.  The factor travels by
+ * alabi_ens_set_move_scale ahead of the table; alabi_ens_set_moves is ALABI_BAD_ARGUMENT for a kind-7 move whose slot has no
+ * factor, for a step size that is not positive and finite, for max_depth outside 1 ... 10 and for a table that mixes kind 7 with
+ * another kind.  One transition of walker x with lp = the caller's logp, g = grad lnp(x), e = p0 f as kind 6: z0 ~ N(0, I), H0 =
+ * -lp + |z0|^2 / 2, both ends of the tree (x, z0, g), rho = z0, proposal x, ln W = 0.  Doubling j = 0 ... max_depth - 1: direction
+ * bit v_j set extends forward from the right end (s = e), otherwise backward from the left end (s = -e), by 2^j leaves; a leaf is
+ * z += (s / 2) C^T g, q += s C z, (lp_q, g) = lnp and its gradient at q, z += (s / 2) C^T g.  Per leaf delta = H0 - (-lp_q +
+ * |z|^2 / 2); divergent iff not (delta > -1000), NaN included: the subtree is dropped and the transition ends; ln w = delta where q
+ * lies in the open box, -inf elsewhere (lnp itself has no box gate); the acceptance statistic a = min(1, exp(delta)) in the box, 0
+ * elsewhere and for a divergent leaf.  With ln w > -inf: ln W' = logaddexp(ln W', ln w) and the leaf becomes the subtree's candidate
+ * iff ln u_leaf < ln w - ln W'.  With the subtree's leaves numbered n = 0, 1, ... as made, the last leaf of every aligned block of
+ * 2^k leaves (k >= 1) tests the block: it turns iff rho_block . z_first <= 0 or rho_block . z_last <= 0 (rho_block the sum of the
+ * block's z), which drops the subtree and ends the transition.  A complete subtree: the proposal becomes its candidate iff ln W' >
+ * -inf and ln u_tree,j < ln W' - ln W; then ln W = logaddexp(ln W, ln W'), rho += rho', the extended end moves, and the tree stops
+ * iff rho . z_left <= 0 or rho . z_right <= 0.  The walker becomes the proposal with the lp and gradient of its leaf; n_accept
+ * grows by 1 when a leaf was taken.  Stan's further U-turn checks across subtree joints are not built.  Draws: Philox counter
+ * (step, global walker id, stream word S + 16 b) -- S = 3, 11 and 12 as kind 6; S = 13, b = 0: bit j of r0 is v_j; S = 14, b = the
+ * leaf's ordinal within the transition (0 ... 2^max_depth - 2): u_leaf = u53(r0, r1); S = 15, b = j: u_tree,j = u53(r0, r1); stream
+ * 2 is not read; streams 0-12 keep their meaning.  Such a table runs on ens_nuts_kernel (path 6 of alabi_ens_last_path) and on
+ * nothing else: one workgroup per walker, every transition of a chunk in one launch, any W >= 1 and any n_ensembles;
+ * alabi_ens_set_stream does not move it, and alabi_ens_run is ALABI_BAD_ARGUMENT where the factors [n][d, d | 1], the gradient
+ * weights [Npad] and the 10 KB of U-turn checkpoints exceed 128 KB of LDS together.  ALABI_ENS_NUTS_CHUNK=k caps the transitions of
+ * one launch at k, read at every alabi_ens_run; the chunk length and call splitting change no bit.  alabi_ens_draw, the sharded
+ * run and alabi_ens_hmc_adapt refuse such a table. */
 int alabi_ens_set_moves(alabi_ens* ens, int n, const int* kind, const double* cum, const double* p0, const double* p1);
 
 /* The scale factor of slot k (0 <= k < 8) of the move table, for the Gaussian move that the NEXT alabi_ens_set_moves puts there
@@ -304,6 +329,14 @@ int alabi_ens_mh_plan(alabi_ens* ens, int* out /* host [4] */);
 /* ens_hmc_kernel's last launch: out[4] = workgroup size, steps per launch, LDS bytes, 1 if a lane takes more than one training
  * point per pass (Npad exceeds the workgroup). */
 int alabi_ens_hmc_plan(alabi_ens* ens, int* out /* host [4] */);
+/* ens_nuts_kernel's last launch: out[4] = workgroup size, transitions per launch, LDS bytes, 1 if a lane takes more than one
+ * training point per pass (Npad exceeds the workgroup). */
+int alabi_ens_nuts_plan(alabi_ens* ens, int* out /* host [4] */);
+/* Per-walker sums of the handle's NUTS transitions since the last reset (they belong to the handle and start at zero with its
+ * first kind-7 table): counts_host [E*W, 3] = leaves made, depths reached (completed doublings), divergent transitions;
+ * accept_host [E*W] = the sum of the acceptance statistic a over all leaves -- over the leaves it is what a warm-up averages.
+ * reset != 0 zeroes them after the copy.  Synchronises the device.  Transitions of alabi_ens_step_with_randoms_nuts count too. */
+int alabi_ens_nuts_stats(alabi_ens* ens, long long* counts_host /* host [E*W, 3] */, double* accept_host /* host [E*W] */, int reset);
 /* HMC warm-up: nsteps steps of a table of exactly ONE kind-6 move on ens_hmc_adapt_kernel -- ens_hmc_kernel's launch shape,
  * arithmetic, draws and accept rule -- with a step size per walker adapted by dual averaging (Hoffman & Gelman 2014, algorithm 5;
  * tests/hmc_adapt_numpy.py states it).  da_state device [E*W, 5] doubles in/out: m (steps since the last restart), H-bar, ln e,
@@ -359,7 +392,8 @@ int alabi_ens_set_stream(alabi_ens* ens, int enabled);
  * registers (ens_stream_kernel: N <= 2048, small d), 3 = persistent group kernel (ens_group_kernel: training set
  * partitioned over groups of workgroups, kernel sums on the matrix cores; d <= 30), 4 = ens_mh_kernel (a table of Gaussian moves
  * alone: one workgroup per walker; alabi_ens_set_stream(ens, 0) sends such a table to path 0), 5 = ens_hmc_kernel (a table of HMC
- * moves: one workgroup per walker; it has no other path), 0 = one launch per half step. */
+ * moves: one workgroup per walker; it has no other path), 6 = ens_nuts_kernel (a table of NUTS moves: likewise), 0 = one launch per
+ * half step. */
 int alabi_ens_last_path(alabi_ens* ens, int* path /* host */);
 /* Which persistent kernel the last alabi_ens_run of path 1 launched: 0 = ens_stream_kernel (one workgroup per list position),
  * 1 = ens_pair_kernel (two per list position, which evaluate both outcomes of a pending update; chosen where 2 ceil(W/2) E
@@ -562,6 +596,20 @@ int alabi_ens_export_gauss_draws(alabi_ens* ens, double* f, int* coord, double* 
 int alabi_ens_step_with_randoms_hmc(alabi_ens* ens, double* coords, double* logp, int k_move, double e, const double* z,
                                     const double* u_acc, long long* n_accept, void* stream);
 int alabi_ens_export_hmc_draws(alabi_ens* ens, long long step, int* move, double* e, double* z, double* u_acc, void* stream);
+/* Test entries of the NUTS move (kind 7 of alabi_ens_set_moves; the table must be all NUTS; all arrays on the device, keyed by
+ * walker id).
+ * alabi_ens_step_with_randoms_nuts (n_ensembles == 1): one transition of move k_move of the table, max_depth its own, from injected
+ * draws -- e the step size with the jitter applied, z0 [W, d], dir [W] uint32 direction words (bit j: doubling j goes forward),
+ * u_leaf [W, 2^max_depth - 1] by the leaf's ordinal within the transition, u_tree [W, max_depth].  trace [W, 4] int32 or null:
+ * depth reached (completed doublings), leaves made, stop reason (0 max_depth, 1 U-turn of the tree, 2 U-turn inside a subtree,
+ * 3 divergent) and 1 if a leaf was taken.
+ * alabi_ens_export_nuts_draws: the production draws of global step `step` -- move [E] int32 and e [E] per ensemble, z0 [E*W, d],
+ * dir [E*W] uint32, u_leaf [E*W, 2^max_depth - 1] and u_tree [E*W, max_depth] for the max_depth (1 ... 10) the caller names. */
+int alabi_ens_step_with_randoms_nuts(alabi_ens* ens, double* coords, double* logp, int k_move, double e, const double* z0,
+                                     const unsigned* dir, const double* u_leaf, const double* u_tree, int* trace /* or null */,
+                                     long long* n_accept, void* stream);
+int alabi_ens_export_nuts_draws(alabi_ens* ens, long long step, int max_depth, int* move, double* e, double* z0, unsigned* dir,
+                                double* u_leaf, double* u_tree, void* stream);
 
 /* Nested sampling (dynesty's NestedSampler / DynamicNestedSampler with sample="rwalk" as driven by
  * SurrogateModel.run_dynesty, alabi/core.py:2417-2787, likelihood = surrogate_log_likelihood core.py:1446-1508, prior =

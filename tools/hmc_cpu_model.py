@@ -4,7 +4,8 @@ target, in plain NumPy (no GPU, no library; NOT a GPU timing).
 Target: a d-dimensional Gaussian with standard deviations log-spaced from 0.1 to 1 (d = 32 by default), 64 walkers started from
 exact draws.  Moves: the stretch move (a = 2, emcee's red-blue halves), and the rule of alabi_amd.moves.HMCMove with identity mass
 (eps = 0.10, 16 leapfrog steps), with the diagonal covariance as ``cov`` (eps = 0.71, 4 leapfrog steps) and MALA with it (eps =
-0.71, 1 step).  tau: the mean over coordinates of oracle.autocorr_oracle.integrated_time of the chain [steps, walkers, d].
+0.71, 1 step), and the rule of alabi_amd.moves.NUTSMove (tests/nuts_numpy.py: multinomial NUTS) with the diagonal covariance (eps =
+0.71, max_depth 8), whose evaluations per step are the leaves it made per transition.  tau: the mean over coordinates of oracle.autocorr_oracle.integrated_time of the chain [steps, walkers, d].
 Cost per independent sample in kernel sums: max(tau, 1) x (evaluations per step) x --grad-cost for a value-and-gradient evaluation
 (4.1 value evaluations, measured on the device at C3: profiles/moves_step_hmc.txt), x 1 for a value evaluation.
 
@@ -18,6 +19,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))   # the NumPy statement of NUTS
 from oracle.autocorr_oracle import integrated_time  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -26,6 +28,7 @@ ap.add_argument("--walkers", type=int, default=64)
 ap.add_argument("--seed", type=int, default=1)
 ap.add_argument("--stretch-steps", type=int, default=40000)
 ap.add_argument("--hmc-steps", type=int, default=4000)
+ap.add_argument("--nuts-steps", type=int, default=1000)
 ap.add_argument("--grad-cost", type=float, default=4.1)
 args = ap.parse_args()
 d, W = args.d, args.walkers
@@ -70,6 +73,21 @@ def hmc(x, nsteps, rs, c, eps, L):
     return chain, nacc / (nsteps * W)
 
 
+def nuts(x, nsteps, rs, c, eps, max_depth):
+    """alabi_amd.moves.NUTSMove's rule (tests/nuts_numpy.py) with the diagonal scale factor c; the box is far away."""
+    import hmc_numpy as hm
+    import nuts_numpy as nn
+    tgt = hm.GaussianTarget(np.zeros(d), np.diag(sd ** 2), np.stack([-1e6 * np.ones(d), 1e6 * np.ones(d)], axis=1))
+    lp, g, _ = tgt.value_grad(x)
+    chain = np.empty((nsteps, W, d)); leaves = taken = 0
+    for t in range(nsteps):
+        x, lp, g, trace, _ = nn.nuts_step_arrays(tgt, x, lp, g, np.diag(c), eps, rs.randn(W, d), rs.randint(0, 1 << 30, size=W),
+                                                 rs.rand(W, (1 << max_depth) - 1), rs.rand(W, max_depth), max_depth)
+        leaves += trace[:, 1].sum(); taken += trace[:, 3].sum()
+        chain[t] = x
+    return chain, taken / (nsteps * W), leaves / (nsteps * W)
+
+
 out = {"target": f"{d}-D Gaussian, standard deviations log-spaced 0.1 ... 1", "walkers": W, "seed": args.seed,
        "stretch_steps": args.stretch_steps, "hmc_steps": args.hmc_steps, "note": "CPU model in NumPy, not a GPU number"}
 start = lambda rs: rs.randn(W, d) * sd  # noqa: E731
@@ -81,8 +99,14 @@ for name, c, eps, L in (("hmc_identity_mass_eps0.10_L16", np.ones(d), 0.10, 16),
     rs = np.random.RandomState(args.seed + 1)
     ch, acc = hmc(start(rs), args.hmc_steps, rs, c, eps, L)
     out[name] = {"tau": float(np.mean(integrated_time(ch))), "acceptance": float(acc), "evaluations_per_step": L, "cost_factor": args.grad_cost}
+rs = np.random.RandomState(args.seed + 2)
+ch, acc, leaves = nuts(start(rs), args.nuts_steps, rs, sd, 0.71, 8)
+out["nuts_diag_cov_eps0.71_depth8"] = {"tau": float(np.mean(integrated_time(ch))), "moved_fraction": float(acc), "nuts_steps": args.nuts_steps,
+                                       "evaluations_per_step": float(leaves), "cost_factor": args.grad_cost,
+                                       "note": "NOT a GPU number: leaves per transition and tau from the NumPy model"}
 for k, v in out.items():
     if isinstance(v, dict) and "tau" in v:
+        v["gradient_evaluations_per_independent_sample"] = max(v["tau"], 1.0) * v["evaluations_per_step"] if k != "stretch" else None
         v["kernel_sums_per_independent_sample"] = max(v["tau"], 1.0) * v["evaluations_per_step"] * v["cost_factor"]
 for k, v in out.items():
     if isinstance(v, dict) and "tau" in v:
