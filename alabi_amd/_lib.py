@@ -80,6 +80,8 @@ SIGNATURES = {
     "alabi_ens_nuts_plan": (_i, [_vp, _pi]),
     "alabi_ens_nuts_stats": (_i, [_vp, _vp, _vp, _i]),
     "alabi_ens_hmc_adapt": (_i, [_vp, _vp, _vp, _ll, _ll, _i, _vp, _pd, _vp, _vp, _vp, _vp, _vp]),
+    "alabi_ens_nuts_adapt": (_i, [_vp, _vp, _vp, _ll, _ll, _i, _vp, _pd, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "alabi_ens_find_step_size": (_i, [_vp, _vp, _vp, _ll, _i, _vp, _vp, _vp]),
     "alabi_ens_log_prob_grad": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "alabi_ens_maximize": (_i, [_vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "alabi_ens_log_prob_hessian": (_i, [_vp, _vp, _i, _vp, _vp]),

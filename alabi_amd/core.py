@@ -1081,8 +1081,11 @@ class SurrogateModel(object):
         None) runs ``EnsembleSampler.tune_hmc`` for n steps in front of the run -- Stan-style warm-up of the step size and the mass
         matrix; what it found is ``sm.hmc_tuning`` --; with any other move set these keys raise ``ValueError``.  ``alabi_amd.moves.NUTSMove(cov,
         step_size=None, max_depth=8, jitter=None)`` is the No-U-Turn sampler on the same gradient under the same restrictions: the
-        trajectory length is chosen per transition; ``sm.nuts_stats`` says afterwards how deep the trees went (tune an ``HMCMove``
-        first and pass ``NUTSMove(sm.hmc_tuning["cov"], step_size=sm.hmc_tuning["step_size"])``).  Any other emcee move raises ``NotImplementedError`` -- in
+        trajectory length is chosen per transition; ``sm.nuts_stats`` says afterwards how deep the trees went.  With a single ``NUTSMove``,
+        ``sampler_kwargs["nuts_warmup"] = n`` (optionally ``"nuts_target_accept"``, default 0.8, ``"nuts_metric"``: "diag", "dense" or None,
+        and ``"nuts_init_step_size"``: "search" or None) runs ``EnsembleSampler.tune_nuts`` for n transitions in front of the run --
+        Stan's step-size search, dual averaging on the tree's mean acceptance statistic and the windowed mass matrix; what it found
+        is ``sm.nuts_tuning`` --; with any other move set these keys raise ``ValueError``, as the ``hmc_*`` keys do with a ``NUTSMove``.  Any other emcee move raises ``NotImplementedError`` -- in
         particular emcee's ``DESnookerMove``, whose arithmetic is not the published rule; none of ``DEMove``, ``SnookerMove``,
         ``WalkMove``, ``KDEMove``, ``GaussianMove``, ``MHMove`` can be combined with ``"shard": True``.
 
@@ -1105,15 +1108,27 @@ class SurrogateModel(object):
         hmc_tune_kw = {name: kw.pop(key) for key, name in (("hmc_target_accept", "target_accept"), ("hmc_metric", "metric")) if key in kw}
         if hmc_warmup is not None or hmc_tune_kw:
             if move_set is not None and move_set.has_nuts:
-                raise ValueError('sampler_kwargs "hmc_warmup", "hmc_target_accept" and "hmc_metric" adapt an HMCMove, not a NUTSMove (a '
-                                 'NUTS warm-up is not built): tune an HMCMove first, then pass NUTSMove(sm.hmc_tuning["cov"], '
-                                 'step_size=sm.hmc_tuning["step_size"])')
+                raise ValueError('sampler_kwargs "hmc_warmup", "hmc_target_accept" and "hmc_metric" adapt an HMCMove, not a NUTSMove: a '
+                                 'NUTSMove has "nuts_warmup" (EnsembleSampler.tune_nuts).  The older route still works -- tune an HMCMove '
+                                 'first, then pass NUTSMove(sm.hmc_tuning["cov"], step_size=sm.hmc_tuning["step_size"])')
             if move_set is None or len(move_set) != 1 or not move_set.all_hmc:
                 raise ValueError('sampler_kwargs "hmc_warmup", "hmc_target_accept" and "hmc_metric" need sampler_kwargs["moves"] to be '
                                  'a single HMCMove: its step size and mass matrix are what the warm-up adapts')
             if hmc_warmup is None or int(hmc_warmup) < 1:
                 raise ValueError('sampler_kwargs["hmc_warmup"] must be a positive number of warm-up steps')
             hmc_warmup = int(hmc_warmup)
+        # NUTS warm-up (EnsembleSampler.tune_nuts), likewise
+        nuts_warmup = kw.pop("nuts_warmup", None)
+        nuts_tune_kw = {name: kw.pop(key) for key, name in (("nuts_target_accept", "target_accept"), ("nuts_metric", "metric"),
+                                                            ("nuts_init_step_size", "init_step_size")) if key in kw}
+        if nuts_warmup is not None or nuts_tune_kw:
+            if move_set is None or len(move_set) != 1 or not move_set.all_nuts:
+                raise ValueError('sampler_kwargs "nuts_warmup", "nuts_target_accept", "nuts_metric" and "nuts_init_step_size" need '
+                                 'sampler_kwargs["moves"] to be a single NUTSMove: its step size and mass matrix are what the warm-up '
+                                 'adapts (an HMCMove has "hmc_warmup")')
+            if nuts_warmup is None or int(nuts_warmup) < 1:
+                raise ValueError('sampler_kwargs["nuts_warmup"] must be a positive number of warm-up transitions')
+            nuts_warmup = int(nuts_warmup)
         if kw.get("shard", False) and move_set is not None and (move_set.has_gauss or move_set.all_mh):
             raise ValueError('sampler_kwargs={"shard": True} cannot run a GaussianMove or an MHMove: a Metropolis proposal reads no '
                              'other walker, so there is nothing to exchange -- run replicas instead')
@@ -1178,6 +1193,9 @@ class SurrogateModel(object):
             if hmc_warmup is not None:
                 start = self.emcee_sampler.tune_hmc(start, nwarmup=hmc_warmup, **hmc_tune_kw).coords
                 self.hmc_tuning = self.emcee_sampler.hmc_tuning
+            if nuts_warmup is not None:
+                start = self.emcee_sampler.tune_nuts(start, nwarmup=nuts_warmup, **nuts_tune_kw).coords
+                self.nuts_tuning = self.emcee_sampler.nuts_tuning
             self.emcee_sampler.run_mcmc(start, self.nsteps, **run_kwargs)
             self.nuts_stats = getattr(self.emcee_sampler, "nuts_stats", None)      # None without a NUTSMove
             self.emcee_runtime += time.time() - t0

@@ -464,6 +464,13 @@ int launch_ens_nuts(alabi_ens* e, double* coords, double* logp, long long step0,
                     double* chain_logp, long long* n_accept, const NutsInject* inj, hipStream_t s);
 int launch_ens_nuts_export(alabi_ens* e, long long step, int depth, int* move, double* e_out, double* z, unsigned* dir, double* u_leaf,
                            double* u_tree, hipStream_t s);
+// ens_nuts_adapt.hip: ens_nuts_kernel with a dual-averaged step size per walker (da_state, par, accept_stat as launch_ens_hmc_adapt;
+// counts [E*W, 3] and accept_sum [E*W] the caller's), and the initial step-size search of move k_move (ln_e [E*W] in/out)
+int launch_ens_nuts_adapt(alabi_ens* e, double* coords, double* logp, long long step0, long long done0, int K, int thin_by, double* chain,
+                          double* chain_logp, long long* n_accept, double* da_state, const double* par, long long* counts,
+                          double* accept_sum, double* accept_stat, hipStream_t s);
+int launch_ens_step_search(alabi_ens* e, const double* coords, const double* logp, long long step, int k_move, double* ln_e, int* iters,
+                           hipStream_t s);
 int launch_ens_lnprob(alabi_ens* e, const double* coords, int nwalkers, double* logp, int gate_box, hipStream_t s);
 int launch_ens_propose(alabi_ens* e, const HalfArgs& args, int nblocks, int gate_box, double* q, double* like, hipStream_t s);
 int launch_ens_accept(alabi_ens* e, const HalfArgs& args, int count, const double* q, const double* lp_new, hipStream_t s);

@@ -1,6 +1,8 @@
 // No-U-Turn sampler ensemble for gfx950: W independent chains of multinomial NUTS (Betancourt 2017, as in Stan) on the surrogate's
 // closed-form gradient (kind 7 of the move table, alabi_amd.moves.NUTSMove; tests/nuts_numpy.py is the CPU statement).
 //
+// The kernel's body is nuts_walker_transitions<D, GENERIC, false> of ens_nuts_device.hpp, which ens_nuts_adapt_kernel
+// (ens_nuts_adapt.hip, the warm-up) instantiates with ADAPT = true; what follows describes both.
 // ens_nuts_kernel has ens_hmc_kernel's launch shape: ONE workgroup per walker (E W of them, any count; no spin loops, no atomics,
 // no traffic between workgroups, so trees of different sizes cost load imbalance and nothing else) and every transition of a chunk
 // in one launch.  Wave 0 keeps the tree, lane k coordinate k, one double per lane each: the two ends (q, z, g), the point being
@@ -43,11 +45,11 @@
 // 128 KB (ens_nuts_lds_bytes; alabi_ens_run refuses a table that needs more), plus 1.2 KB static.
 // hipcc -Rpass-analysis=kernel-resource-usage for ens_nuts_kernel, VGPRs / scratch bytes per lane (squared exponential | the other
 // families), two waves per SIMD throughout (__launch_bounds__(512) leaves 256 VGPRs per lane):
-//   D = 1: 236 / 36 | 241 / 0     D = 5: 238 / 36 | 251 / 0     D = 10: 242 / 36 | 255 / 28    D = 16: 254 / 36 | 255 / 44
-//   D = 20: 256 / 60 | 255 / 76   D = 24: 256 / 68 | 256 / 116  D = 32: 256 / 112 | 256 / 168
-//   D = 48: 256 / 244 | 256 / 304 D = 64: 256 / 360 | 256 / 436
+//   D = 1: 234 / 36 | 239 / 0   D = 5: 236 / 36 | 249 / 0   D = 10: 240 / 36 | 255 / 20
+//   D = 16: 252 / 36 | 254 / 44   D = 20: 256 / 52 | 254 / 76   D = 24: 256 / 52 | 256 / 100
+//   D = 32: 256 / 108 | 256 / 168   D = 48: 256 / 236 | 256 / 304   D = 64: 256 / 360 | 256 / 428
 // The tree is 16 doubles per lane on top of ens_hmc_kernel's 180 to 230 VGPRs, live across the evaluation: from D = 20 on (from
-// D = 8 for the other families) a part of it waits in scratch while the training set is read, stored once before and loaded once
+// D = 10 for the other families) a part of it waits in scratch while the training set is read, stored once before and loaded once
 // after an evaluation.  Static LDS 1168 bytes at every bucket.
 #include <cstdlib>
 #include "ens_nuts_device.hpp"
@@ -61,159 +63,7 @@ ens_nuts_kernel(NutsArgs a) {
     __shared__ double qs_s[ALABI_MAX_DIM], g_s[ALABI_MAX_DIM];
     __shared__ double scratch[16];
     __shared__ int stop_s;
-    const HmcArgs& p = a.h;
-    const int tid = threadIdx.x, T = blockDim.x, d = p.lg.d, ld = d | 1;
-    const int w = blockIdx.x;                                       // global walker id
-    const uint32_t g0 = (uint32_t)((w / p.W) * p.W);                // global id of the ensemble's walker 0
-    double* w_s = nuts_lds + (size_t)p.mt.n * d * ld;
-    double* ck_z = w_s + p.lg.Npad;                                 // [ALABI_NUTS_MAX_DEPTH][64] z of the block's first leaf
-    double* ck_r = ck_z + ALABI_NUTS_MAX_DEPTH * 64;                // [ALABI_NUTS_MAX_DEPTH][64] running rho' including that leaf
-    for (int idx = tid; idx < p.mt.n * d * d; idx += T) {
-        const int m = idx / (d * d), rc = idx - m * d * d;
-        nuts_lds[(size_t)m * d * ld + (rc / d) * ld + (rc % d)] = p.scale_C[idx];
-    }
-    const bool in = tid < d;                                        // wave 0 keeps the walker: lane k its coordinate k
-    double xv = 0.0, inv_len = 0.0, lo = 0.0, hi = 0.0;
-    if (in) {
-        xv = p.coords[(size_t)w * d + tid];
-        inv_len = p.lg.consts[tid];
-        lo = p.lg.consts[ALABI_MAX_DIM + tid];
-        hi = p.lg.consts[2 * ALABI_MAX_DIM + tid];
-    }
-    double lp_old = p.logp[w];
-    long long nacc = 0, n_leaves = 0, n_depth = 0, n_div = 0;
-    double a_sum = 0.0;
-    if (tid < 64) {
-        if (a.counts) { n_leaves = a.counts[(size_t)w * 3]; n_depth = a.counts[(size_t)w * 3 + 1]; n_div = a.counts[(size_t)w * 3 + 2]; }
-        if (a.accept_sum) a_sum = a.accept_sum[w];
-    }
-    const uint32_t k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
-    const size_t WT = (size_t)gridDim.x;
-    double gx, lp_unused;
-    lp_grad_eval<D, GENERIC>(p.lg, w_s, qs_s, g_s, scratch, xv, inv_len, lp_unused, gx);   // its first barrier covers the factors
-    for (int t = 0; t < p.K; ++t) {
-        const long long step = p.step0 + t;
-        const uint32_t s_lo = (uint32_t)step, s_hi = (uint32_t)((unsigned long long)step >> 32);
-        const int mi = p.inj_z ? p.inj_k : hmc_step_move(p.mt, s_lo, s_hi, g0, k0, k1);   // workgroup-uniform
-        double mp0, mp1;
-        hmc_move_params(p.mt, mi, mp0, mp1);
-        const int Dmax = hmc_leapfrog_of(mp1);                       // p1 = max_depth + ln jitter / 512
-        const int nleaf_max = (1 << Dmax) - 1;
-        const double* Cs = nuts_lds + (size_t)mi * d * ld;
-        const int diagonal = (p.scale_diag >> mi) & 1;
-        // wave 0's tree
-        double e = 0.0, s = 0.0, H0 = 0.0, lnW = 0.0, lnWs = 0.0, lpp = lp_old, lpc = 0.0, lpq = 0.0;
-        double qL = xv, zL = 0.0, gL = gx, qR = xv, zR = 0.0, gR = gx, rho = 0.0, rhoS = 0.0;
-        double q = xv, z = 0.0, g = gx, qp = xv, gp = gx, qc = xv, gc = gx;
-        uint32_t dirw = 0;
-        int j = 0, n = 0, leaves = 0, depth = 0, reason = ALABI_NUTS_STOP_DEPTH, taken = 0;
-        bool fwd = false;
-        if (tid < 64) {
-            if (p.inj_z) {
-                e = p.inj_e;
-                zL = in ? p.inj_z[(size_t)w * d + tid] : 0.0;
-                dirw = a.inj_dir[w];
-            } else {
-                e = hmc_step_size(mp0, hmc_ln_jitter_of(mp1), s_lo, s_hi, g0, k0, k1);
-                zL = in ? philox_normal(s_lo, s_hi, (uint32_t)w, ALABI_HMC_STREAM_Z + 16u * (uint32_t)tid, k0, k1) : 0.0;
-                uint32_t r[4];
-                philox4x32_10(s_lo, s_hi, (uint32_t)w, ALABI_NUTS_STREAM_DIR, k0, k1, r);
-                dirw = r[0];
-            }
-            zR = zL; rho = zL;
-            H0 = -lp_old + 0.5 * wave_total(zL * zL);
-        }
-        bool go;
-        do {   // one leaf per trip; the trip count is the stop word's, the same for every thread
-            if (tid < 64) {
-                if (n == 0) {                                       // doubling j starts: from which end, which way
-                    fwd = ((dirw >> j) & 1u) != 0u;
-                    s = fwd ? e : -e;
-                    q = fwd ? qR : qL; z = fwd ? zR : zL; g = fwd ? gR : gL;
-                    rhoS = 0.0; lnWs = -INFINITY;
-                }
-                z = fma(0.5 * s, scale_transposed_times(Cs, diagonal, d, ld, tid, g), z);
-                q = fma(s, scale_times(Cs, diagonal, d, ld, tid, z), q);
-            }
-            lp_grad_eval<D, GENERIC>(p.lg, w_s, qs_s, g_s, scratch, q, inv_len, lpq, g);
-            if (tid < 64) {
-                z = fma(0.5 * s, scale_transposed_times(Cs, diagonal, d, ld, tid, g), z);
-                const double delta = H0 - (0.5 * wave_total(z * z) - lpq);
-                const bool out = in && !((q > lo) && (q < hi));         // NaN is outside
-                const bool inb = __ballot(out) == 0ull;
-                int stop = 0;
-                const int ordinal = leaves;
-                ++leaves;
-                if (!(delta > -1000.0)) {                               // divergent (NaN included): drop the subtree
-                    reason = ALABI_NUTS_STOP_DIVERGENT; stop = 1; ++n_div;
-                } else {
-                    if (inb) {
-                        a_sum += fmin(1.0, exp(delta));
-                        lnWs = nuts_logaddexp(lnWs, delta);
-                        const double ul = p.inj_z ? a.inj_uleaf[(size_t)w * nleaf_max + ordinal]
-                                                  : nuts_uniform(s_lo, s_hi, (uint32_t)w, ALABI_NUTS_STREAM_LEAF + 16u * (uint32_t)ordinal, k0, k1);
-                        if (log(ul) < delta - lnWs) { qc = q; gc = g; lpc = lpq; }
-                    }
-                    rhoS += z;
-                    if ((n & 1) == 0) {                                 // slot popcount(n) <= Dmax - 2 < ALABI_NUTS_MAX_DEPTH
-                        const int slot = __popc((unsigned)n);
-                        ck_z[slot * 64 + tid] = z; ck_r[slot * 64 + tid] = rhoS;
-                    } else {
-                        const int base = __popc((unsigned)(n >> 1));
-                        bool turn = false;
-                        for (int i = 0; ((n >> i) & 1) != 0; ++i) {     // wave-uniform: t trailing one bits, slots base ... base - t + 1 >= 0
-                            const double zf = ck_z[(base - i) * 64 + tid];
-                            const double rb = rhoS - ck_r[(base - i) * 64 + tid] + zf;
-                            const double d1 = wave_total(rb * zf), d2 = wave_total(rb * z);
-                            if (d1 <= 0.0 || d2 <= 0.0) turn = true;
-                        }
-                        if (turn) { reason = ALABI_NUTS_STOP_SUBTREE; stop = 1; }
-                    }
-                    ++n;
-                    if (!stop && n == (1 << j)) {                       // the subtree is complete: join it
-                        if (lnWs > -INFINITY) {
-                            const double ut = p.inj_z ? a.inj_utree[(size_t)w * Dmax + j]
-                                                      : nuts_uniform(s_lo, s_hi, (uint32_t)w, ALABI_NUTS_STREAM_TREE + 16u * (uint32_t)j, k0, k1);
-                            if (log(ut) < lnWs - lnW) { qp = qc; gp = gc; lpp = lpc; taken = 1; }
-                        }
-                        lnW = nuts_logaddexp(lnW, lnWs);
-                        rho += rhoS;
-                        if (fwd) { qR = q; zR = z; gR = g; } else { qL = q; zL = z; gL = g; }
-                        depth = j + 1;
-                        const double d1 = wave_total(rho * zL), d2 = wave_total(rho * zR);
-                        if (d1 <= 0.0 || d2 <= 0.0) { reason = ALABI_NUTS_STOP_TREE; stop = 1; }
-                        else if (depth == Dmax) { reason = ALABI_NUTS_STOP_DEPTH; stop = 1; }
-                        ++j; n = 0;
-                    }
-                }
-                if (tid == 0) stop_s = stop;
-            }
-            __syncthreads();
-            go = stop_s == 0;
-        } while (go);
-        if (tid < 64) {
-            xv = qp; lp_old = lpp; gx = gp;
-            nacc += taken;
-            n_leaves += leaves; n_depth += depth;
-            if (a.trace && tid < 4) a.trace[(size_t)w * 4 + tid] = tid == 0 ? depth : tid == 1 ? leaves : tid == 2 ? reason : taken;
-            if (p.chain || p.chain_logp) {
-                const long long done = p.done0 + t + 1;
-                if (done % p.thin_by == 0) {
-                    const size_t slot = (size_t)(done / p.thin_by - 1);
-                    if (p.chain && in) __builtin_nontemporal_store(xv, &p.chain[(slot * WT + w) * d + tid]);
-                    if (p.chain_logp && tid == 0) __builtin_nontemporal_store(lp_old, &p.chain_logp[slot * WT + w]);
-                }
-            }
-        }
-    }
-    if (tid >= 64) return;
-    if (in) p.coords[(size_t)w * d + tid] = xv;
-    if (tid == 0) {
-        p.logp[w] = lp_old;
-        if (p.n_accept) p.n_accept[w] += nacc;
-        if (a.counts) { a.counts[(size_t)w * 3] = n_leaves; a.counts[(size_t)w * 3 + 1] = n_depth; a.counts[(size_t)w * 3 + 2] = n_div; }
-        if (a.accept_sum) a.accept_sum[w] = a_sum;
-    }
+    nuts_walker_transitions<D, GENERIC, false>(a, HmcAdaptArgs{}, nuts_lds, qs_s, g_s, scratch, &stop_s, nullptr);
 }
 
 // The production draws of one step (alabi_ens_export_nuts_draws): per ensemble the move and e, per walker the momentum normals, the

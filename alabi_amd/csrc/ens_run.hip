@@ -381,6 +381,42 @@ int alabi_ens_hmc_adapt(alabi_ens* e, double* coords, double* logp, long long st
     return ALABI_OK;
 }
 
+int alabi_ens_nuts_adapt(alabi_ens* e, double* coords, double* logp, long long step0, long long nsteps, int thin_by, double* da_state,
+                         const double* da_par, double* chain, double* chain_logp, long long* n_accept, long long* counts, double* accept_sum,
+                         double* accept_stat, void* stream) {
+    if (!e || !coords || !logp || !da_state || !da_par || nsteps < 0 || thin_by < 1) return ALABI_BAD_ARGUMENT;
+    const double delta = da_par[0], gamma = da_par[1], t0 = da_par[2], kappa = da_par[3];
+    if (!(delta > 0.0 && delta < 1.0) || !(gamma > 0.0) || !(t0 >= 0.0) || !std::isfinite(t0) || !(kappa > 0.5 && kappa <= 1.0))
+        return ALABI_BAD_ARGUMENT;                                    // (gamma = +inf is allowed: ln e stays at mu)
+    if (!e->all_nuts || e->moves.n != 1) return ALABI_BAD_ARGUMENT;   // one step size is adapted: exactly one kind-7 move
+    if (!e->gp->computed || !e->gp->has_alpha) return ALABI_NOT_COMPUTED;
+    hipStream_t s = as_stream(stream);
+    const int chunk = ens_nuts_chunk(ens_shape(e, s != nullptr), e->n_cu, ens_switches());
+    if (chunk <= 0) return ALABI_BAD_ARGUMENT;                        // factor, weights and checkpoints exceed the LDS, or no dimension bucket
+    if (nsteps == 0) return ALABI_OK;
+    int st;
+    if ((st = ens_sync_consts(e, s)) != ALABI_OK) return st;
+    for (long long done = 0; done < nsteps; done += chunk) {
+        const int K = (int)(nsteps - done < chunk ? nsteps - done : chunk);
+        if ((st = launch_ens_nuts_adapt(e, coords, logp, step0, done, K, thin_by, chain, chain_logp, n_accept, da_state, da_par, counts,
+                                        accept_sum, accept_stat, s)) != ALABI_OK)
+            return st;
+    }
+    e->nuts_plan[1] = chunk;
+    return ALABI_OK;
+}
+
+int alabi_ens_find_step_size(alabi_ens* e, const double* coords, const double* logp, long long step, int k_move, double* ln_e, int* iters,
+                             void* stream) {
+    if (!e || !coords || !logp || !ln_e) return ALABI_BAD_ARGUMENT;
+    if (!(e->all_hmc || e->all_nuts) || k_move < 0 || k_move >= e->moves.n) return ALABI_BAD_ARGUMENT;
+    if (!e->gp->computed || !e->gp->has_alpha) return ALABI_NOT_COMPUTED;
+    hipStream_t s = as_stream(stream);
+    int st;
+    if ((st = ens_sync_consts(e, s)) != ALABI_OK) return st;
+    return launch_ens_step_search(e, coords, logp, step, k_move, ln_e, iters, s);
+}
+
 int alabi_ens_draw(alabi_ens* e, long long step0, int nsteps, double a, void* stream) {
     if (!e || nsteps <= 0 || nsteps > e->chunk_cap || !(a > 1.0)) return ALABI_BAD_ARGUMENT;
     if (e->W < 2 && !e->all_gauss && !e->all_nuts) return ALABI_BAD_ARGUMENT;   // a red-blue record names a walker of the other half

@@ -8,7 +8,7 @@ from __future__ import annotations
 import numpy as np
 
 __all__ = ["warmup_windows", "warmup_segments", "pooled_step_size", "regularised_covariance", "initial_state", "restart_state",
-           "DA_DEFAULTS", "DA_WORDS"]
+           "searched_state", "DA_DEFAULTS", "DA_WORDS"]
 
 DA_WORDS = 5                                  # m, H-bar, ln e, ln e-bar, mu per walker
 DA_DEFAULTS = (0.8, 0.05, 10.0, 0.75)         # delta, gamma, t0, kappa (Stan's)
@@ -109,4 +109,14 @@ def restart_state(n_walkers, pooled):
     st = np.zeros((int(n_walkers), DA_WORDS))
     st[:, 2] = st[:, 3] = np.log(float(pooled))
     st[:, 4] = np.log(10.0) + np.log(float(pooled))
+    return st
+
+
+def searched_state(ln_e):
+    """The state each walker starts from after the step-size search (``EnsembleSampler.find_step_size``), ``ln_e`` [n_walkers] its
+    own searched value: m = 0, H-bar = 0, ln e = ln e-bar = ln e_w, mu = ln 10 + ln e_w."""
+    v = np.asarray(ln_e.detach().cpu().numpy() if hasattr(ln_e, "detach") else ln_e, dtype=np.float64).reshape(-1)
+    st = np.zeros((len(v), DA_WORDS))
+    st[:, 2] = st[:, 3] = v
+    st[:, 4] = np.log(10.0) + v
     return st

@@ -41,8 +41,8 @@ Metropolis move --, alone or as a weighted mixture from which ONE move is chosen
 * ``NUTSMove(cov, step_size=None, max_depth=8, jitter=None)`` -- the No-U-Turn sampler (multinomial NUTS, Betancourt 2017, as in
   Stan) on the same gradient and mass matrix: the trajectory length is chosen per transition by doubling a tree of leapfrog steps
   until it turns back on itself, at most ``2 ** max_depth - 1`` gradient evaluations.  A set of NUTS moves runs on
-  ``ens_nuts_kernel`` under HMC's restrictions; it holds NUTS moves only.  It has no warm-up of its own: tune an ``HMCMove`` and
-  pass what ``tune_hmc`` found.
+  ``ens_nuts_kernel`` under HMC's restrictions; it holds NUTS moves only.  Its warm-up is ``EnsembleSampler.tune_nuts`` (one
+  ``NUTSMove``): step-size search, dual averaging on the tree's mean acceptance statistic, windowed mass matrix.
 
 ``MHMove(proposal_function, ndim=None)`` is emcee's generic Metropolis move: ``proposal_function(coords[W, d], rng) -> (q[W, d],
 log_factors[W])`` is a Python callable, so it runs on a host-driven step loop (one round trip per step: slow by nature), the
@@ -287,8 +287,10 @@ class NUTSMove:
     drop that subtree), or ``max_depth`` doublings (1 ... 10) are done: at most ``2 ** max_depth - 1`` gradient evaluations.  The
     next state is drawn from the tree's points with weights exp(-energy error), biased towards the newer half; a point outside the
     open box has weight 0 -- the orbit itself follows the surrogate's smooth extension.  Stan's extra U-turn
-    checks across subtree joints are not built.  There is no warm-up for this move: tune an ``HMCMove`` with
-    ``EnsembleSampler.tune_hmc`` and pass ``NUTSMove(tuning["cov"], step_size=tuning["step_size"])``."""
+    checks across subtree joints are not built.  ``EnsembleSampler.tune_nuts`` (``run_emcee``:
+    ``sampler_kwargs["nuts_warmup"]``) is this move's warm-up: ``NUTSMove(cov_guess)`` followed by it leaves no knob to set by hand.
+    It adapts the step size on the mean of min(1, exp(-energy error)) over all leaves of a tree, which is NUTS's statistic; an
+    ``HMCMove`` tuned by ``tune_hmc`` lands on another step size, that of a fixed-length trajectory's end point."""
 
     def __init__(self, cov, step_size=None, max_depth=8, jitter=None):
         if isinstance(max_depth, bool) or int(max_depth) != max_depth or not (1 <= int(max_depth) <= NUTS_MAX_DEPTH):

@@ -626,7 +626,8 @@ class EnsembleSampler:
         from . import hmc_adapt as ha
         from .moves import HMCMove
         if self._move_set is not None and self._move_set.has_nuts:
-            raise ValueError("tune_hmc adapts an HMCMove, not a NUTSMove (a NUTS warm-up is not built): tune an HMCMove with the same "
+            raise ValueError("tune_hmc adapts an HMCMove, not a NUTSMove: a NUTSMove has tune_nuts (run_emcee: nuts_warmup).  The older "
+                             "route still works -- tune an HMCMove with the same "
                              'cov, then pass NUTSMove(sm.hmc_tuning["cov"], step_size=sm.hmc_tuning["step_size"]) (hmc_tuning of the sampler, or of '
                              "the SurrogateModel after run_emcee with hmc_warmup)")
         if self.generic:
@@ -691,6 +692,161 @@ class EnsembleSampler:
                                metric=metric, seconds=time.perf_counter() - t_start, last_path="hmc-adapt")
         self.last_path = "hmc-adapt"
         self.last_stream_kernel = "ens_hmc_adapt_kernel"
+        return State(self._coords.cpu().numpy(), self._logp.cpu().numpy())
+
+    # ------------------------------------------------------------------ NUTS warm-up
+    def _grad_route_checks(self, route, cls, what):
+        """The refusals that ``tune_nuts`` shares with ``tune_hmc``, mirrored; returns the one move."""
+        if self.generic:
+            raise ValueError(f"{route} needs the gradient of the log-probability, which exists for the fused surrogate only: a Python "
+                             "prior_fn or like_fn (the host-callback path) has none")
+        if self.shard:
+            raise ValueError(f"{route} cannot run with shard=True: the sharded form of a {cls.__name__} is not built")
+        ms = self._move_set
+        if ms is None or len(ms) != 1 or not isinstance(ms.moves[0], cls):
+            raise ValueError(f"{route} {what} of exactly one {cls.__name__}: mixtures under adaptation are not built, and no other "
+                             "move has a step size to adapt" + (" (an HMCMove has tune_hmc)" if ms is not None and ms.has_hmc else ""))
+        return ms.moves[0]
+
+    def _search_ln_e(self, ln_e, k_move=0):
+        """alabi_ens_find_step_size on the current walkers at the current draw counter (which does not advance): ``ln_e`` [E W]
+        (device, in / out); returns the iteration counts (device, int32)."""
+        iters = torch.zeros(self.total_walkers, dtype=torch.int32, device=ln_e.device)
+        _lib.check(_lib.lib().alabi_ens_find_step_size(self._ens, _lib.ptr(self._coords), _lib.ptr(self._logp), self._rng_step, int(k_move),
+                                                       _lib.ptr(ln_e), _lib.ptr(iters), _lib.current_stream()), "alabi_ens_find_step_size")
+        return iters
+
+    def find_step_size(self, coords=None, k_move=0):
+        """Stan's initial step-size search for move ``k_move`` of a set of HMC moves or of NUTS moves, on ``ens_step_search_kernel``:
+        per walker, from the move's resolved step size, one leapfrog step with a fresh momentum per iteration, the step size doubled
+        (or halved) until the step's energy error crosses ln 0.8 -- at most 40 times.  ``coords`` [E W, ndim] (default: where the
+        sampler stands) are not moved, and the draw counter does not advance.  Returns a dict: ``step_sizes`` [E W], ``step_size``
+        (their geometric mean) and ``iters`` [E W] (the doublings or halvings made; 40: the cap was hit).  Any other move set, host
+        callables and ``shard=True`` raise ``ValueError``."""
+        from . import hmc_adapt as ha
+        if self.generic:
+            raise ValueError("find_step_size needs the gradient of the log-probability, which exists for the fused surrogate only: a "
+                             "Python prior_fn or like_fn (the host-callback path) has none")
+        if self.shard:
+            raise ValueError("find_step_size cannot run with shard=True: the sharded form of an HMCMove or a NUTSMove is not built")
+        ms = self._move_set
+        if ms is None or not (ms.all_hmc or ms.all_nuts):
+            raise ValueError("find_step_size searches the step size of an HMCMove or a NUTSMove: the move set must consist of HMC moves "
+                             "or of NUTS moves")
+        k_move = int(k_move)
+        if not 0 <= k_move < len(ms):
+            raise ValueError(f"find_step_size: k_move must be in 0 ... {len(ms) - 1}")
+        if coords is None:
+            if self._coords is None:
+                raise ValueError("find_step_size needs coords before the sampler has run")
+        else:
+            c = _to_dev(coords.coords if isinstance(coords, State) else coords, 2).clone()
+            if c.shape != (self.total_walkers, self.ndim):
+                raise ValueError("incompatible input dimensions: coords must be (nwalkers * n_ensembles, ndim)")
+            self._coords, self._logp = c, self.compute_log_prob(c)
+        self._ensure_ens()
+        ln_e = torch.full((self.total_walkers,), float(np.log(ms.moves[k_move].resolved_step_size(self.ndim))), dtype=torch.float64,
+                          device=self._coords.device)
+        iters = self._search_ln_e(ln_e, k_move)
+        torch.cuda.current_stream().synchronize()
+        return dict(step_sizes=np.exp(ln_e.cpu().numpy()), step_size=ha.pooled_step_size(ln_e), iters=iters.cpu().numpy())
+
+    def _nuts_adapt(self, nsteps, state, par, counts, accept_sum, chain=None, accept_stat=None):
+        """``nsteps`` warm-up transitions on ens_nuts_adapt_kernel (alabi_ens_nuts_adapt) from the draw counter, which advances;
+        ``state`` [E W, 5] as ``_hmc_adapt``; ``counts`` [E W, 3] int64 and ``accept_sum`` [E W] take the transitions' sums."""
+        _lib.check(_lib.lib().alabi_ens_nuts_adapt(self._ens, _lib.ptr(self._coords), _lib.ptr(self._logp), self._rng_step, int(nsteps), 1,
+                                                   _lib.ptr(state), _lib.host_doubles(par), _lib.ptr(chain), None, None, _lib.ptr(counts),
+                                                   _lib.ptr(accept_sum), _lib.ptr(accept_stat), _lib.current_stream()), "alabi_ens_nuts_adapt")
+        self._rng_step += int(nsteps)
+
+    def tune_nuts(self, initial_state, nwarmup=500, target_accept=0.8, metric="diag", init_step_size="search", gamma=0.05, t0=10,
+                  kappa=0.75):
+        """Stan-style warm-up of the sampler's one ``NUTSMove``, ``tune_hmc``'s structure on NUTS's own statistic: the step size by
+        dual averaging per walker towards a mean of ``target_accept`` of a_t -- the mean over ALL leaves of a transition's tree of
+        min(1, exp(-energy error)), 0 outside the box and for a divergent leaf -- on ``ens_nuts_adapt_kernel``, and, with ``metric``
+        "diag" or "dense", the mass matrix from the pooled covariance of the walkers' positions in Stan's doubling windows
+        (``alabi_amd.hmc_adapt``; every segment is ONE library call).  ``init_step_size="search"`` runs Stan's step-size search
+        (``find_step_size``) before the first segment and again after every mass-matrix update, and every walker restarts from its own
+        searched value; ``None`` starts at the move's resolved step size and restarts at the pooled one, exactly as ``tune_hmc``.
+        Afterwards the sampler's move is ``NUTSMove(cov, step_size=pooled, max_depth, jitter)``, the library's table holds it, and
+        ``nuts_tuning`` says what happened: ``step_size``, ``cov`` (None where the mass was not adapted), ``window_ends``,
+        ``step_sizes`` (pooled, at every window's end), ``mean_accept_stat``, ``mean_depth`` and ``divergences`` of the terminal
+        buffer, ``search_iters`` (per search, the walkers' iteration counts), ``nwarmup``, ``metric``, ``seconds`` and ``last_path ==
+        "nuts-adapt"``.  Warm-up consumes the draw counter like ``run_mcmc`` but is no part of the chain, of ``iteration``, of the
+        acceptance counts or of ``nuts_stats``.  Returns the ``State`` to continue from.  A set that is not exactly one ``NUTSMove``,
+        host callables and ``shard=True`` raise ``ValueError``."""
+        from . import hmc_adapt as ha
+        from .moves import NUTSMove
+        move = self._grad_route_checks("tune_nuts", NUTSMove, "adapts the step size and the mass matrix")
+        if metric not in (None, "diag", "dense"):
+            raise ValueError("metric must be None, 'diag' or 'dense'")
+        if init_step_size not in (None, "search"):
+            raise ValueError("init_step_size must be 'search' or None")
+        nwarmup = int(nwarmup)
+        par = (float(target_accept), float(gamma), float(t0), float(kappa))
+        if nwarmup < 1 or not (0.0 < par[0] < 1.0) or not par[1] > 0.0 or not par[2] >= 0.0 or not (0.5 < par[3] <= 1.0):
+            raise ValueError("tune_nuts needs nwarmup >= 1, 0 < target_accept < 1, gamma > 0, t0 >= 0 and 0.5 < kappa <= 1")
+        search = init_step_size == "search"
+        t_start = time.perf_counter()
+        coords = initial_state.coords if isinstance(initial_state, State) else initial_state
+        coords = _to_dev(coords, 2).clone()
+        if coords.shape != (self.total_walkers, self.ndim):
+            raise ValueError("incompatible input dimensions: initial state must be (nwalkers * n_ensembles, ndim)")
+        self._coords = coords
+        self._logp = self.compute_log_prob(coords)
+        if torch.isnan(self._logp).any():
+            raise ValueError("The initial log_prob was NaN")
+        self._ensure_ens()
+        dev, WT = coords.device, self.total_walkers
+        search_iters = []
+
+        def searched(eps):
+            ln_e = torch.full((WT,), float(np.log(eps)), dtype=torch.float64, device=dev)
+            iters = self._search_ln_e(ln_e)
+            search_iters.append(iters.cpu().numpy())
+            return torch.as_tensor(ha.searched_state(ln_e), device=dev)
+
+        eps0 = move.resolved_step_size(self.ndim)
+        state = searched(eps0) if search else torch.as_tensor(ha.initial_state(WT, eps0), device=dev)
+        segments = ha.warmup_segments(nwarmup, windows=metric is not None)
+        cov, step_sizes, window_ends, stat, counts = None, [], [], None, None
+        for k, (first, end, is_window) in enumerate(segments):
+            n = end - first
+            scratch = torch.empty((n, WT, self.ndim), dtype=torch.float64, device=dev) if is_window else None
+            last = k == len(segments) - 1
+            counts = torch.zeros((WT, 3), dtype=torch.int64, device=dev)
+            leaf_sum = torch.zeros(WT, dtype=torch.float64, device=dev)
+            stat = torch.zeros(WT, dtype=torch.float64, device=dev) if last else None
+            self._nuts_adapt(n, state, par, counts, leaf_sum, chain=scratch, accept_stat=stat)
+            if is_window:
+                torch.cuda.current_stream().synchronize()
+                cov = ha.regularised_covariance(scratch.reshape(-1, self.ndim), metric)
+                move = NUTSMove(cov, step_size=eps0, max_depth=move.max_depth, jitter=move.jitter)
+                _lib.check(_lib.lib().alabi_ens_set_move_scale(self._ens, 0, _lib.host_doubles(move.scale_matrix(self.ndim).ravel()),
+                                                               int(move.diagonal)), "alabi_ens_set_move_scale")
+                pooled = ha.pooled_step_size(state[:, 3])
+                step_sizes.append(pooled); window_ends.append(end)
+                self._last_window_chain = scratch
+                if not last:
+                    state.copy_(searched(pooled) if search else torch.as_tensor(ha.restart_state(WT, pooled), device=dev))
+        torch.cuda.current_stream().synchronize()
+        eps = ha.pooled_step_size(state[:, 3])
+        move = NUTSMove(move.cov, step_size=eps, max_depth=move.max_depth, jitter=move.jitter)
+        self._move_set = parse_moves(move, self.ndim)
+        m = self._move_set
+        _lib.check(_lib.lib().alabi_ens_set_move_scale(self._ens, 0, _lib.host_doubles(move.scale_matrix(self.ndim).ravel()),
+                                                       int(move.diagonal)), "alabi_ens_set_move_scale")
+        _lib.check(_lib.lib().alabi_ens_set_moves(self._ens, 1, (C.c_int * 1)(int(m.kind[0])), _lib.host_doubles(m.cum),
+                                                  _lib.host_doubles(m.p0), _lib.host_doubles(m.p1)), "alabi_ens_set_moves")
+        n_last = segments[-1][1] - segments[-1][0]
+        cn = counts.cpu().numpy()
+        self.nuts_tuning = dict(step_size=eps, cov=None if cov is None else np.array(cov, copy=True), window_ends=window_ends,
+                                step_sizes=step_sizes, mean_accept_stat=float(stat.mean().item()) / n_last,
+                                mean_depth=float(cn[:, 1].sum()) / (n_last * WT), divergences=int(cn[:, 2].sum()),
+                                search_iters=search_iters, nwarmup=nwarmup, metric=metric, seconds=time.perf_counter() - t_start,
+                                last_path="nuts-adapt")
+        self.last_path = "nuts-adapt"
+        self.last_stream_kernel = "ens_nuts_adapt_kernel"
         return State(self._coords.cpu().numpy(), self._logp.cpu().numpy())
 
     def reset(self):

@@ -284,7 +284,9 @@ int alabi_ens_set_logp_map(alabi_ens* ens, int kind);
  * smooth extension (lnp there: GP mean through the folded scalers, the y map, the normal priors, no box gate).  Draws: Philox
  * counter (step, global walker id, stream word S + 16 b) -- S = 11, b = k: the momentum normal z0_k at the walker (Box-Muller as
  * stream 4); S = 12, b = 0: v = (2 u53(r0, r1) - 1) ln jitter at the ensemble's walker 0, not drawn without jitter; accept uniform
- * and move choice are streams 2 and 3 as for every move; streams 0-10 keep their meaning.  Such a table runs on ens_hmc_kernel
+ * and move choice are streams 2 and 3 as for every move; streams 0-10 keep their meaning.  (S = 11 at b >= 64 -- word
+ * 11 + 16 (64 (i + 1) + k) -- is the momentum normal of iteration i, coordinate k of alabi_ens_find_step_size, which consumes no
+ * step: kinds 6 and 7 read b = k < 64 only.)  Such a table runs on ens_hmc_kernel
  * (path 5 of alabi_ens_last_path) and on nothing else: one workgroup per walker, every step of a chunk in one launch, any W >= 1
  * and any n_ensembles; alabi_ens_set_stream does not move it, and alabi_ens_run is ALABI_BAD_ARGUMENT where the kernel cannot run
  * (the factors [n][d, d | 1] and the gradient weights [Npad] exceed 128 KB of LDS together).  ALABI_ENS_HMC_CHUNK=k caps the steps
@@ -353,6 +355,40 @@ int alabi_ens_nuts_stats(alabi_ens* ens, long long* counts_host /* host [E*W, 3]
 int alabi_ens_hmc_adapt(alabi_ens* ens, double* coords, double* logp, long long step0, long long nsteps, int thin_by,
                         double* da_state /* device [E*W, 5] in/out */, const double* da_par /* host [4]: delta, gamma, t0, kappa */,
                         double* chain, double* chain_logp, long long* n_accept, double* accept_stat /* or null */, void* stream);
+/* NUTS warm-up: nsteps transitions of a table of exactly ONE kind-7 move on ens_nuts_adapt_kernel -- ens_nuts_kernel's launch
+ * shape, arithmetic, draws, tree and stop rules (kind 7 above) -- with a step size per walker adapted by dual averaging on NUTS's
+ * own statistic (tests/nuts_adapt_numpy.py states it).  da_state device [E*W, 5] doubles in/out as for alabi_ens_hmc_adapt: m,
+ * H-bar, ln e, ln e-bar, mu.  A transition of walker w runs with e = exp(ln e_w) f, f the step's jitter factor as alabi_ens_run
+ * draws it (the table's p0 is not read).  With leaves_t >= 1 the leaves the transition made, a_t = (the sum of the leaf statistic a
+ * of kind 7 over exactly these leaves) / leaves_t: a = min(1, exp(delta)) in the open box, 0 outside it and 0 for a divergent
+ * leaf, which counts as a leaf.  Then m <- m + 1, H-bar <- (1 - 1 / (m + t0)) H-bar + (delta - a_t) / (m + t0), ln e <- mu -
+ * (sqrt(m) / gamma) H-bar, ln e-bar <- m^-kappa ln e + (1 - m^-kappa) ln e-bar.  da_par host [4] with alabi_ens_hmc_adapt's
+ * ranges: delta in (0, 1), gamma > 0 (+inf allowed: ln e stays at mu), t0 >= 0, kappa in (0.5, 1].  The call consumes the global
+ * steps step0 ... step0 + nsteps - 1 exactly as alabi_ens_run does, with coords, logp, thin_by, chain, chain_logp and n_accept
+ * as there.  counts device [E*W, 3] int64 and accept_sum device [E*W] (either may be null) are the CALLER's and take what
+ * alabi_ens_nuts_stats sums for a run -- leaves, depths, divergent transitions; the sum of a over all leaves -- in/out: warm-up
+ * transitions are no part of the handle's sums.  accept_stat device [E*W] or null: the sum of a_t over the call's transitions is
+ * added.  The state is read when a launch starts and written when it ends, so chunking (ens_nuts_chunk, ALABI_ENS_NUTS_CHUNK) and
+ * splitting the call change no bit.  Reports through alabi_ens_nuts_plan.  ALABI_BAD_ARGUMENT: the table is not exactly one kind-7
+ * move, a parameter is out of range, or the factor, the gradient weights and the checkpoints exceed 128 KB of LDS. */
+int alabi_ens_nuts_adapt(alabi_ens* ens, double* coords, double* logp, long long step0, long long nsteps, int thin_by,
+                         double* da_state /* device [E*W, 5] in/out */, const double* da_par /* host [4]: delta, gamma, t0, kappa */,
+                         double* chain, double* chain_logp, long long* n_accept, long long* counts /* device [E*W, 3] in/out or null */,
+                         double* accept_sum /* device [E*W] in/out or null */, double* accept_stat /* or null */, void* stream);
+/* Initial step-size search (Stan's find_reasonable heuristic) for move k_move of a table that is all kind 6 or all kind 7 (both
+ * use the same whitened leapfrog), on ens_step_search_kernel: one workgroup per walker, which does not move -- coords and logp are
+ * read only.  Per walker from ln e = ln_e[w], with lp = the caller's logp and g = grad lnp(x), iteration i = 0, 1, ...: z ~ N(0, I)
+ * fresh; H0 = -lp + |z|^2 / 2; one leapfrog step as a NUTS leaf with e = exp(ln e): z += (e / 2) C^T g, q = x + e C z, (lp_q, g_q)
+ * at q, z += (e / 2) C^T g_q; dH = H0 - (-lp_q + |z|^2 / 2), with NaN and a q outside the open box counting as -inf.  Iteration 0
+ * fixes dir = +1 if dH > ln 0.8, else -1.  The loop ends at the first iteration where dir = +1 and not dH > ln 0.8, or dir = -1
+ * and not dH < ln 0.8; otherwise ln e += dir ln 2 and the next iteration follows, 40 such steps at the most.  iters device [E*W]
+ * int32 or null: the number of ln 2 steps taken = the index of the iteration that ended the loop; 40 says that the cap ended it,
+ * the walker keeps its last ln e.  Draws: Philox counter (step, global walker id, stream word 11 + 16 (64 (i + 1) + k)) for the
+ * momentum normal of iteration i, coordinate k -- stream 11 at b >= 64, where kinds 6 and 7 read b = k < 64 only, so no draw of a
+ * move at the same step is read twice.  The search consumes no global step.  ALABI_BAD_ARGUMENT: a table of other kinds, k_move
+ * outside the table, no factor, or the factor and the gradient weights exceed 128 KB of LDS. */
+int alabi_ens_find_step_size(alabi_ens* ens, const double* coords, const double* logp, long long step, int k_move,
+                             double* ln_e /* device [E*W] in/out */, int* iters /* device [E*W] int32 or null */, void* stream);
 /* The ensemble's log-probability and its gradient at M arbitrary points, by the evaluation ens_hmc_kernel runs: coords [M, d],
  * logp [M], grad [M, d] on the device.  lnp = GP mean through the folded affine scalers and the y map, plus the normal priors;
  * grad = a T^T dmu (no map), ln10 lnp a T^T dmu (either map), minus (x_k - m_k) / s_k^2 per normal-prior coordinate.  Outside the

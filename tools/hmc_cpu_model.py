@@ -10,6 +10,13 @@ Cost per independent sample in kernel sums: max(tau, 1) x (evaluations per step)
 (4.1 value evaluations, measured on the device at C3: profiles/moves_step_hmc.txt), x 1 for a value evaluation.
 
     python tools/hmc_cpu_model.py [--d 32] [--seed 1]
+
+--nuts-warmup runs only the NumPy statement of the NUTS warm-up (tests/nuts_adapt_numpy.py: step-size search, dual averaging on the
+tree's mean acceptance statistic, windowed mass matrix) on the same target from identity mass, --warmup transitions of --walkers
+walkers (16 by default in this leg), beside tests/hmc_adapt_numpy.py's warm-up of an HMC move with 4 leapfrog steps: the step sizes
+and terminal acceptance statistics the two land on, and the recovered variances.
+
+    python tools/hmc_cpu_model.py --nuts-warmup [--d 8] [--seed 1] [--warmup 300]
 """
 import argparse
 import json
@@ -30,7 +37,11 @@ ap.add_argument("--stretch-steps", type=int, default=40000)
 ap.add_argument("--hmc-steps", type=int, default=4000)
 ap.add_argument("--nuts-steps", type=int, default=1000)
 ap.add_argument("--grad-cost", type=float, default=4.1)
+ap.add_argument("--nuts-warmup", action="store_true")
+ap.add_argument("--warmup", type=int, default=300)
 args = ap.parse_args()
+if args.nuts_warmup and "--walkers" not in sys.argv:
+    args.walkers = 16
 d, W = args.d, args.walkers
 sd = np.logspace(-1.0, 0.0, d)
 lnp = lambda x: -0.5 * np.sum((x / sd) ** 2, axis=-1)  # noqa: E731
@@ -87,6 +98,32 @@ def nuts(x, nsteps, rs, c, eps, max_depth):
         chain[t] = x
     return chain, taken / (nsteps * W), leaves / (nsteps * W)
 
+
+def nuts_warmup_leg():
+    import hmc_adapt_numpy as han
+    import hmc_numpy as hm
+    import nuts_adapt_numpy as nan_
+    tgt = hm.GaussianTarget(np.zeros(d), np.diag(sd ** 2), np.stack([np.full(d, -10.0), np.full(d, 10.0)], axis=1))
+    p0 = np.random.RandomState(args.seed).randn(W, d) * sd
+    eps0 = hm.default_step_size(d)
+    res = {"target": f"{d}-D Gaussian, standard deviations log-spaced 0.1 ... 1, identity mass at the start", "walkers": W, "seed": args.seed,
+           "nwarmup": args.warmup, "note": "CPU model in NumPy, not a GPU number"}
+    for key, search in (("nuts_search", True), ("nuts_no_search", False)):
+        w = nan_.warmup(tgt, p0, args.warmup, args.seed, (1.0, eps0, 8, None, 1.0), metric="diag", search=search)
+        ratio = w.cov / sd ** 2
+        res[key] = {"step_size": w.step_size, "step_sizes": w.step_sizes, "mean_accept_stat": w.mean_accept_stat, "mean_depth": w.mean_depth,
+                    "divergences": w.divergences, "variance_ratio_min_max": [float(ratio.min()), float(ratio.max())],
+                    "search_iters_min_max": [[int(i.min()), int(i.max())] for i in w.search_iters]}
+    h = han.warmup(tgt, p0, args.warmup, args.seed, (1.0, eps0, 4, None, 1.0), metric="diag")
+    ratio = h.cov / sd ** 2
+    res["hmc_4_leapfrog"] = {"step_size": h.step_size, "step_sizes": h.step_sizes, "mean_accept_stat": h.mean_accept_stat,
+                             "variance_ratio_min_max": [float(ratio.min()), float(ratio.max())]}
+    print(json.dumps(res, indent=1))
+
+
+if args.nuts_warmup:
+    nuts_warmup_leg()
+    sys.exit(0)
 
 out = {"target": f"{d}-D Gaussian, standard deviations log-spaced 0.1 ... 1", "walkers": W, "seed": args.seed,
        "stretch_steps": args.stretch_steps, "hmc_steps": args.hmc_steps, "note": "CPU model in NumPy, not a GPU number"}

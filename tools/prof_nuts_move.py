@@ -13,6 +13,16 @@ line.  Derived: us per leaf over us per value-and-gradient evaluation -- what th
 barrier and the load imbalance between walkers (a launch ends with its deepest trees) add to an evaluation.
 
     python tools/prof_nuts_move.py > profiles/moves_step_nuts.txt
+
+--adapt measures the warm-up instead (256 walkers):
+  (s) (a)    --steps sampling transitions on ens_nuts_kernel and as many warm-up transitions on ens_nuts_adapt_kernel
+             (alabi_ens_nuts_adapt) in alternation, from the same walkers, at the same draw counter and with the state frozen at the
+             same step size (gamma = inf, mu = ln e): the same trees (leaf for leaf where exp(ln e) = e), so the difference is what
+             ADAPT costs; leaves per transition are printed for both,
+  (t)        EnsembleSampler.tune_nuts(500) end to end from NUTSMove(cov): seconds, the step size and the terminal mean acceptance
+             statistic it lands on, with and without the step-size search, beside tune_hmc(500) of HMCMove(cov, n_leapfrog=4).
+
+    python tools/prof_nuts_move.py --adapt > profiles/moves_step_nuts_adapt.txt
 """
 import argparse
 import ctypes as C
@@ -26,6 +36,7 @@ ap.add_argument("--runs", type=int, default=5)
 ap.add_argument("--steps", type=int, default=512)
 ap.add_argument("--depth", type=int, default=8)
 ap.add_argument("--tag", default="")
+ap.add_argument("--adapt", action="store_true")
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.root))
 
@@ -73,6 +84,70 @@ def timed(s):
     s.reset()
     return a.elapsed_time(b) * 1e3 / args.steps, acc, extra
 
+
+def adapt_report():
+    W, p0 = int(cfg["W"]), cfg["p0"]
+    eps = float(d) ** -0.25
+    s = make(W, p0, NUTSMove(cov, max_depth=args.depth))
+    par = _lib.host_doubles((0.8, float("inf"), 10.0, 0.75))
+    state = torch.zeros((W, 5), dtype=torch.float64, device="cuda")
+    state[:, 2] = state[:, 4] = float(np.log(eps))
+    counts = torch.zeros((W, 3), dtype=torch.int64, device="cuda")
+    leaf_sum, stat = torch.zeros(W, dtype=torch.float64, device="cuda"), torch.zeros(W, dtype=torch.float64, device="cuda")
+    chain = torch.empty((args.steps, W, d), dtype=torch.float64, device="cuda")
+    us, leaves = {"sample": [], "adapt": []}, {"sample": [], "adapt": []}
+    for r in range(args.runs + 1):                             # round 0 warms the adapt kernel's code object up
+        c0, l0, step0 = s._coords.clone(), s._logp.clone(), s._rng_step
+        t, _, extra = timed(s)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        counts.zero_(); state[:, 0] = 0.0
+        torch.cuda.synchronize()
+        a.record()
+        _lib.check(_lib.lib().alabi_ens_nuts_adapt(s._ens, _lib.ptr(c0), _lib.ptr(l0), step0, args.steps, 1, _lib.ptr(state), par, _lib.ptr(chain),
+                                                   None, None, _lib.ptr(counts), _lib.ptr(leaf_sum), _lib.ptr(stat), _lib.current_stream()),
+                   "alabi_ens_nuts_adapt")
+        b.record()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(c0, s._coords))                # exp(ln e) may be an ulp off e: then the trees differ in detail only
+        if r:
+            us["sample"].append(t); us["adapt"].append(a.elapsed_time(b) * 1e3 / args.steps)
+            leaves["sample"].append(extra["leaves_per_transition"]); leaves["adapt"].append(float(counts[:, 0].sum()) / (args.steps * W))
+    out = {"tag": args.tag, "config": "C3", "N": int(cfg["X"].shape[0]), "d": d, "W": W, "steps": args.steps, "runs": args.runs,
+           "step_size": eps, "max_depth": args.depth, "unit": "us per transition, device events, chain stored; frozen state: the same trees"}
+    for k in us:
+        out[k] = {"median": float(np.median(us[k])), "min": float(np.min(us[k])), "max": float(np.max(us[k])),
+                  "runs": [round(x, 3) for x in us[k]], "leaves_per_transition": float(np.median(leaves[k]))}
+    out["adapt_over_sample"] = out["adapt"]["median"] / out["sample"]["median"]
+    out["adapt_us_per_leaf_over_sample"] = (out["adapt"]["median"] / out["adapt"]["leaves_per_transition"]) / (
+        out["sample"]["median"] / out["sample"]["leaves_per_transition"])
+    out["same_walkers_after_the_last_round"] = same
+    s._release()
+    tune = {}
+    for key, kw in (("search", {}), ("no_search", {"init_step_size": None})):
+        best = None
+        for rep in range(2):                                   # the second call has its code objects
+            t = EnsembleSampler(W, d, gp, cfg["y"], cfg["bounds"], seed=5, moves=NUTSMove(cov, max_depth=args.depth))
+            t.tune_nuts(p0, nwarmup=500, **kw)
+            best = {k: v for k, v in t.nuts_tuning.items() if k in ("step_size", "step_sizes", "mean_accept_stat", "mean_depth", "divergences",
+                                                                    "seconds", "window_ends")}
+            best["search_iters_min_max"] = [[int(i.min()), int(i.max())] for i in t.nuts_tuning["search_iters"]]
+            if rep:
+                t.run_mcmc(None, 200)
+                best["next_200_transitions"] = t.nuts_stats
+            t._release()
+        tune["tune_nuts_" + key] = best
+    for rep in range(2):
+        t = EnsembleSampler(W, d, gp, cfg["y"], cfg["bounds"], seed=5, moves=HMCMove(cov, n_leapfrog=4))
+        t.tune_hmc(p0, nwarmup=500)
+        tune["tune_hmc_4_leapfrog"] = {k: v for k, v in t.hmc_tuning.items() if k in ("step_size", "step_sizes", "mean_accept_stat", "seconds")}
+        t._release()
+    out["tune_500"] = tune
+    print(json.dumps(out))
+
+
+if args.adapt:
+    adapt_report()
+    sys.exit(0)
 
 p0 = cfg["p0"]
 rs = np.random.RandomState(9)
