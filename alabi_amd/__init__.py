@@ -4,7 +4,7 @@ The numerical work lives in ``csrc/libalabi_hip.so`` (hand-written HIP for gfx95
 ``include/alabi_hip.h``); this package is the Python host side mirroring the reference's
 ``SurrogateModel`` interface.  Importing the package does not need a GPU; using it does.
 """
-from . import benchmarks, gp_utils, laplace, mcmc_utils, metrics, moves, utility  # noqa: F401
+from . import benchmarks, diagnostics, gp_utils, laplace, mcmc_utils, metrics, moves, utility  # noqa: F401
 from .core import CachedSurrogateLikelihood, SurrogateModel  # noqa: F401
 from .gp import HipGP  # noqa: F401
 from .kde import DeviceKDE  # noqa: F401

@@ -101,6 +101,7 @@ SIGNATURES = {
     "alabi_ens_restore": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "alabi_ens_boundary_stats": (_i, [_vp, _pll]),
     "alabi_chain_autocorr": (_i, [_vp, _ll, _i, _i, _vp, _vp]),
+    "alabi_chain_split_stats": (_i, [_vp, _ll, _ll, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "alabi_ens_draw": (_i, [_vp, _ll, _i, _d, _vp]),
     "alabi_ens_half_step": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "alabi_dist_unique_id": (_i, [_vp]),

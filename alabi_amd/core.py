@@ -1207,6 +1207,7 @@ class SurrogateModel(object):
 
         self.emcee_samples = post.run_until_min_ess(run, min_ess, (lambda total: f" (total {total})") if self.verbose else None)
         self._emcee_full, self._emcee_full_src = None, (self.emcee_sampler, plan.t_add, plan.t_mult)   # emcee_samples_full: lazily
+        self._emcee_affine = (plan.t_add, plan.t_mult)                # mcmc_diagnostics reports in theta coordinates
         if self.like_fn_name == "true":
             self.emcee_samples_true = self.emcee_samples
         elif self.like_fn_name == "surrogate":
@@ -1228,6 +1229,23 @@ class SurrogateModel(object):
         self._write_samples("emcee", self.emcee_samples, samples_file)
 
     run_mcmc = run_emcee  # BASELINE.json's name for the same entry point
+
+    def mcmc_diagnostics(self, discard=None, thin=1):
+        """Chain diagnostics of the last run_emcee (Vehtari et al. 2021; alabi_amd/diagnostics.py): a dict of [ndim] arrays mean,
+        sd, mcse_mean (in theta coordinates), ess_mean, ess_bulk, ess_tail and rhat of the chain after ``discard`` steps (None:
+        ``self.burn``), every ``thin``-th step; also stored as ``self.emcee_diagnostics``.  The chain is judged where it lies, on
+        the device.  Every walker counts as a chain: walkers are independent under the metropolis, hmc and nuts moves; under the
+        red-blue ensemble moves (the default stretch move among them) the walkers of one ensemble are coupled -- R-hat still
+        detects disagreement, but the ESS formula assumes independent chains and is approximate there."""
+        if not getattr(self, "emcee_run", False) or getattr(self, "emcee_sampler", None) is None:
+            raise AttributeError("mcmc_diagnostics: run_emcee has not been called")
+        out = self.emcee_sampler.diagnostics(discard=int(self.burn if discard is None else discard), thin=int(thin))
+        t_add, t_mult = self._emcee_affine                         # sampler coordinates = t_mult * theta + t_add
+        out["mean"] = (out["mean"] - t_add) / t_mult
+        out["sd"] = out["sd"] / np.abs(t_mult)
+        out["mcse_mean"] = out["mcse_mean"] / np.abs(t_mult)
+        self.emcee_diagnostics = out
+        return out
 
     # ------------------------------------------------------------------------ nested sampling
     def _nested_setup(self, like_fn, prior_transform, prior_transform_comment):

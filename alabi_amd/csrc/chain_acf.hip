@@ -22,6 +22,10 @@
 //   D  acf_reduce_kernel     out[k][lag] += sum over the batch's walkers of R[(w,k)][lag] / R[(w,k)][0]
 // The spectrum never needs to be in natural order: |F|^2 is taken element by element and the inverse starts from the same layout.
 // HBM traffic per batch of 256 series of 2^17 points: ~2.5 GB; a 1 GB chain takes ~15 ms.
+//
+// alabi_chain_split_stats (the device half of alabi_amd/diagnostics.py: split R-hat, bulk / tail ESS, MCSE) runs A, B and C as they
+// are on split, optionally transformed chains read through a step stride, with per-chain moments in place of acf_mean_kernel and
+// a reduction that keeps the autocovariances un-normalised; its three kernels stand below D.
 #include <cmath>
 #include <cstdlib>
 
@@ -175,6 +179,79 @@ acf_reduce_kernel(const double* __restrict__ R, long long ldr, long long n_t, in
     *o = first ? scale * acc : fma(scale, acc, *o);
 }
 
+// ---- split chains, transforms on load, moments, un-normalised autocovariances (alabi_chain_split_stats) ----------------------
+// Series s of a batch = split chain c = c0 + s / n_d (half = c / n_w, walker = c % n_w), dimension k = s % n_d; half 1 starts at
+// step t_half1.  Element (t, w, k) of the chain lies at chain[t * t_stride + w * n_d + k].
+// transform: 0 y = x, 1 y = 1[x <= par[k]], 2 y = |x - par[k]|, applied here so that no second chain is ever stored.
+__global__ void __launch_bounds__(256)
+acf_split_transpose_kernel(const double* __restrict__ chain, long long n, long long t_stride, long long t_half1, int n_w, int n_d, int c0,
+                           int ns, int transform, const double* __restrict__ par, double* __restrict__ xt, long long ldx) {
+    __shared__ double tile[64][65];
+    const long long t0 = (long long)blockIdx.x * 64;
+    const int sb = blockIdx.y * 64;
+    const int col = threadIdx.x & 63;                                // the series this thread loads: the same for all its elements
+    const bool live = sb + col < ns;
+    const double* src = chain;
+    double pk = 0.0;
+    if (live) {
+        const int c = c0 + (sb + col) / n_d, k = (sb + col) % n_d;
+        const int half = c / n_w, w = c - half * n_w;
+        src = chain + (size_t)(half ? t_half1 : 0) * t_stride + (size_t)w * n_d + k;
+        if (transform) pk = par[k];
+    }
+    for (int e = threadIdx.x; e < 4096; e += 256) {
+        const int r = e >> 6;                                        // r: time
+        double v = 0.0;
+        if (live && t0 + r < n) {
+            v = src[(size_t)(t0 + r) * t_stride];
+            if (transform == 1) v = v <= pk ? 1.0 : 0.0;
+            else if (transform == 2) v = fabs(v - pk);
+        }
+        tile[r][col] = v;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < 4096; e += 256) {
+        const int r = e >> 6, c = e & 63;                            // r: series, c: time
+        if (sb + r < ns && t0 + c < n) xt[(size_t)(sb + r) * ldx + t0 + c] = tile[c][r];
+    }
+}
+
+// Mean and variance (ddof 1) of every row: two passes over the row, both with the summation tree of acf_mean_kernel -- thread i adds
+// x[i], x[i + 256], ... in order, wave_sum's six xor steps, then the four wave sums in order (tests/test_gpu_diagnostics.py counts
+// these roundings).  mean = sum / n, var = sum (x - mean)^2 / (n - 1).
+__global__ void __launch_bounds__(256)
+acf_moments_kernel(const double* __restrict__ xt, long long n, long long ldx, double* __restrict__ mean, double* __restrict__ var) {
+    __shared__ double scratch[16];
+    const double* x = xt + (size_t)blockIdx.x * ldx;
+    double s = 0.0;
+    for (long long t = threadIdx.x; t < n; t += 256) s += x[t];
+    s = block_sum(s, scratch);
+    const double mu = s / (double)n;
+    double q = 0.0;
+    for (long long t = threadIdx.x; t < n; t += 256) {
+        const double d = x[t] - mu;
+        q += d * d;
+    }
+    q = block_sum(q, scratch);
+    if (threadIdx.x == 0) {
+        mean[blockIdx.x] = mu;
+        var[blockIdx.x] = q / (double)(n - 1);
+    }
+}
+
+// D': out[k][lag] (+)= scale * sum over the batch's chains of R[(c, k)][lag] (no division by lag 0: autocovariances)
+__global__ void __launch_bounds__(256)
+acf_cov_reduce_kernel(const double* __restrict__ R, long long ldr, long long n, int nc_batch, int n_d, double scale, int first,
+                      double* __restrict__ out) {
+    const long long lag = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int k = blockIdx.y;
+    if (lag >= n) return;
+    double acc = 0.0;
+    for (int c = 0; c < nc_batch; ++c) acc += R[(size_t)(c * n_d + k) * ldr + lag];
+    double* o = out + (size_t)k * n + lag;
+    *o = first ? scale * acc : fma(scale, acc, *o);
+}
+
 }  // namespace alabi
 
 using namespace alabi;
@@ -229,6 +306,69 @@ extern "C" int alabi_chain_autocorr(const double* chain, long long n_t, int n_w,
         if ((he = hipGetLastError()) != hipSuccess) fail(he, "autocorrelation kernels");
     }
     // the workspace goes back to the cache only when nothing in flight uses it any more
+    if ((he = hipStreamSynchronize(s)) != hipSuccess && rc == ALABI_OK) fail(he, "hipStreamSynchronize");
+    dev_cache_give(ws, got);
+    return rc;
+}
+
+extern "C" int alabi_chain_split_stats(const double* chain, long long n_t, long long t_stride, int n_w, int n_d, int n_split, int transform,
+                                       const double* par, double* chain_mean, double* chain_var, double* acov_mean, void* stream) {
+    if (!chain || !chain_mean || !chain_var || n_w < 1 || n_d < 1 || n_d > 65535) return ALABI_BAD_ARGUMENT;
+    if (n_split != 1 && n_split != 2) return ALABI_BAD_ARGUMENT;
+    if (transform < 0 || transform > 2 || (transform != 0 && !par)) return ALABI_BAD_ARGUMENT;
+    if (n_t < 1 || t_stride < (long long)n_w * n_d) return ALABI_BAD_ARGUMENT;
+    const long long n = n_t / n_split;                                // length of a (split) chain; the second half ends at n_t
+    if (n < 2 || n > (1LL << 21)) return ALABI_BAD_ARGUMENT;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int p = 1;                                                        // M = 2 * (next power of two >= n) = 2^p
+    for (long long q = 1; q < n; q <<= 1) ++p;
+    if (p < 4) p = 4;
+    const int M1 = 1 << (p / 2), M2 = 1 << (p - p / 2);
+    const long long M = (long long)M1 * M2;
+    int J = 4096 / M1;
+    if (J > 16) J = 16;
+    if (J > M2) J = M2;
+    const int m = n_split * n_w;                                      // chains
+    const bool acov = acov_mean != nullptr;
+    // chains per batch: <= 1 GB of complex scratch (moments only: of transposed rows)
+    long long cb = ((1LL << 30) / (acov ? M * 16 : n * 8)) / n_d;
+    if (cb > 65535 / n_d) cb = 65535 / n_d;                           // a batch's series are a grid's y extent
+    if (cb < 1) cb = 1;
+    if (cb > m) cb = m;
+    const long long sb_max = cb * n_d, ldx = n, ldr = n;
+    const size_t bytes_Z = acov ? (size_t)sb_max * M * sizeof(cplx) : 0, bytes_x = (size_t)sb_max * ldx * sizeof(double);
+    const size_t need = bytes_Z + (acov ? 2 : 1) * bytes_x + 1024;
+    void* ws = nullptr;
+    size_t got = 0;
+    if (dev_alloc_cached(&ws, need, &got) != (int)hipSuccess) return hip_fail(hipErrorOutOfMemory, "hipMalloc(chain statistics workspace)", __FILE__, __LINE__);
+    cplx* Z = reinterpret_cast<cplx*>(ws);
+    double* xt = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + bytes_Z);
+    double* R = xt + (size_t)sb_max * ldx;
+    const size_t lds_cols = (size_t)2 * M1 * J * sizeof(cplx), lds_rows = (size_t)2 * M2 * sizeof(cplx);
+    const double scale = 1.0 / ((double)M * (double)n * (double)m);   // the transforms are unnormalised: R = M sum y[t] y[t + lag]
+    int rc = ALABI_OK;
+    auto fail = [&](hipError_t e, const char* what) { rc = hip_fail(e, what, __FILE__, __LINE__); };
+    hipError_t he;
+    if (acov) {
+        if ((he = hipFuncSetAttribute(reinterpret_cast<const void*>(acf_cols_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 131072)) != hipSuccess) fail(he, "hipFuncSetAttribute");
+        if ((he = hipFuncSetAttribute(reinterpret_cast<const void*>(acf_cols_inv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 131072)) != hipSuccess) fail(he, "hipFuncSetAttribute");
+        if ((he = hipFuncSetAttribute(reinterpret_cast<const void*>(acf_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 131072)) != hipSuccess) fail(he, "hipFuncSetAttribute");
+    }
+    for (int c0 = 0; c0 < m && rc == ALABI_OK; c0 += (int)cb) {
+        const int ncb = (int)((m - c0) < cb ? (m - c0) : cb), ns = ncb * n_d;
+        double* mean = chain_mean + (size_t)c0 * n_d;                 // series s of the batch is element c0 * n_d + s of [m][n_d]
+        hipLaunchKernelGGL(acf_split_transpose_kernel, dim3((unsigned)((n + 63) / 64), (ns + 63) / 64), dim3(256), 0, s, chain, n, t_stride,
+                           n_t - n, n_w, n_d, c0, ns, transform, par, xt, ldx);
+        hipLaunchKernelGGL(acf_moments_kernel, dim3(ns), dim3(256), 0, s, xt, n, ldx, mean, chain_var + (size_t)c0 * n_d);
+        if (acov) {
+            hipLaunchKernelGGL(acf_cols_fwd_kernel, dim3(M2 / J, ns), dim3(256), lds_cols, s, xt, mean, n, ldx, M1, M2, J, Z);
+            hipLaunchKernelGGL(acf_rows_kernel, dim3(M1, ns), dim3(256), lds_rows, s, Z, M1, M2);
+            hipLaunchKernelGGL(acf_cols_inv_kernel, dim3(M2 / J, ns), dim3(256), lds_cols, s, Z, n, M1, M2, J, R, ldr);
+            hipLaunchKernelGGL(acf_cov_reduce_kernel, dim3((unsigned)((n + 255) / 256), n_d), dim3(256), 0, s, R, ldr, n, ncb, n_d, scale,
+                               c0 == 0 ? 1 : 0, acov_mean);
+        }
+        if ((he = hipGetLastError()) != hipSuccess) fail(he, "chain statistics kernels");
+    }
     if ((he = hipStreamSynchronize(s)) != hipSuccess && rc == ALABI_OK) fail(he, "hipStreamSynchronize");
     dev_cache_give(ws, got);
     return rc;

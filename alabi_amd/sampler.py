@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from .gp import HipGP, _dev, _to_dev
+from . import diagnostics
 from .mcmc_utils import integrated_time
 from .moves import parse_moves
 
@@ -855,6 +856,7 @@ class EnsembleSampler:
         self._naccept.zero_()
         self.iteration = 0
         self._tau_memo = None
+        self._diag_memo = None
 
     # -------------------------------------------------------------------------- results
     def get_chain_device(self, discard=0, thin=1, flat=False, log_prob=False):
@@ -893,3 +895,24 @@ class EnsembleSampler:
         tau = thin * integrated_time(x, **kwargs)
         self._tau_memo = (key, np.array(tau, copy=True))
         return tau
+
+    def diagnostics(self, discard=0, thin=1):
+        """Rank-normalised split R-hat, bulk / tail / mean ESS and the MCSE of the mean of the stored chain (Vehtari et al. 2021;
+        alabi_amd/diagnostics.py ``summary``): a dict of [ndim] arrays mean, sd, mcse_mean, ess_mean, ess_bulk, ess_tail, rhat, in
+        the sampler's coordinates.  The discard / thin view of the chain is read in place on the device; the result is remembered
+        until the chain grows or is reset.  Every walker counts as a chain: the walkers are independent under the metropolis, hmc
+        and nuts moves; under the red-blue ensemble moves the walkers of one ensemble are coupled -- R-hat still detects
+        disagreement, but the ESS formula assumes independent chains and is approximate there."""
+        key = (self.iteration, len(self._chains), int(discard), int(thin))
+        memo = getattr(self, "_diag_memo", None)
+        if memo is None or memo[0] != key:
+            memo = self._diag_memo = (key, diagnostics.summary(self.get_chain_device(discard=discard, thin=thin)))
+        return {k: v.copy() for k, v in memo[1].items()}
+
+    def get_rhat(self, discard=0, thin=1):
+        return self.diagnostics(discard, thin)["rhat"]
+
+    def get_ess(self, method="bulk", discard=0, thin=1):
+        if method not in ("bulk", "tail", "mean"):
+            raise ValueError("method must be 'bulk', 'tail' or 'mean'")
+        return self.diagnostics(discard, thin)["ess_" + method]

@@ -508,6 +508,18 @@ int alabi_ens_boundary_stats(alabi_ens* ens, long long* out /* host [4] */);
  * transforms in LDS (alabi_amd/csrc/chain_acf.hip): no run-time kernel compilation per transform length.  n_t <= 2^21.  The Sokal
  * window and tau = 2 cumsum(acf) - 1 follow on the host (alabi_amd/mcmc_utils.py).  Synchronises the stream. */
 int alabi_chain_autocorr(const double* chain, long long n_t, int n_w, int n_d, double* acf_mean, void* stream);
+/* The device half of the chain diagnostics of Vehtari et al. (2021) (alabi_amd/diagnostics.py: split R-hat, bulk / tail ESS, MCSE):
+ * per-chain moments and the chain-averaged, UN-normalised autocovariance of the (split) chains of a run.
+ * Element (t, w, k) lies at chain[t * t_stride + w * n_d + k] (t_stride >= n_w * n_d: a discard / thin view is read in place).
+ * n = n_t / n_split; split chain c = half * n_w + w holds the steps [0, n) (half 0) or [n_t - n, n_t) (half 1) of walker w.
+ * transform is applied on load: 0 y = x, 1 y = 1[x <= par[k]], 2 y = |x - par[k]| (par [n_d] device; may be NULL for 0).
+ *   chain_mean, chain_var [n_split * n_w, n_d]   mean and variance (ddof 1) of every split chain: direct two-pass sums
+ *   acov_mean [n_d, n]                           mean over the chains c of gamma_c(lag) = (1/n) sum_{t < n - lag} (y[t] - mean)(y[t + lag] - mean),
+ *                                                by the transforms of alabi_chain_autocorr; NULL: moments only, no transform runs
+ * ALABI_BAD_ARGUMENT: n_split not 1 or 2, n < 2, n > 2^21, t_stride < n_w * n_d, transform not 0..2, transform != 0 without par.
+ * Synchronises the stream. */
+int alabi_chain_split_stats(const double* chain, long long n_t, long long t_stride, int n_w, int n_d, int n_split, int transform,
+                            const double* par, double* chain_mean, double* chain_var, double* acov_mean, void* stream);
 
 /* Multi-GPU building blocks for ONE sharded ensemble (n_ensembles == 1; alabi_amd/dist.py
  * drives them around an RCCL all-gather): draw the proposal records of steps
